@@ -21,10 +21,15 @@ its (periodic) episode cycle — the nets-left distribution is then stationary a
 `value` counts REAL env-steps (a slot that spends the step re-initialising a finished episode is not counted) over all
 ranks / max-rank time.
 
-The JSON line also carries `roofline` (the step kernel, HIP-event timed live on its launch stream), `kernels` (per kernel:
-the step kernel, the route-only kernel xr_batch_step, and — rank 0, N = 1 — the BASELINE config 5 route kernel on
-256x256x12 regions, each with its own bytes / ms / fraction), `parity` (oracle replay of the run's own actions) and
-`cpu_baseline` (the C oracle on the host cores: one thread and all cores, bounded samples).
+The JSON line also carries `roofline` and `kernels` (the step kernel, HIP-event timed live on its launch stream during the timed
+steps).  A plain one-GPU run stops there: set-up, warm-up, the timed steps, `--dump-outputs`, the line.  `--full` adds everything that
+takes runs of its own: more `kernels` (rank 0, N = 1: the route-only kernel xr_batch_step, the in-place step, BASELINE configs 2 and 5,
+XR-Maze v2 and the design-derived region pack, each with its own bytes / ms / fraction), `extras` (configs 1, 3 and 4 with the agents
+attached, the sustained step), `parity` (oracle replay of the run's own actions) and `cpu_baseline` (the C oracle on the host cores: one
+thread and all cores, bounded samples).  With N > 1 ranks the oracle replay always runs: it certifies the N-GPU line.
+
+`--dump-outputs DIR` writes what the timed path handed its caller after the last timed step as float64 / float32 .npy files (at most
+64 MB, `dump_outputs`); the inputs depend on the arguments only, so two builds can be compared output for output.
 """
 import argparse
 import hashlib
@@ -112,7 +117,15 @@ def parse():
                          "run of the multi-GPU code path on one GPU (also: XR_FORCE_COLLECTIVES=1); the line says so in config.forced_collectives")
     ap.add_argument("--pmc-calibrate", action="store_true",
                     help="run 1 GiB fill/add kernels first (known HBM byte counts for rocprofv3 --pmc passes)")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="also the legs that take runs of their own: per-kernel legs, extras, oracle replay (parity) and CPU baseline "
+                         "(--no-legs / --no-extras / --no-cpu-baseline still drop theirs)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed path computed in its last step to DIR/<name>.npy (float64 / float32, <= 64 MB)")
+    args = ap.parse_args()
+    if args.dump_outputs and args.agent:
+        ap.error("--dump-outputs covers the env-only line, not --agent")
+    return args
 
 
 def source_sha():
@@ -237,6 +250,57 @@ def obs_sample_sha(obs, nlegal, slot_regions, n_check=256, n_sample=32, head_onl
         size = (2 if head_only else 2 + 7 * int(nl[e])) * slot_regions[e].n_nodes          # head_only: the compact-consumer step's planes 0..1
         out[e] = (int(nl[e]), hashlib.sha256(obs[e, :size].cpu().numpy().tobytes()).hexdigest())
     return out
+
+
+DUMP_SAMPLE_SEED = 0xD0D0
+DUMP_OBS_PER_ENV = 8192         # observation values sampled per sampled env
+
+
+def dump_outputs(dirname, batch, acts, obs, seed):
+    """`--dump-outputs DIR`: what the timed path handed its caller after the LAST timed step, right after the timed region (nothing
+    has touched the batch since), as .npy files of at most 64 MB in all.  Every env: the actions it took (actions.npy) and every field
+    of its result record (record_<field>.npy, float64: exact for these integers and the f64 reward), its hash chain as two 32-bit halves
+    (hash_lo.npy, hash_hi.npy).  A fixed sample of envs (seeded, the same for the same arguments; observation_envs.npy): planes 0..1 of
+    the fp32 observation (observation_head.npy, [E, 2*N], zero past the env's N), DUMP_OBS_PER_ENV values at seeded positions inside
+    the env's (2+7K)*N floats (observation_sample.npy + observation_sample_pos.npy, float32: the positions are < 2^24) and the routed
+    path's node ids (path.npy, -1 past path_len)."""
+    import numpy as np
+    import torch
+    os.makedirs(dirname, exist_ok=True)
+
+    def save(name, a):
+        np.save(os.path.join(dirname, name + ".npy"), a)
+
+    rec = batch.records()
+    save("actions", acts.cpu().numpy().astype(np.float64))
+    for f in rec.dtype.names:
+        if f != "pad":
+            save("record_" + f, rec[f].astype(np.float64))
+    h = batch.fetch("hash").cpu().numpy().view(np.uint64)
+    save("hash_lo", (h & np.uint64(0xFFFFFFFF)).astype(np.float64))
+    save("hash_hi", (h >> np.uint64(32)).astype(np.float64))
+    B = batch.n_envs
+    n_max = batch.n_max
+    E = max(1, min(256, B, (16 << 20) // (8 * n_max)))          # observation_head <= 16 MB
+    rng = np.random.default_rng([seed, DUMP_SAMPLE_SEED])
+    envs = np.sort(rng.choice(B, size=E, replace=False))
+    save("observation_envs", envs.astype(np.float64))
+    env_t = torch.from_numpy(envs).to(obs.device if obs is not None else batch.device)
+    plen = batch.fetch("path_len").cpu().numpy()[envs]
+    path = batch.fetch("path")[env_t, :max(1, int(plen.max()))].cpu().numpy()
+    path[np.arange(path.shape[1])[None, :] >= plen[:, None]] = -1
+    save("path", path.astype(np.float32))
+    if obs is not None:
+        n_nodes = np.array([r.n_nodes for r in batch.regions], np.int64)[batch.fetch("region").cpu().numpy()[envs]]
+        valid = (2 + 7 * batch.fetch("nlegal").cpu().numpy()[envs].astype(np.int64)) * n_nodes
+        if not (0 < valid.min() and valid.max() <= obs.shape[1] and 2 * n_max <= obs.shape[1]):
+            raise RuntimeError(f"--dump-outputs: observation rows of {valid.min()}..{valid.max()} floats in a stride of {obs.shape[1]}")
+        head = obs[env_t, :2 * n_max].cpu().numpy()
+        head[np.arange(2 * n_max)[None, :] >= 2 * n_nodes[:, None]] = 0.0
+        save("observation_head", head)
+        pos = np.minimum((rng.random((E, DUMP_OBS_PER_ENV)) * valid[:, None]).astype(np.int64), valid[:, None] - 1)
+        save("observation_sample", obs[env_t[:, None], torch.from_numpy(pos).to(env_t.device)].cpu().numpy())
+        save("observation_sample_pos", pos.astype(np.float32))
 
 
 def parity_check(regions, seeds, stagger, gpu_hash, gpu_cum, n_check=256, obs_sha=None, v2=None, actions_log=None, head_only=False):
@@ -366,7 +430,7 @@ def main():
     learner_regions = None
     if args.agent and args.learner and multi and rank == 0 and not args.region_pack and args.regions == 0:
         learner_regions = gen_regions(args.config, args.global_envs if strong else args.envs * world, 0)      # the central learner's region table: every env's region
-    do_legs = (not multi) and rank == 0 and not args.no_legs and not args.region_pack
+    do_legs = args.full and (not multi) and rank == 0 and not args.no_legs and not args.region_pack
     c5_regions = gen_regions(5, min(args.c5_regions, args.c5_envs)) if do_legs and args.c5_envs > 0 else None
     pack_regions = None
     if do_legs and args.pack_envs > 0 and os.path.exists(PACK_PATH):
@@ -550,9 +614,14 @@ def main():
     real_steps = batch.total_steps() - steps0
     gpu_hash = batch.fetch("hash").cpu().numpy().view("uint64")          # state right after the timed region
     gpu_cum = batch.fetch("cum").cpu().numpy()
+    if args.dump_outputs and rank == 0 and nsteps_total > 0:
+        dump_outputs(args.dump_outputs, batch, acts, obs, args.seed)
+    # oracle replay (`parity`): --full, or N > 1 where it certifies the line
+    can_replay = not args.region_pack and (len(regions) >= B or args.regions > 0)      # regions == env slots: rotation keeps every slot on its region (--regions: no rotation), the oracle subset can follow
+    replay = can_replay and (multi or (args.full and not args.no_cpu_baseline))
     # bytes of the observation the LAST timed launch wrote, for envs spread over K (compared with the oracle in `parity`)
     obs_sha = None
-    if obs is not None and nsteps_total > 0:
+    if replay and obs is not None and nsteps_total > 0:
         obs_sha = obs_sample_sha(obs, nlegal_log[nsteps_total - 1], slot_regions[:n_par], n_check=n_par)
 
     # ---- N > 1: the run certifies itself — the gather delivered every rank's records, and every rank's envs replay on the oracle
@@ -741,8 +810,7 @@ def main():
                 "avg_launch_ms": round(dom["ms"], 4), "algorithmic_bytes_per_launch": int(dom["bytes"])}
 
     parity = None
-    can_replay = not args.region_pack and (len(regions) >= B or args.regions > 0)      # regions == env slots: rotation keeps every slot on its region (--regions: no rotation), the oracle subset can follow
-    if can_replay and (multi or not args.no_cpu_baseline):
+    if replay:
         try:
             seeds = [args.seed + rank * 7919 + i for i in range(args.warmup + args.steps)]
             parity = parity_check(slot_regions, seeds, stagger, gpu_hash, gpu_cum, n_check=n_par, obs_sha=obs_sha,
@@ -806,7 +874,7 @@ def main():
             out["extras"] = extras_leg(args, regions, dev, batch, obs)
             if sustained is not None:
                 out["extras"]["sustained"] = sustained
-        if (not multi) and not args.no_cpu_baseline:
+        if (not multi) and args.full and not args.no_cpu_baseline:
             try:
                 out["cpu_baseline"] = cpu_baseline(regions, args.cpu_seconds, with_obs=with_obs)
             except Exception as ex:          # the oracle is optional for the GPU number itself

@@ -1,4 +1,4 @@
-"""bench.py contract on the GPU box (tiny run): one JSON line with the driver's keys, roofline and cpu_baseline."""
+"""bench.py contract on the GPU box (tiny runs): one JSON line with the driver's keys; --full adds the legs, parity and cpu_baseline."""
 import json
 import os
 import subprocess
@@ -12,7 +12,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 def _run(extra):
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
-                          "--envs", "256", "--cpu-seconds", "2", "--c5-envs", "8", "--c5-regions", "2", "--pack-envs", "512"] + extra, capture_output=True, text=True, timeout=600)
+                          "--envs", "256", "--cpu-seconds", "2", "--c5-envs", "8", "--c5-regions", "2", "--pack-envs", "512", "--full"] + extra, capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1
@@ -88,6 +88,36 @@ def test_bench_json_contract(extra):
     assert p["observations_equal"] is True and p["observations_checked"] == 32 and p["ok"] is True
     # value is consistent with the reported step time: real env-steps <= slots
     assert d["value"] <= 256 * 1 / (d["ms_per_step"] * 1e-3) * 1.001
+
+
+def test_bench_plain_run_is_lean_and_dumps_its_outputs(tmp_path):
+    """A plain run (no --full) is set-up, warm-up, the timed steps and the line: the headline keys, no leg, no oracle replay, no CPU
+    baseline.  --dump-outputs writes the last timed step's outputs as float32 / float64 .npy files, <= 64 MB, the same bytes for the
+    same arguments; --steps is the number of timed steps."""
+    import numpy as np
+    runs = []
+    for tag in ("a", "b"):
+        out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "4", "--warmup", "2", "--envs", "256",
+                              "--dump-outputs", str(tmp_path / tag)], capture_output=True, text=True, timeout=600)
+        assert out.returncode == 0, out.stderr[-2000:]
+        lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
+        assert len(lines) == 1
+        d = json.loads(lines[0])
+        for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+            assert k in d, k
+        assert d["steps"] == 4 and d["unit"] == "env-steps/s" and d["value"] > 0 and d["ms_per_step"] > 0
+        assert "parity" not in d and "cpu_baseline" not in d and "extras" not in d
+        assert [k["kernel"] for k in d["kernels"]] == ["xr_step_queue_kernel"]
+        files = sorted(os.listdir(tmp_path / tag))
+        assert {"actions.npy", "record_reward.npy", "record_nlegal.npy", "hash_lo.npy", "observation_sample.npy", "observation_head.npy"} <= set(files)
+        assert sum(os.path.getsize(tmp_path / tag / f) for f in files) <= 64 << 20
+        arrays = {f: np.load(tmp_path / tag / f) for f in files}
+        assert all(a.dtype in (np.float32, np.float64) for a in arrays.values())
+        assert arrays["actions.npy"].shape == (256,) and (arrays["record_nlegal.npy"] >= 0).all()
+        runs.append(arrays)
+    assert runs[0].keys() == runs[1].keys()
+    for f in runs[0]:
+        assert np.array_equal(runs[0][f], runs[1][f]), f
 
 
 @pytest.mark.gpu

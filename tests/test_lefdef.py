@@ -1,7 +1,9 @@
 """Row f3 (next): LEF/DEF/guide -> regions.  No oracle exists for this step (pin access is TritonRoute's own);
 the tests check the parsers against the counts the files declare, the documented rules on the small ispd18_sample
 design, and that the committed region pack (extracted from ispd18_test1) round-trips and is routable."""
+import gzip
 import os
+import shutil
 
 import numpy as np
 import pytest
@@ -10,16 +12,24 @@ from tests.helpers import GOLDEN
 from xroute_env_amd import lefdef
 from xroute_env_amd.regions import ACCESS, BLOCKAGE, unpack_records
 
-REF = "/root/reference"
-SAMPLE = os.path.join(REF, "simulator/testcases/ispd18_sample/ispd18_sample.input")
-TEST1 = os.path.join(REF, "ispd/ispd18_test1/ispd18_test1.input")
-needs_ref = pytest.mark.skipif(not os.path.exists(SAMPLE + ".def"), reason="reference inputs only exist in the build container")
 PACK = os.path.join(GOLDEN, "ispd18_test1_regions.npz")
 
 
-@needs_ref
-def test_parsers_match_declared_counts():
-    d = lefdef.load_design(TEST1 + ".lef", TEST1 + ".def", TEST1 + ".guide")
+@pytest.fixture(scope="module")
+def ref_input(tmp_path_factory):
+    """The reference's ispd18_sample / ispd18_test1 LEF, DEF and guide files, kept gzipped under tests/golden/
+    (tools/gen_golden_ref_inputs.py) and unpacked here: stem -> path prefix of its three files."""
+    d = tmp_path_factory.mktemp("ref_input")
+    for stem in ("ispd18_sample.input", "ispd18_test1.input"):
+        for ext in ("lef", "def", "guide"):
+            with gzip.open(os.path.join(GOLDEN, f"{stem}.{ext}.gz"), "rb") as fi, open(d / f"{stem}.{ext}", "wb") as fo:
+                shutil.copyfileobj(fi, fo)
+    return lambda stem: str(d / stem)
+
+
+def test_parsers_match_declared_counts(ref_input):
+    test1 = ref_input("ispd18_test1.input")
+    d = lefdef.load_design(test1 + ".lef", test1 + ".def", test1 + ".guide")
     assert d.dbu == 2000 and d.die == (0, 0, 390800, 383040)                  # def:5-7
     assert len(d.components) == 8879 and len(d.nets) == 3153                   # def:254, :9142
     assert d.layers == [f"Metal{i}" for i in range(1, 10)]
@@ -32,9 +42,9 @@ def test_parsers_match_declared_counts():
     assert m.pins["VDD"]["use"] == "POWER" and len(m.pins["Y"]["rects"]) == 10
 
 
-@needs_ref
-def test_sample_design_region_follows_the_rules():
-    d = lefdef.load_design(SAMPLE + ".lef", SAMPLE + ".def", SAMPLE + ".guide")
+def test_sample_design_region_follows_the_rules(ref_input):
+    sample = ref_input("ispd18_sample.input")
+    d = lefdef.load_design(sample + ".lef", sample + ".def", sample + ".guide")
     assert len(d.components) == 22 and len(d.nets) == 11
     ex = lefdef.RegionExtractor(d)
     reg = ex.extract(d.die, "whole")
@@ -118,11 +128,7 @@ def test_pack_regions_gpu_parity():
     assert [int(h) for h in batch.fetch("hash").cpu().numpy().view(np.uint64)] == [e.hash() for e in envs]
 
 
-REF_INPUT = "/root/reference/ispd/ispd18_test1/ispd18_test1.input"
-
-
-@pytest.mark.skipif(not os.path.exists(REF_INPUT + ".def"), reason="the reference's ispd18_test1 inputs only exist in the build container")
-def test_static_region1_matches_the_reference_record():
+def test_static_region1_matches_the_reference_record(ref_input):
     """SANITY, NOT PARITY (row f3).  The one region the reference describes, xroute_env/__init__.py:13-23: ISPD-2018 test1, size 1x1,
     position (199500, 245100)-(205200, 250800), "net": 36, "pin": 30 — and the one run it recorded (tests/golden/g8_ppo_episode_stats.json:
     717 episodes over the 1x1 regions of the same design, 7.95 steps = routed nets per episode, 44 961 DBU of wirelength per episode).
@@ -133,7 +139,8 @@ def test_static_region1_matches_the_reference_record():
     halo 0 / 500 / 2000 with 24.4 nets per region die-wide — three times the recorded steps per episode.  Die-wide the new rule gives
     7.7 nets per non-empty region (record 7.95) and 6.1 k DBU per routed net on the oracle (record 5.66 k): the numbers asserted here."""
     from oracle import xr_oracle as orc
-    d = lefdef.load_design(REF_INPUT + ".lef", REF_INPUT + ".def", REF_INPUT + ".guide")
+    test1 = ref_input("ispd18_test1.input")
+    d = lefdef.load_design(test1 + ".lef", test1 + ".def", test1 + ".guide")
     ex = lefdef.RegionExtractor(d)
     rb = (199500, 245100, 205200, 250800)
     box = (rb[0] - 2000, rb[1] - 2000, rb[2] + 2000, rb[3] + 2000)

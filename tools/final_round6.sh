@@ -7,7 +7,7 @@ TAG=${1:-r06_z}
 R=${GRAFT_REPO_ROOT:-$(pwd)}; OUT=$R/gpurun_out/$TAG; mkdir -p $OUT; cd $R
 export TMPDIR=/tmp
 timeout 1800 python -m pytest tests -x -q -m gpu > $OUT/pytest_gpu.log 2>&1; echo "suite rc=$?"; tail -3 $OUT/pytest_gpu.log
-S0=$SECONDS; timeout 900 python bench.py > $OUT/bench.json 2> $OUT/bench.err; echo "python bench.py (the driver's command): $((SECONDS - S0)) s of wall clock" | tee $OUT/bench_wall_seconds.txt; tail -c 1600 $OUT/bench.json; echo
+S0=$SECONDS; timeout 900 python bench.py --full > $OUT/bench.json 2> $OUT/bench.err; echo "python bench.py (the driver's command): $((SECONDS - S0)) s of wall clock" | tee $OUT/bench_wall_seconds.txt; tail -c 1600 $OUT/bench.json; echo
 cd /tmp; export XR_BENCH_NO_FORK=1
 prof() {   # name, bench args...: kernel stats + PMC traffic of one command
     local name=$1; shift
