@@ -363,6 +363,42 @@ int32_t xr_batch_fetch(xr_batch* b, int32_t what, void* dst_dev, size_t dst_byte
  * a batch restored into a twin created with the same config and regions continues bit-identically (hash chains included). */
 int32_t xr_batch_store(xr_batch* b, int32_t what, const void* src_dev, size_t src_bytes, void* stream);
 
+/* ---- env groups: step subsets of the slots independently, each on its own stream --------------- */
+/* The reference never steps its envs in lock-step: A3C runs 8 workers with a simulator port each (baseline/A3C/discrete_A3C.py:246-247),
+ * MCTS 32 Ray workers (baseline/xroute/net_order.py:34), trainer4 N server processes (baseline/xroute/trainer4/launcher.sh:10-12).  Every
+ * per-env state lives in per-env rows and the region rotation and the built-in random policy are functions of the env's own counters, so
+ * an env's trajectory depends on its own action sequence only: any interleaving of group steps equals the lock-step batch, env by env.
+ *
+ * xr_batch_set_groups     declares a partition of the slots: group g = slots [bounds_host[g], bounds_host[g + 1]); n_groups + 1 strictly
+ *                         ascending values from 0 to n_envs (no empty group), 1 <= n_groups <= XR_MAX_GROUPS.  n_groups == 1 is the
+ *                         default (one group = the whole batch).  It may allocate and synchronise: no work of the batch may be in flight
+ *                         when it is called.  A reload of the regions keeps the partition.
+ * xr_batch_step_group     steps envs [lo, hi) of `group`: actions_dev[i] belongs to env lo + i.  out_dev == NULL: route only, like
+ *                         xr_batch_step.  Else also the observation of env lo + i at out_dev + i*env_stride, byte-identical to
+ *                         xr_batch_step_observe (the queue form where the batch takes it, else the fused form; never the split form or
+ *                         the helper writers, whose internal stream belongs to the batch).  flags & XR_GROUP_INPLACE: the in-place form
+ *                         of xr_batch_step_observe_inplace, its validity tracked per group (a group's buffer is valid after a step of
+ *                         that group, or an xr_batch_observation that covered the group, into it).  Any whole-batch call that changes
+ *                         state invalidates every group's buffer; a group step invalidates the batch-wide one (the next
+ *                         xr_batch_step_observe_inplace writes everything).
+ * xr_batch_random_actions_group   xr_batch_random_actions for envs [lo, hi): actions_dev[i] for env lo + i (the same action env lo + i
+ *                         gets from the whole-batch call at the same env_steps).
+ * xr_batch_fetch_group    xr_batch_fetch of the group's rows of a per-env array: XR_FETCH_RECORD, _REWARD, _DONE, _NLEGAL, _STATUS, _LEGAL,
+ *                         _DELTA, _CUM, _PATH_LEN, _PATH, _OWNER, _HASH, _REGION, _SWEEPS, _REPLAY, _ENV_STEPS (batch-wide selectors:
+ *                         XR_ERR_INVALID); dst_bytes must equal the slice's size exactly (else XR_ERR_RANGE).
+ *
+ * Concurrency contract.  Host calls on one batch stay serialised, as everywhere.  Device work of DIFFERENT groups may run concurrently on
+ * different streams (they share no queue counters, unit lists, route orders or rows; the persistent step launch never has a workgroup
+ * wait for another, so launches sized for the whole chip may share it).  Work of one group is ordered by the caller (one stream per group,
+ * or events).  A whole-batch call must be ordered after all outstanding group work (and a group step after outstanding whole-batch work). */
+#define XR_MAX_GROUPS 64
+#define XR_GROUP_INPLACE 1
+int32_t xr_batch_set_groups(xr_batch* b, const int32_t* bounds_host, int32_t n_groups);
+int32_t xr_batch_step_group(xr_batch* b, int32_t group, const int32_t* actions_dev, float* out_dev, int64_t env_stride, int32_t flags,
+                            void* stream);
+int32_t xr_batch_random_actions_group(xr_batch* b, int32_t group, int32_t* actions_dev, uint64_t seed, void* stream);
+int32_t xr_batch_fetch_group(xr_batch* b, int32_t group, int32_t what, void* dst_dev, size_t dst_bytes, void* stream);
+
 /* ---- XR-Maze v2: global-route guides (optional) ---------------------------------------------- */
 /* The reference's simulator runs with `-follow_guide 1` (ispd/ispd18_test1/run-net-ordering-training.tcl:3) on the guide file
  * it ships (ispd/ispd18_test1/ispd18_test1.input.guide: per net, rectangles per metal layer).  With xr_config.guide_cost > 0 a

@@ -30,6 +30,7 @@ SYMBOLS = [
     "xr_batch_reset", "xr_batch_step", "xr_batch_step_observe", "xr_batch_step_observe_inplace", "xr_batch_step_compact", "xr_batch_net_planes", "xr_batch_route_order", "xr_batch_observe_timing", "xr_batch_route_occupancy", "xr_batch_random_actions", "xr_batch_observation", "xr_batch_fetch", "xr_batch_store", "xr_batch_load_guides",
     "xr_batch_state_row_bytes", "xr_batch_pack_state", "xr_batch_expand_state", "xr_batch_ingest_state",
     "xr_agent_obstacle_tower_weights", "xr_agent_obstacle_tower", "xr_agent_net_tower_weights", "xr_agent_matrix_mode", "xr_batch_net_vectors", "xr_agent_actor_weights", "xr_agent_actor", "xr_agent_actor_sample",
+    "xr_batch_set_groups", "xr_batch_step_group", "xr_batch_random_actions_group", "xr_batch_fetch_group",
     "xr_observation_from_records", "xr_proto_decode", "xr_proto_encode_response", "xr_proto_encode_request",
 ]
 
@@ -53,6 +54,7 @@ class XrStepRecord(C.Structure):          # include/xroute_hip.h xr_step_record 
 
 
 RECORD_BYTES = 48
+XR_MAX_GROUPS, XR_GROUP_INPLACE = 64, 1
 XR_ROUTER_SWEEP, XR_ROUTER_DIAL = 1, 2
 
 
@@ -113,6 +115,10 @@ def lib():
     L.xr_batch_pack_state.argtypes = [vp, vp, C.c_int64, C.c_int32, vp]
     L.xr_batch_expand_state.argtypes = [vp, vp, C.c_int64, C.c_int32, vp, C.c_int64, vp, vp, vp]
     L.xr_batch_ingest_state.argtypes = [vp, vp, vp, vp, vp]
+    L.xr_batch_set_groups.argtypes = [vp, vp, C.c_int32]
+    L.xr_batch_step_group.argtypes = [vp, C.c_int32, vp, vp, C.c_int64, C.c_int32, vp]
+    L.xr_batch_random_actions_group.argtypes = [vp, C.c_int32, vp, C.c_uint64, vp]
+    L.xr_batch_fetch_group.argtypes = [vp, C.c_int32, C.c_int32, vp, C.c_size_t, vp]
     L.xr_agent_obstacle_tower_weights.argtypes = []
     L.xr_agent_obstacle_tower.argtypes = [vp, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, vp, vp, C.c_int32, vp]
     L.xr_agent_net_tower_weights.argtypes = []

@@ -33,6 +33,27 @@ def _stream_ptr(dev) -> C.c_void_p:
     return C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
 
 
+def partition_bounds(groups, n_envs: int) -> List[int]:
+    """Env-group bounds [0, b1, ..., n_envs] of `groups`: an int G (G near-equal contiguous groups) or explicit ascending bounds.
+    Raises ValueError for what xr_batch_set_groups would refuse: empty groups, bounds not from 0 to n_envs, more than XR_MAX_GROUPS."""
+    n_envs = int(n_envs)
+    if isinstance(groups, bool):
+        raise ValueError("groups must be an int or a sequence of bounds, not a bool")
+    if isinstance(groups, (int, np.integer)):
+        g = int(groups)
+        if g < 1 or g > min(n_envs, _lib.XR_MAX_GROUPS):
+            raise ValueError(f"groups must be in 1..min(n_envs = {n_envs}, {_lib.XR_MAX_GROUPS}), got {g}")
+        return [(i * n_envs) // g for i in range(g + 1)]
+    b = [int(v) for v in groups]
+    if len(b) < 2 or len(b) - 1 > _lib.XR_MAX_GROUPS:
+        raise ValueError(f"bounds must hold 2..{_lib.XR_MAX_GROUPS + 1} values (n_groups + 1), got {len(b)}")
+    if b[0] != 0 or b[-1] != n_envs:
+        raise ValueError(f"bounds must run from 0 to n_envs = {n_envs}, got {b[0]} .. {b[-1]}")
+    if any(hi <= lo for lo, hi in zip(b, b[1:])):
+        raise ValueError("bounds must be strictly ascending: no group may be empty")
+    return b
+
+
 class RegionBatch:
     """B env slots playing a set of regions.  Mirrors, per env, the reference's Game
     (baseline/baseline_utils.py:383-481): reset() / step(actions) / observation()."""
@@ -173,6 +194,85 @@ class RegionBatch:
                 _lib.check(fn(self._h, C.c_void_p(actions.data_ptr()), C.c_void_p(obs_out.data_ptr()), obs_out.shape[1],
                               _stream_ptr(self.device)))
         return obs_out
+
+    # ---- env groups: subsets of the slots stepped independently, each on its own stream (include/xroute_hip.h) ------------------
+    def set_groups(self, bounds):
+        """Partition the slots into env groups: `bounds` = [0, b1, ..., n_envs] strictly ascending, or an int G (near-equal groups).
+        No work of the batch may be in flight (xr_batch_set_groups may synchronise)."""
+        b = np.ascontiguousarray(partition_bounds(bounds, self.n_envs), np.int32)
+        with torch.cuda.device(self.device):
+            _lib.check(self.L.xr_batch_set_groups(self._h, b.ctypes.data, b.size - 1))
+        self._group_bounds = [int(v) for v in b]
+
+    @property
+    def n_groups(self) -> int:
+        return len(self._bounds()) - 1
+
+    def _bounds(self) -> List[int]:
+        return getattr(self, "_group_bounds", None) or [0, self.n_envs]
+
+    def group_bounds(self, g: int):
+        """(lo, hi): group g is slots [lo, hi)."""
+        b = self._bounds()
+        if not 0 <= int(g) < len(b) - 1:
+            raise ValueError(f"group {g} outside 0..{len(b) - 2}")
+        return b[int(g)], b[int(g) + 1]
+
+    def _stream_arg(self, stream) -> C.c_void_p:
+        return C.c_void_p((stream if stream is not None else torch.cuda.current_stream(self.device)).cuda_stream)
+
+    def step_group(self, g: int, actions: torch.Tensor, obs_out: Optional[torch.Tensor] = None, inplace: bool = False, stream=None):
+        """step() for the envs of group g only (xr_batch_step_group), enqueued on `stream` (default: the current stream): actions int32
+        [hi - lo] (entry i = env lo + i); obs_out ([hi - lo, stride] fp32, e.g. rows lo:hi of the batch's buffer) receives env lo + i's
+        observation in row i.  `inplace`: obs_out holds the group's previous observation (the in-place form, validity tracked per group)."""
+        lo, hi = self.group_bounds(g)
+        if actions.device != self.device or actions.dtype != torch.int32 or not actions.is_contiguous() or actions.numel() != hi - lo:
+            raise ValueError("actions must be a contiguous int32 tensor of the group's size on the batch device")
+        out_ptr, stride = None, 0
+        if obs_out is not None:
+            if obs_out.device != self.device or obs_out.dtype != torch.float32 or not obs_out.is_contiguous() \
+                    or obs_out.dim() != 2 or obs_out.shape[0] < hi - lo:
+                raise ValueError("obs_out must be a contiguous fp32 [group size, stride] tensor on the batch device")
+            out_ptr, stride = C.c_void_p(obs_out.data_ptr()), int(obs_out.shape[1])
+        flags = _lib.XR_GROUP_INPLACE if (inplace and obs_out is not None) else 0
+        with torch.cuda.device(self.device):
+            _lib.check(self.L.xr_batch_step_group(self._h, int(g), C.c_void_p(actions.data_ptr()), out_ptr, stride, flags,
+                                                  self._stream_arg(stream)))
+        return obs_out
+
+    def random_actions_group(self, g: int, seed: int, out: Optional[torch.Tensor] = None, stream=None) -> torch.Tensor:
+        """random_actions() for the envs of group g: out int32 [hi - lo], entry i = env lo + i."""
+        lo, hi = self.group_bounds(g)
+        if out is None:
+            with torch.cuda.stream(stream if stream is not None else torch.cuda.current_stream(self.device)):
+                out = torch.empty(hi - lo, dtype=torch.int32, device=self.device)
+        if out.device != self.device or out.dtype != torch.int32 or not out.is_contiguous() or out.numel() != hi - lo:
+            raise ValueError("out must be a contiguous int32 tensor of the group's size on the batch device")
+        with torch.cuda.device(self.device):
+            _lib.check(self.L.xr_batch_random_actions_group(self._h, int(g), C.c_void_p(out.data_ptr()), C.c_uint64(seed & (2 ** 64 - 1)),
+                                                            self._stream_arg(stream)))
+        return out
+
+    # the per-env arrays xr_batch_fetch_group copies
+    _GROUP_FETCH = ("record", "reward", "done", "nlegal", "status", "legal", "delta", "cum", "path_len", "path", "owner", "hash", "region",
+                    "sweeps", "replay", "env_steps")
+
+    def fetch_group(self, what: str, g: int, out: Optional[torch.Tensor] = None, stream=None) -> torch.Tensor:
+        """fetch() of group g's rows of a per-env array (async on `stream`, default the current stream)."""
+        if what not in self._GROUP_FETCH:
+            raise ValueError(f"fetch_group: {what!r} is not a per-env array ({', '.join(self._GROUP_FETCH)})")
+        sel, dtype, shape = self._FETCH[what]
+        lo, hi = self.group_bounds(g)
+        shp = (hi - lo,) + tuple(shape(self))[1:]
+        if out is None:
+            with torch.cuda.stream(stream if stream is not None else torch.cuda.current_stream(self.device)):
+                out = torch.empty(shp, dtype=dtype, device=self.device)
+        if out.dtype != dtype or not out.is_contiguous() or tuple(out.shape) != shp:
+            raise ValueError(f"out must be a contiguous {dtype} tensor of shape {shp}")
+        with torch.cuda.device(self.device):
+            _lib.check(self.L.xr_batch_fetch_group(self._h, int(g), sel, C.c_void_p(out.data_ptr()), out.numel() * out.element_size(),
+                                                   self._stream_arg(stream)))
+        return out
 
     def alloc_head(self) -> torch.Tensor:
         """[n_envs, 2*n_max] fp32 buffer for the compact-consumer step (planes 0..1 of every env)."""

@@ -83,6 +83,14 @@ struct DevBuf {
     ~DevBuf() { release(); }
 };
 
+// The kernels index per-env rows of the caller's buffers (actions, observation) by the ABSOLUTE slot; for an env group the base is
+// shifted back by `elems` elements so that slot lo lands on element 0 of the caller's buffer.  Only addresses of the group's own slots
+// are ever formed from it on the device.  (Integer arithmetic: the shifted address need not point into any object.)
+template <class T>
+T* shift_back(T* p, int64_t elems) {
+    return reinterpret_cast<T*>(reinterpret_cast<uintptr_t>(p) - (uintptr_t)(elems * (int64_t)sizeof(T)));
+}
+
 }  // namespace
 
 struct xr_batch {
@@ -153,6 +161,13 @@ struct xr_batch {
     int last_obs_sweeps = 0;
     const float* obs_valid_ptr = nullptr;       // buffer that holds the current observation of ALL env slots (in-place form)
     int64_t obs_valid_stride = 0;
+    // env groups (xr_batch_set_groups): group g = slots [group_bounds[g], group_bounds[g + 1]); one group = the whole batch until set
+    int n_groups = 1;
+    int32_t group_bounds[XR_MAX_GROUPS + 1] = {};
+    DevBuf<uint32_t> group_queue;               // [XR_MAX_GROUPS][2][4]: two banks of queue counters per group, alternating per group step
+    int group_bank[XR_MAX_GROUPS] = {};
+    const float* group_valid_ptr[XR_MAX_GROUPS] = {};   // per group: buffer (row 0 = the group's first slot) that holds its observation
+    int64_t group_valid_stride[XR_MAX_GROUPS] = {};
     XrBatchDev dev{};
     ~xr_batch() {
         if (ev_fork) (void)hipEventDestroy(ev_fork);
@@ -243,6 +258,8 @@ int32_t xr_batch_create(const xr_config* cfg, xr_batch** out) {
     xr_batch* b = new (std::nothrow) xr_batch();
     if (!b) return fail(XR_ERR_NOMEM, "xr_batch_create: out of host memory");
     b->cfg = *cfg;
+    b->group_bounds[0] = 0;
+    b->group_bounds[1] = cfg->n_envs;
     *out = b;
     return XR_OK;
 }
@@ -256,6 +273,12 @@ int32_t xr_batch_destroy(xr_batch* b) {
 
 static int32_t build_guide_masks(xr_batch* b, hipStream_t st);
 
+// A whole-batch call that changes env state: no caller buffer holds the current observation any more (batch-wide or per group).
+static void drop_obs_valid(xr_batch* b) {
+    b->obs_valid_ptr = nullptr;
+    for (int g = 0; g < XR_MAX_GROUPS; g++) b->group_valid_ptr[g] = nullptr;
+}
+
 int32_t xr_batch_load_regions(xr_batch* b, const xr_region_desc* regs, int32_t n_regions, void* stream) {
     if (!b || !regs || n_regions < 1) return fail(XR_ERR_INVALID, "xr_batch_load_regions: bad argument");
     XR_HIP(hipSetDevice(b->cfg.device));
@@ -264,7 +287,7 @@ int32_t xr_batch_load_regions(xr_batch* b, const xr_region_desc* regs, int32_t n
     // a reload invalidates the batch until it has completed: a failure midway must not leave `loaded` set over
     // freed or partly reallocated device buffers
     b->loaded = false;
-    b->obs_valid_ptr = nullptr;
+    drop_obs_valid(b);
     b->n_cus = 0;
     b->route_slots = 0;
     b->guide_csr.release(); b->guide_box.release(); b->guide_mask.release(); b->guide_mask_bytes = 0;        // guides belong to the regions they were loaded for
@@ -723,6 +746,7 @@ int32_t xr_batch_load_regions(xr_batch* b, const xr_region_desc* regs, int32_t n
     XR_ALLOC(b->phase_cycles, (size_t)B * 8);
     XR_ALLOC(b->plan_region, B);
     XR_ALLOC(b->queue, 8);
+    XR_ALLOC(b->group_queue, (size_t)XR_MAX_GROUPS * 8);
     XR_ALLOC(b->plan_units, (size_t)B * std::max(1, k_max));
     XR_ALLOC(b->plan_unit_net, (size_t)B * std::max(1, k_max));
     if (b->dial_big) {
@@ -786,6 +810,8 @@ int32_t xr_batch_load_regions(xr_batch* b, const xr_region_desc* regs, int32_t n
 
     XR_HIP(hipMemsetAsync(b->queue.p, 0, 8 * sizeof(uint32_t), st));       // both banks start clean; from then on every plan zeroes the other bank
     b->queue_bank = 0; b->queue_last = b->queue.p;
+    XR_HIP(hipMemsetAsync(b->group_queue.p, 0, (size_t)XR_MAX_GROUPS * 8 * sizeof(uint32_t), st));     // (the partition itself survives a reload)
+    for (int g = 0; g < XR_MAX_GROUPS; g++) b->group_bank[g] = 0;
     XR_HIP(xr_launch_ingest(b->rg_rec.p, b->rg_node_net.p, b->rg_owner0.p, (int64_t)hrec.size(), st));
     XR_HIP(hipStreamSynchronize(st));   // host staging vectors die here
 
@@ -948,15 +974,17 @@ int32_t xr_batch_reset(xr_batch* b, const uint8_t* mask_dev, int32_t rotate, voi
     if (!b) return fail(XR_ERR_INVALID, "xr_batch_reset: null batch");
     if (!b->loaded) return fail(XR_ERR_STATE, "xr_batch_reset: load regions first");
     XR_HIP(hipSetDevice(b->cfg.device));
-    b->obs_valid_ptr = nullptr;
+    drop_obs_valid(b);
     XR_HIP(xr_launch_reset(&b->dev, mask_dev, rotate ? 1 : 0, static_cast<hipStream_t>(stream)));
     return XR_OK;
 }
 
 namespace {
-// One launch over all env slots, or — stream_per_region — one single-workgroup launch per slot on a pool of internal streams
-// (fork from / join to the caller's stream with events; the host never waits).
+// One launch over the env slots of d (all of them, or one env group: d.env_base / env_count), or — stream_per_region — one
+// single-workgroup launch per slot on a pool of internal streams (fork from / join to the caller's stream with events; the host
+// never waits).  actions_dev is indexed by the absolute slot (shift_back for a group).
 int32_t launch_route_form(xr_batch* b, const XrBatchDev& d, const int32_t* actions_dev, hipStream_t st) {
+    const int lo = d.env_base, n = XR_ENV_END(d) - d.env_base;
     if (!b->cfg.stream_per_region) {
         // launch order: longest predicted route first when the launch runs in more than one round of workgroups
         bool lpt = b->cfg.launch_order == 2;
@@ -969,21 +997,20 @@ int32_t launch_route_form(xr_batch* b, const XrBatchDev& d, const int32_t* actio
                 XR_HIP(xr_route_occupancy(b->lds_dist ? 1 : 0, b->kzch, b->route_lds, b->route_threads, &per_cu, &stat));
                 b->route_slots = std::max(1, per_cu) * prop.multiProcessorCount;
             }
-            lpt = b->cfg.n_envs > b->route_slots;
+            lpt = n > b->route_slots;
         }
         if (!lpt) {
             XR_HIP(xr_launch_route(&d, actions_dev, b->lds_dist ? 1 : 0, b->kzch, b->route_lds, b->route_threads, st));
             return XR_OK;
         }
         XrBatchDev dl = d;
-        XR_HIP(xr_launch_route_order(&dl, actions_dev, b->route_order.p, st));
-        dl.route_order = b->route_order.p;
+        XR_HIP(xr_launch_route_order(&dl, actions_dev, b->route_order.p + lo, st));
+        dl.route_order = b->route_order.p + lo;
         XR_HIP(xr_launch_route(&dl, actions_dev, b->lds_dist ? 1 : 0, b->kzch, b->route_lds, b->route_threads, st));
         return XR_OK;
     }
-    const int B = b->cfg.n_envs;
     if (b->region_streams.empty()) {
-        const int ns = std::min(B, 16);
+        const int ns = std::min(b->cfg.n_envs, 16);
         for (int i = 0; i < ns; i++) {
             hipStream_t s; hipEvent_t ev;
             XR_HIP(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
@@ -994,7 +1021,7 @@ int32_t launch_route_form(xr_batch* b, const XrBatchDev& d, const int32_t* actio
     const int ns = (int)b->region_streams.size();
     XR_HIP(hipEventRecord(b->ev_fork, st));
     for (int i = 0; i < ns; i++) XR_HIP(hipStreamWaitEvent(b->region_streams[i], b->ev_fork, 0));
-    for (int e = 0; e < B; e++) {
+    for (int e = lo; e < lo + n; e++) {
         XrBatchDev de = d;
         de.env_base = e; de.env_count = 1;
         XR_HIP(xr_launch_route(&de, actions_dev, b->lds_dist ? 1 : 0, b->kzch, b->route_lds, b->route_threads, b->region_streams[e % ns]));
@@ -1011,12 +1038,13 @@ int32_t xr_batch_step(xr_batch* b, const int32_t* actions_dev, void* stream) {
     if (!b || !actions_dev) return fail(XR_ERR_INVALID, "xr_batch_step: null argument");
     if (!b->loaded) return fail(XR_ERR_STATE, "xr_batch_step: load regions first");
     XR_HIP(hipSetDevice(b->cfg.device));
-    b->obs_valid_ptr = nullptr;
+    drop_obs_valid(b);
     return launch_route_form(b, b->dev, actions_dev, static_cast<hipStream_t>(stream));
 }
 
 namespace {
-int32_t step_observe_impl(xr_batch* b, const int32_t* actions_dev, float* out_dev, int64_t env_stride, void* stream, bool inplace);
+// group < 0: the whole batch (xr_batch_step_observe*); else env group `group` (xr_batch_step_group), its slot lo at row 0 of out_dev
+int32_t step_observe_impl(xr_batch* b, const int32_t* actions_dev, float* out_dev, int64_t env_stride, void* stream, bool inplace, int group = -1);
 }
 
 int32_t xr_batch_step_observe(xr_batch* b, const int32_t* actions_dev, float* out_dev, int64_t env_stride, void* stream) {
@@ -1028,7 +1056,7 @@ int32_t xr_batch_step_observe_inplace(xr_batch* b, const int32_t* actions_dev, f
 }
 
 namespace {
-int32_t step_observe_impl(xr_batch* b, const int32_t* actions_dev, float* out_dev, int64_t env_stride, void* stream, bool inplace) {
+int32_t step_observe_impl(xr_batch* b, const int32_t* actions_dev, float* out_dev, int64_t env_stride, void* stream, bool inplace, int group) {
     if (!b || !actions_dev || !out_dev) return fail(XR_ERR_INVALID, "xr_batch_step_observe: null argument");
     if (!b->loaded) return fail(XR_ERR_STATE, "xr_batch_step_observe: load regions first");
     if (env_stride < (int64_t)(2 + 7 * (int64_t)b->k_max) * b->n_max_nodes)
@@ -1036,7 +1064,20 @@ int32_t step_observe_impl(xr_batch* b, const int32_t* actions_dev, float* out_de
                     (long long)((2 + 7 * (int64_t)b->k_max) * b->n_max_nodes));
     XR_HIP(hipSetDevice(b->cfg.device));
     XrBatchDev d = b->dev;
-    d.obs_out = out_dev;
+    // the slots of this call: [lo, lo + n).  Every host decision below that a batch takes by its size takes the call's size.
+    const int lo = group < 0 ? 0 : b->group_bounds[group];
+    const int n = group < 0 ? b->cfg.n_envs : b->group_bounds[group + 1] - lo;
+    // in-place bookkeeping of this call: the batch-wide buffer, or the group's own
+    const float*& valid_ptr = group < 0 ? b->obs_valid_ptr : b->group_valid_ptr[group];
+    int64_t& valid_stride = group < 0 ? b->obs_valid_stride : b->group_valid_stride[group];
+    if (group < 0) {
+        for (int g = 0; g < XR_MAX_GROUPS; g++) b->group_valid_ptr[g] = nullptr;      // every slot's state changes
+    } else {
+        b->obs_valid_ptr = nullptr;                 // the batch-wide buffer no longer holds this group's state
+        d.env_base = lo; d.env_count = n;
+        actions_dev = shift_back(actions_dev, lo);
+    }
+    d.obs_out = group < 0 ? out_dev : shift_back(out_dev, (int64_t)lo * env_stride);
     d.obs_stride = env_stride;
     // 1: aligned float4 (every N % 4 == 0), 2: shifted float4 (any N), 0: scalar (unaligned caller buffer)
     const bool aligned = (env_stride % 4 == 0) && ((reinterpret_cast<uintptr_t>(out_dev) & 15) == 0);
@@ -1050,9 +1091,9 @@ int32_t step_observe_impl(xr_batch* b, const int32_t* actions_dev, float* out_de
         d.obs_head_only = 1;
         d.obs_split_pm = 1000;
         // in-place form: only when THIS buffer holds the observation of the state before the step (else: a full write)
-        d.obs_incremental = (inplace && b->obs_valid_ptr == out_dev && b->obs_valid_stride == env_stride) ? 1 : 0;
+        d.obs_incremental = (inplace && valid_ptr == out_dev && valid_stride == env_stride) ? 1 : 0;
         b->last_obs_inplace = d.obs_incremental;
-        b->obs_valid_ptr = nullptr;                 // (set again below once every launch of this call has been enqueued without error)
+        valid_ptr = nullptr;                        // (set again below once every launch of this call has been enqueued without error)
         d.queue_quota_pm = b->cfg.obs_split_permille > 0 ? b->cfg.obs_split_permille : 750;
         {
             // which workgroups start with units instead of a route: bit 5 of the workgroup index.  Bit 0 (rounds 1-2) put every
@@ -1075,11 +1116,18 @@ int32_t step_observe_impl(xr_batch* b, const int32_t* actions_dev, float* out_de
                 b->queue_blocks_sweep = std::max(1, per_cu) * b->n_cus;
             }
         }
-        // this call's counters / the other bank (zeroed by this call's plan for the next one: no memset per call)
-        d.queue = b->queue.p + 4 * b->queue_bank;
-        uint32_t* const next_queue = b->queue.p + 4 * (b->queue_bank ^ 1);
-        b->queue_bank ^= 1;
+        // this call's counters / the other bank (zeroed by this call's plan for the next one: no memset per call).  An env group has two
+        // banks of its own, and its units their own slice of plan_units (at most k_max per env): group launches share no queue state
+        int& bank = group < 0 ? b->queue_bank : b->group_bank[group];
+        uint32_t* const banks = group < 0 ? b->queue.p : b->group_queue.p + 8 * group;
+        d.queue = banks + 4 * bank;
+        uint32_t* const next_queue = banks + 4 * (bank ^ 1);
+        bank ^= 1;
         b->queue_last = d.queue;
+        if (group >= 0) {
+            d.plan_units = b->plan_units.p + (size_t)lo * std::max(1, b->k_max);
+            d.plan_unit_net = b->plan_unit_net.p + (size_t)lo * std::max(1, b->k_max);
+        }
         // Route tasks: slot order for large batches (longest-first measured SLOWER there, full rewrite 1.72 -> 1.83 ms, in-place
         // 1.06 -> 1.09 ms — the launch is bound by its write stream, and long routes up front delay the first units).  A batch of at
         // most ~2 routes per resident workgroup is different: its launch ends with the longest route, and a workgroup that starts
@@ -1091,15 +1139,17 @@ int32_t step_observe_impl(xr_batch* b, const int32_t* actions_dev, float* out_de
         // 0.931 / 1.023 / 1.951 / 3.829.  Hence: up to 2 routes per resident workgroup, 4 for regions with unaligned planes.
         const int lpt_limit = (b->all_n_mult4 ? 2 : 4) * b->queue_blocks;
         const bool lpt_tasks = b->cfg.launch_order == 2 ||
-                               (b->cfg.launch_order == 0 && b->queue_blocks > 0 && b->cfg.n_envs <= lpt_limit && b->cfg.n_envs > 64);
+                               (b->cfg.launch_order == 0 && b->queue_blocks > 0 && n <= lpt_limit && n > 64);
         int order_done = 0;       // (a batch of <= 1024 envs: plan and order are ONE launch; every dependent dispatch costs a small batch ~8 us)
-        XR_HIP(xr_launch_plan(&d, actions_dev, next_queue, lpt_tasks ? b->route_order.p : nullptr, &order_done, st));
+        int32_t* const order = b->route_order.p + lo;       // (a group's longest-first order: its own slice)
+        XR_HIP(xr_launch_plan(&d, actions_dev, next_queue, lpt_tasks ? order : nullptr, &order_done, st));
         if (lpt_tasks) {
-            if (!order_done) XR_HIP(xr_launch_route_order(&d, actions_dev, b->route_order.p, st));
-            d.route_order = b->route_order.p;
+            if (!order_done) XR_HIP(xr_launch_route_order(&d, actions_dev, order, st));
+            d.route_order = order;
         }
-        // which router runs the route tasks of this launch (auto: sweeps for the full rewrite of a large batch, see load)
-        const bool use_sweep = b->sweep_full && !d.obs_incremental;
+        // which router runs the route tasks of this launch (auto: sweeps for the full rewrite of a large batch, see load; a group
+        // takes them only when it is that large itself)
+        const bool use_sweep = b->sweep_full && !d.obs_incremental && n >= 4096;
         b->last_obs_sweeps = use_sweep ? 1 : 0;
         const int kz = use_sweep ? b->zch : b->kzch;
         const size_t klds = use_sweep ? b->sweep_lds : b->route_lds;
@@ -1107,28 +1157,31 @@ int32_t step_observe_impl(xr_batch* b, const int32_t* actions_dev, float* out_de
         const int blocks = b->cfg.obs_writer_blocks > 0 ? b->cfg.obs_writer_blocks : (use_sweep ? b->queue_blocks_sweep : b->queue_blocks);
         // helper writers (aligned planes only): LDS-free workgroups on the internal stream draining the same unit queue;
         // forked after the plan, joined before the call returns the stream (events, no host wait)
+        // (an env group runs without them: the internal stream and its events are the batch's, and group steps may run concurrently)
         const int helpers = d.obs_vec4 == 1 && b->cfg.obs_helper_blocks > 0 ? b->cfg.obs_helper_blocks : 0;
-        const bool use_helpers = helpers > 0 && b->cfg.n_envs >= 64;
+        const bool use_helpers = helpers > 0 && n >= 64 && group < 0;
         if (use_helpers) {
             XR_HIP(hipEventRecord(b->ev_fork, st));
             XR_HIP(hipStreamWaitEvent(b->aux_stream, b->ev_fork, 0));
         }
-        d.queue_grid = std::min(blocks, 4 * b->cfg.n_envs);
+        d.queue_grid = std::min(blocks, 4 * n);
         XR_HIP(xr_launch_step_queue(&d, actions_dev, b->lds_dist ? 1 : 0, kz, klds, b->route_threads, d.queue_grid, st));
         if (use_helpers) {
             XR_HIP(xr_launch_unit_helpers(&d, helpers, b->aux_stream));
             XR_HIP(hipEventRecord(b->ev_join, b->aux_stream));
             XR_HIP(hipStreamWaitEvent(st, b->ev_join, 0));
         }
-        b->obs_valid_ptr = out_dev; b->obs_valid_stride = env_stride;
+        valid_ptr = out_dev; valid_stride = env_stride;
         return XR_OK;
     }
-    b->last_obs_mode = split ? XR_OBS_SPLIT : XR_OBS_FUSED;
+    // (an env group takes the fused form where the batch would split: the split form's writer stream and events are the batch's)
+    const bool split_here = split && group < 0;
+    b->last_obs_mode = split_here ? XR_OBS_SPLIT : XR_OBS_FUSED;
     b->last_obs_inplace = 0;                                  // the fused and split forms always write the whole observation
-    b->obs_valid_ptr = nullptr;
-    if (!split) {
+    valid_ptr = nullptr;
+    if (!split_here) {
         const int32_t rc = launch_route_form(b, d, actions_dev, st);
-        if (rc == XR_OK) { b->obs_valid_ptr = out_dev; b->obs_valid_stride = env_stride; }
+        if (rc == XR_OK) { valid_ptr = out_dev; valid_stride = env_stride; }
         return rc;
     }
     // plan (caller's stream) -> fork: net-plane writer on the internal stream || route kernel (+ planes 0..1) on the
@@ -1166,7 +1219,7 @@ int32_t xr_batch_step_compact(xr_batch* b, const int32_t* actions_dev, float* he
     d.obs_vec4 = aligned ? (b->all_n_mult4 ? 1 : (b->stream_ok ? 2 : 0)) : 0;
     if (d.obs_vec4 == 0)        // (the scalar epilogue has no head-only form)
         return fail(XR_ERR_INVALID, "xr_batch_step_compact: head_out_dev must be 16-byte aligned and head_stride a multiple of 4");
-    b->obs_valid_ptr = nullptr;
+    drop_obs_valid(b);
     d.obs_head_only = 1;          // the epilogue writes planes 0..1 and the net planes of the lowest XR_SPLIT_KEEP ranks: none
     d.obs_split_pm = 1000;
     b->last_obs_mode = XR_OBS_FUSED;
@@ -1227,7 +1280,7 @@ int32_t xr_batch_ingest_state(xr_batch* b, const int16_t* owner_dev, const uint6
     if ((reinterpret_cast<uintptr_t>(owner_dev) & 15) != 0 || (reinterpret_cast<uintptr_t>(legal_dev) & 7) != 0 || (reinterpret_cast<uintptr_t>(cum_dev) & 3) != 0)
         return fail(XR_ERR_INVALID, "xr_batch_ingest_state: owner rows must be 16-byte aligned, legal words 8-byte, metrics 4-byte");
     XR_HIP(hipSetDevice(b->cfg.device));
-    b->obs_valid_ptr = nullptr;                       // whatever observation a caller holds no longer describes the batch
+    drop_obs_valid(b);                                // whatever observation a caller holds no longer describes the batch
     XR_HIP(xr_launch_ingest_state(&b->dev, owner_dev, legal_dev, cum_dev, static_cast<hipStream_t>(stream)));
     return XR_OK;
 }
@@ -1277,7 +1330,7 @@ int32_t xr_batch_route_order(xr_batch* b, const int32_t* orders_dev, int32_t str
     if (stride < b->k_max)
         return fail(XR_ERR_RANGE, "xr_batch_route_order: stride %d < k_max %d", stride, b->k_max);
     XR_HIP(hipSetDevice(b->cfg.device));
-    b->obs_valid_ptr = nullptr;
+    drop_obs_valid(b);
     XR_HIP(xr_launch_order(&b->dev, orders_dev, stride, net_stats_dev, b->lds_dist ? 1 : 0, b->kzch, b->route_lds,
                            b->route_threads, static_cast<hipStream_t>(stream)));
     return XR_OK;
@@ -1307,6 +1360,12 @@ int32_t xr_batch_observation(xr_batch* b, float* out_dev, int64_t env_stride, in
     if (env_lo == 0 && env_hi == b->cfg.n_envs && env_stride >= (int64_t)(2 + 7 * (int64_t)b->k_max) * b->n_max_nodes) {
         b->obs_valid_ptr = out_dev; b->obs_valid_stride = env_stride;      // this buffer now holds every slot's observation
     }
+    if (env_stride >= (int64_t)(2 + 7 * (int64_t)b->k_max) * b->n_max_nodes)
+        for (int g = 0; g < b->n_groups; g++)                                // ... and every group it covers, its slice of it
+            if (env_lo <= b->group_bounds[g] && b->group_bounds[g + 1] <= env_hi) {
+                b->group_valid_ptr[g] = out_dev + (int64_t)(b->group_bounds[g] - env_lo) * env_stride;
+                b->group_valid_stride[g] = env_stride;
+            }
     return XR_OK;
 }
 
@@ -1410,8 +1469,106 @@ int32_t xr_batch_store(xr_batch* b, int32_t what, const void* src_dev, size_t sr
             }
         }
     }
-    b->obs_valid_ptr = nullptr;                       // whatever observation a caller holds no longer describes the batch
+    drop_obs_valid(b);                                // whatever observation a caller holds no longer describes the batch
     XR_HIP(hipMemcpyAsync(dst, src_dev, bytes, hipMemcpyDefault, st));
+    return XR_OK;
+}
+
+// ---- env groups ----------------------------------------------------------------------------------------------------------------
+// Audit of what a group step shares with the rest of the batch (xr_batch_step_group may run on several streams at once):
+//   per-env rows (owner, legal, cum, hash, env_steps, replay, region, records, router scratch, plan_region): a group touches its own only;
+//   plan_units / plan_unit_net: B*k_max entries, a group's units go to its slice at lo*k_max (at most k_max per env); route_order: the
+//     group's slice at lo; queue counters: two banks per group (group_queue), the plan of group g zeroes only g's next bank;
+//   total_steps: a device atomic; net_meas: racy per (region, net) bytes that steer launch orders only — no result depends on them;
+//   aux_stream, ev_fork / ev_join, ev_w0 / ev_w1: the batch's — a group step never uses the helper writers or the split form (it runs the
+//     fused form instead, same bytes); stream_per_region: the slot launches of the group's envs only, forked from and joined to the
+//     caller's stream (the pool's events are re-recorded per call; host calls are serialised);
+//   queue_last / last_obs_mode / last_obs_inplace: what the last call on the batch did.
+// No workgroup of the persistent step-queue launch ever waits for another one (tasks are claimed by atomics; a workgroup's static first
+// task just runs whenever it is scheduled), so several such launches sized for the whole chip may share it in any interleaving.
+
+int32_t xr_batch_set_groups(xr_batch* b, const int32_t* bounds_host, int32_t n_groups) {
+    if (!b || !bounds_host) return fail(XR_ERR_INVALID, "xr_batch_set_groups: null argument");
+    if (n_groups < 1 || n_groups > XR_MAX_GROUPS || n_groups > b->cfg.n_envs)
+        return fail(XR_ERR_RANGE, "xr_batch_set_groups: n_groups %d outside 1..min(%d, n_envs = %d)", n_groups, XR_MAX_GROUPS, b->cfg.n_envs);
+    if (bounds_host[0] != 0 || bounds_host[n_groups] != b->cfg.n_envs)
+        return fail(XR_ERR_INVALID, "xr_batch_set_groups: bounds must run from 0 to n_envs = %d (got %d .. %d)", b->cfg.n_envs, bounds_host[0],
+                    bounds_host[n_groups]);
+    for (int g = 0; g < n_groups; g++)
+        if (bounds_host[g + 1] <= bounds_host[g])
+            return fail(XR_ERR_INVALID, "xr_batch_set_groups: bounds not strictly ascending at group %d (%d, %d): no group may be empty", g,
+                        bounds_host[g], bounds_host[g + 1]);
+    XR_HIP(hipSetDevice(b->cfg.device));
+    if (b->group_queue.p) XR_HIP(hipMemset(b->group_queue.p, 0, (size_t)XR_MAX_GROUPS * 8 * sizeof(uint32_t)));
+    b->n_groups = n_groups;
+    for (int g = 0; g <= n_groups; g++) b->group_bounds[g] = bounds_host[g];
+    for (int g = 0; g < XR_MAX_GROUPS; g++) { b->group_bank[g] = 0; b->group_valid_ptr[g] = nullptr; }
+    return XR_OK;
+}
+
+namespace {
+int32_t group_check(xr_batch* b, int32_t group, const char* fn) {
+    if (!b->loaded) return fail(XR_ERR_STATE, "%s: load regions first", fn);
+    if (group < 0 || group >= b->n_groups) return fail(XR_ERR_RANGE, "%s: group %d outside 0..%d", fn, group, b->n_groups - 1);
+    return XR_OK;
+}
+}  // namespace
+
+int32_t xr_batch_step_group(xr_batch* b, int32_t group, const int32_t* actions_dev, float* out_dev, int64_t env_stride, int32_t flags, void* stream) {
+    if (!b || !actions_dev) return fail(XR_ERR_INVALID, "xr_batch_step_group: null argument");
+    if (const int32_t rc = group_check(b, group, "xr_batch_step_group")) return rc;
+    if (flags & ~XR_GROUP_INPLACE) return fail(XR_ERR_INVALID, "xr_batch_step_group: unknown flags 0x%x", flags);
+    if (out_dev) return step_observe_impl(b, actions_dev, out_dev, env_stride, stream, (flags & XR_GROUP_INPLACE) != 0, group);
+    XR_HIP(hipSetDevice(b->cfg.device));
+    const int lo = b->group_bounds[group];
+    b->obs_valid_ptr = nullptr;
+    b->group_valid_ptr[group] = nullptr;
+    XrBatchDev d = b->dev;
+    d.env_base = lo; d.env_count = b->group_bounds[group + 1] - lo;
+    return launch_route_form(b, d, shift_back(actions_dev, lo), static_cast<hipStream_t>(stream));
+}
+
+int32_t xr_batch_random_actions_group(xr_batch* b, int32_t group, int32_t* actions_dev, uint64_t seed, void* stream) {
+    if (!b || !actions_dev) return fail(XR_ERR_INVALID, "xr_batch_random_actions_group: null argument");
+    if (const int32_t rc = group_check(b, group, "xr_batch_random_actions_group")) return rc;
+    XR_HIP(hipSetDevice(b->cfg.device));
+    const int lo = b->group_bounds[group];
+    XrBatchDev d = b->dev;
+    d.env_base = lo; d.env_count = b->group_bounds[group + 1] - lo;
+    XR_HIP(xr_launch_random_actions(&d, shift_back(actions_dev, lo), seed, static_cast<hipStream_t>(stream)));
+    return XR_OK;
+}
+
+int32_t xr_batch_fetch_group(xr_batch* b, int32_t group, int32_t what, void* dst_dev, size_t dst_bytes, void* stream) {
+    if (!b || !dst_dev) return fail(XR_ERR_INVALID, "xr_batch_fetch_group: null argument");
+    if (const int32_t rc = group_check(b, group, "xr_batch_fetch_group")) return rc;
+    const char* src = nullptr;         // the array's row 0, and bytes per env row
+    size_t row = 0;
+    switch (what) {
+    case XR_FETCH_RECORD: src = reinterpret_cast<const char*>(b->records.p); row = sizeof(XrStepRecord); break;
+    case XR_FETCH_REWARD: src = reinterpret_cast<const char*>(b->reward.p); row = sizeof(double); break;
+    case XR_FETCH_DONE: src = reinterpret_cast<const char*>(b->done.p); row = 1; break;
+    case XR_FETCH_NLEGAL: src = reinterpret_cast<const char*>(b->nlegal.p); row = sizeof(int32_t); break;
+    case XR_FETCH_STATUS: src = reinterpret_cast<const char*>(b->status.p); row = sizeof(int32_t); break;
+    case XR_FETCH_LEGAL: src = reinterpret_cast<const char*>(b->legal.p); row = (size_t)b->legal_words * sizeof(uint64_t); break;
+    case XR_FETCH_DELTA: src = reinterpret_cast<const char*>(b->delta.p); row = 3 * sizeof(int32_t); break;
+    case XR_FETCH_CUM: src = reinterpret_cast<const char*>(b->cum.p); row = 3 * sizeof(int32_t); break;
+    case XR_FETCH_PATH_LEN: src = reinterpret_cast<const char*>(b->path_len.p); row = sizeof(int32_t); break;
+    case XR_FETCH_PATH: src = reinterpret_cast<const char*>(b->path.p); row = (size_t)b->path_cap * sizeof(int32_t); break;
+    case XR_FETCH_OWNER: src = reinterpret_cast<const char*>(b->owner.p); row = (size_t)b->n_max * sizeof(int16_t); break;
+    case XR_FETCH_HASH: src = reinterpret_cast<const char*>(b->hash.p); row = sizeof(uint64_t); break;
+    case XR_FETCH_REGION: src = reinterpret_cast<const char*>(b->env_region.p); row = sizeof(int32_t); break;
+    case XR_FETCH_SWEEPS: src = reinterpret_cast<const char*>(b->sweeps.p); row = sizeof(int32_t); break;
+    case XR_FETCH_REPLAY: src = reinterpret_cast<const char*>(b->env_replay.p); row = sizeof(int32_t); break;
+    case XR_FETCH_ENV_STEPS: src = reinterpret_cast<const char*>(b->env_steps.p); row = sizeof(int64_t); break;
+    default: return fail(XR_ERR_INVALID, "xr_batch_fetch_group: selector %d is not a per-env array", what);
+    }
+    const int lo = b->group_bounds[group], n = b->group_bounds[group + 1] - lo;
+    const size_t bytes = (size_t)n * row;
+    if (dst_bytes != bytes)
+        return fail(XR_ERR_RANGE, "xr_batch_fetch_group(%d): destination holds %zu bytes, the group's slice has %zu", what, dst_bytes, bytes);
+    XR_HIP(hipSetDevice(b->cfg.device));
+    XR_HIP(hipMemcpyAsync(dst_dev, src + (size_t)lo * row, bytes, hipMemcpyDefault, static_cast<hipStream_t>(stream)));
     return XR_OK;
 }
 

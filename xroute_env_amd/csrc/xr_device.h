@@ -79,6 +79,9 @@ struct XrStepRecord {
 };
 static_assert(sizeof(XrStepRecord) == 48, "xr_step_record layout");
 
+// one past the last env slot of a launch (XrBatchDev::env_base / env_count)
+#define XR_ENV_END(b) ((b).env_count > 0 ? (b).env_base + (b).env_count : (b).n_envs)
+
 // Everything a kernel needs, passed by value.
 // nets of an env with K nets left whose planes the step kernel writes itself in the split form
 #define XR_SPLIT_KEEP(b, K) ((K) - (int)(((int64_t)(K) * (b).obs_split_pm) / 1000))
@@ -169,7 +172,10 @@ struct XrBatchDev {
     // parameters
     int32_t via_cost, pen_cost, max_route_count, auto_reset;
     const int32_t* route_order;   // route kernel: workgroup i routes env route_order[i] (null: env_base + i); longest predicted first
-    int32_t env_base, env_count;   // route kernel: envs [env_base, env_base + env_count) (env_count 0 = all); stream-per-region mode
+    int32_t env_base, env_count;   // envs [env_base, env_base + env_count) of this launch (env_count 0 = all: the whole-batch calls): one slot of the
+                                   // stream-per-region mode (route kernel), or one env group (xr_batch_step_group: route, plan, route-order, step-queue
+                                   // and random-action kernels).  Per-env rows stay indexed by the absolute slot; the host shifts the caller's actions
+                                   // and observation pointers so that slot env_base lands on their element 0
     int32_t guide_cost, guide_margin, maze_end_iter;   // XR-Maze v2 knobs (0, 0, 1 = XR-Maze v1)
     int32_t dial_mult_big;   // the same for the HBM-scratch form
     int32_t dial_mult;       // bucket width of the frontier router in units of the region's smallest edge length

@@ -905,8 +905,8 @@ __device__ __forceinline__ void xr_route_dispatch(const XrBatchDev& b, const int
 // random net-order policy: j-th legal net, j from a counter-based hash
 // ------------------------------------------------------------------------------------------------
 __global__ void xr_random_action_kernel(XrBatchDev b, int32_t* __restrict__ actions, uint64_t seed) {
-    const int e = blockIdx.x * blockDim.x + threadIdx.x;
-    if (e >= b.n_envs) return;
+    const int e = b.env_base + blockIdx.x * blockDim.x + threadIdx.x;      // (env_base / env_count: one env group, xr_batch_random_actions_group)
+    if (e >= XR_ENV_END(b)) return;
     const int nl = b.nlegal[e];
     if (nl == 0) { actions[e] = 0; return; }
     const uint64_t r = splitmix64(seed ^ splitmix64((uint64_t)e * 0x100000001B3ULL + (uint64_t)b.env_steps[e]));
@@ -1272,14 +1272,16 @@ __global__ void __launch_bounds__(1024) xr_route_order_kernel(XrBatchDev b, cons
     const int t = threadIdx.x;
     if (t < 256) s_cnt[t] = 0;
     __syncthreads();
+    // the slots [e0, e1) of this launch (an env group, or the whole batch); order[i] = the i-th of them, longest first
+    const int e0 = b.env_base, e1 = XR_ENV_END(b);
     int cls[8];                                      // classes of this thread's first 8 slots stay in registers (batches <= 8192)
 #pragma unroll
     for (int k = 0; k < 8; k++) {
-        const int e = t + k * 1024;
-        cls[k] = e < b.n_envs ? xr_route_work_class(b, actions, e) : -1;
+        const int e = e0 + t + k * 1024;
+        cls[k] = e < e1 ? xr_route_work_class(b, actions, e) : -1;
         if (cls[k] >= 0) atomicAdd(&s_cnt[cls[k]], 1u);
     }
-    for (int e = t + 8 * 1024; e < b.n_envs; e += 1024) atomicAdd(&s_cnt[xr_route_work_class(b, actions, e)], 1u);
+    for (int e = e0 + t + 8 * 1024; e < e1; e += 1024) atomicAdd(&s_cnt[xr_route_work_class(b, actions, e)], 1u);
     __syncthreads();
     // exclusive prefix over DESCENDING class: thread t owns class 255 - t
     uint32_t v = 0, incl = 0;
@@ -1301,8 +1303,8 @@ __global__ void __launch_bounds__(1024) xr_route_order_kernel(XrBatchDev b, cons
     __syncthreads();
 #pragma unroll
     for (int k = 0; k < 8; k++)
-        if (cls[k] >= 0) order[atomicAdd(&s_cnt[cls[k]], 1u)] = t + k * 1024;
-    for (int e = t + 8 * 1024; e < b.n_envs; e += 1024) order[atomicAdd(&s_cnt[xr_route_work_class(b, actions, e)], 1u)] = e;
+        if (cls[k] >= 0) order[atomicAdd(&s_cnt[cls[k]], 1u)] = e0 + t + k * 1024;
+    for (int e = e0 + t + 8 * 1024; e < e1; e += 1024) order[atomicAdd(&s_cnt[xr_route_work_class(b, actions, e)], 1u)] = e;
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1343,7 +1345,7 @@ __global__ void __launch_bounds__(1024, 4) xr_route_kernel(XrBatchDev b, const i
 // globally sequential (measured: the fastest write pattern on this device, tools/micro/write_bw.hip).
 // ------------------------------------------------------------------------------------------------
 // BT threads per workgroup.  `next_queue`: the counters of the NEXT call (the two banks alternate, xr_batch.cpp) are zeroed here, so no
-// call needs a memset of its own.  `order` (single-workgroup launches only, n_envs <= BT): the route tasks' longest-predicted-first
+// call needs a memset of its own.  `order` (single-workgroup launches only, at most BT envs): the route tasks' longest-predicted-first
 // order of xr_route_order_kernel, computed by the same launch — a small batch pays for every dependent dispatch (~8 us each).
 template <int BT>
 __global__ void __launch_bounds__(BT) xr_plan_kernel(XrBatchDev b, const int32_t* __restrict__ actions, uint32_t* __restrict__ next_queue,
@@ -1353,13 +1355,15 @@ __global__ void __launch_bounds__(BT) xr_plan_kernel(XrBatchDev b, const int32_t
     __shared__ int s_wsum[BT / 64];
     __shared__ int s_base;
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-    const int e = blockIdx.x * BT + tid;
+    // envs [env_base, e_end): the whole batch, or one env group (xr_batch_step_group: its units go to its own slice of plan_units, its
+    // counters are its own, and the rotation below still steps by the batch's n_envs — a slot plays the same regions whichever group it is in)
+    const int e = b.env_base + blockIdx.x * BT + tid, e_end = XR_ENV_END(b);
     if (blockIdx.x == 0 && tid < 3 && next_queue) next_queue[tid] = 0u;
     int k = 0, r = 0;
     const uint64_t* lsrc = nullptr;        // where the post-step legal words come from
     int clear_bit = -1;
     bool was_reset = false;
-    if (e < b.n_envs) {
+    if (e < e_end) {
         const int nl = b.nlegal[e];
         r = b.env_region[e];
         was_reset = (nl == 0);
@@ -1388,7 +1392,7 @@ __global__ void __launch_bounds__(BT) xr_plan_kernel(XrBatchDev b, const int32_t
     // nets below keep their slot and their bytes.  So only the remaining nets above the routed one are units; a slot that
     // re-initialises writes all of them, a rejected action none.
     int kskip = XR_SPLIT_KEEP(b, k);
-    if (b.obs_incremental && e < b.n_envs && !was_reset) {
+    if (b.obs_incremental && e < e_end && !was_reset) {
         if (clear_bit < 0) kskip = k;
         else {
             int below = 0;
@@ -1414,7 +1418,7 @@ __global__ void __launch_bounds__(BT) xr_plan_kernel(XrBatchDev b, const int32_t
     if (tid == BT - 1) s_base = (int)atomicAdd(&b.queue[2], (unsigned)(woff + incl));
     __syncthreads();
     const int off = s_base + woff + incl - kw;
-    if (e < b.n_envs) {
+    if (e < e_end) {
         int j = 0;
         for (int w = 0; w < b.legal_words && j < k; w++) {
             uint64_t m = lsrc[w];
@@ -1430,12 +1434,12 @@ __global__ void __launch_bounds__(BT) xr_plan_kernel(XrBatchDev b, const int32_t
             }
         }
     }
-    if (order) {                // (gridDim.x == 1, n_envs <= BT) counting sort of the env slots by descending work class: xr_route_order_kernel
+    if (order) {                // (gridDim.x == 1, at most BT envs) counting sort of the env slots by descending work class: xr_route_order_kernel
         __shared__ uint32_t s_cnt[256];
         __shared__ uint32_t s_csum[4];
         if (tid < 256) s_cnt[tid] = 0;
         __syncthreads();
-        const int cls = e < b.n_envs ? xr_route_work_class(b, actions, e) : -1;
+        const int cls = e < e_end ? xr_route_work_class(b, actions, e) : -1;
         if (cls >= 0) atomicAdd(&s_cnt[cls], 1u);
         __syncthreads();
         uint32_t v = 0, inc = 0;
@@ -1675,7 +1679,7 @@ __global__ void __launch_bounds__(1024, XR_QUEUE_WAVES_PER_SIMD) xr_step_queue_k
     extern __shared__ __attribute__((aligned(16))) char smem[];
     __shared__ int s_task;
     const int tid = threadIdx.x;
-    const int B = b.n_envs;
+    const int B = XR_ENV_END(b) - b.env_base;           // route tasks of this launch: task t = env env_base + t (the whole batch, or one env group)
     const int total = (int)b.queue[2];
     const int quota = max(1, (int)(((int64_t)total * b.queue_quota_pm) / (1000 * (int64_t)B)));
     bool routes_left = true, units_left = total > 0;
@@ -1702,13 +1706,13 @@ __global__ void __launch_bounds__(1024, XR_QUEUE_WAVES_PER_SIMD) xr_step_queue_k
         if (routes_left && !skip_route) {
             if (tid == 0) {
                 const int t = (my_first >= 0 && !unit_first) ? my_first : first_r + (int)atomicAdd(&b.queue[0], 1u);
-                s_task = (t < B && b.route_order) ? b.route_order[t] : t;      // (small batches: longest predicted route first)
+                s_task = (t < B && b.route_order) ? b.route_order[t] : b.env_base + t;      // (small batches: longest predicted route first)
             }
             if (!unit_first) my_first = -1;
             xr_lds_barrier();
             const int e = s_task;
             xr_lds_barrier();
-            if (e < B) {
+            if (e < b.env_base + B) {
 #ifdef XR_TIMELINE
                 const long long t0 = XR_TL_NOW();
 #endif
@@ -2171,11 +2175,12 @@ hipError_t xr_launch_route_order(const XrBatchDev* b, const int32_t* actions, in
 // caller launches xr_route_order_kernel.
 hipError_t xr_launch_plan(const XrBatchDev* b, const int32_t* actions, uint32_t* next_queue, int32_t* order, int* order_done, hipStream_t st) {
     if (order_done) *order_done = 0;
-    if (order && b->n_envs <= 1024) {
+    const int n = XR_ENV_END(*b) - b->env_base;          // envs of this plan (the batch, or one env group)
+    if (order && n <= 1024) {
         hipLaunchKernelGGL(xr_plan_kernel<1024>, dim3(1), dim3(1024), 0, st, *b, actions, next_queue, order);
         if (order_done) *order_done = 1;
     } else {
-        hipLaunchKernelGGL(xr_plan_kernel<256>, dim3((b->n_envs + 255) / 256), dim3(256), 0, st, *b, actions, next_queue, (int32_t*)nullptr);
+        hipLaunchKernelGGL(xr_plan_kernel<256>, dim3((n + 255) / 256), dim3(256), 0, st, *b, actions, next_queue, (int32_t*)nullptr);
     }
     return hipGetLastError();
 }
@@ -2187,7 +2192,8 @@ hipError_t xr_launch_netplanes(const XrBatchDev* b, int blocks, int aligned, hip
 }
 
 hipError_t xr_launch_random_actions(const XrBatchDev* b, int32_t* actions, uint64_t seed, hipStream_t st) {
-    hipLaunchKernelGGL(xr_random_action_kernel, dim3((b->n_envs + 255) / 256), dim3(256), 0, st, *b, actions, seed);
+    const int n = XR_ENV_END(*b) - b->env_base;
+    hipLaunchKernelGGL(xr_random_action_kernel, dim3((n + 255) / 256), dim3(256), 0, st, *b, actions, seed);
     return hipGetLastError();
 }
 

@@ -4,6 +4,11 @@ This is the data-parallel form of Game.step the north star asks for.  Nothing he
 the host: actions come in as a device tensor, observation / reward / done / legal masks stay device
 tensors.  Envs that finished an episode are re-initialised by the next step (gym "next-step"
 autoreset), with the reference's region rotation (examples/launch_training.py:28-54).
+
+With `groups`, the slots are also split into env groups that step independently, each on a stream of its own
+(`step_async` / `step_wait` / `poll` / `ready_groups`): the worker model of the reference's A3C / MCTS trainers, whose
+workers never wait for each other.  An env's trajectory depends only on its own actions, so any interleaving of group
+steps gives, env by env, exactly what the lock-step `step()` gives.
 """
 from __future__ import annotations
 
@@ -11,16 +16,18 @@ from typing import Optional, Sequence
 
 import torch
 
-from ..batch import RegionBatch
+from ..batch import RegionBatch, partition_bounds
 from ..dist import RECORD_BYTES, unpack_records
 
 
 class XRouteVectorEnv:
     def __init__(self, regions: Sequence, n_envs: Optional[int] = None, device="cuda:0", with_observation: bool = True,
-                 dict_observation: bool = False, **batch_kw):
+                 dict_observation: bool = False, groups=None, **batch_kw):
         """dict_observation: reset() / step() return the observation as the advertised Dict space's member
         {"grid": [B, stride] fp32, "legal_mask": [B, Kmax] u8} instead of the bare grid tensor (the default: the hot loop's
-        consumers — agents.dqn_actions / ppo_actions — take the grid buffer and the legal bitmasks of `info` as they are)."""
+        consumers — agents.dqn_actions / ppo_actions — take the grid buffer and the legal bitmasks of `info` as they are).
+        groups: None (lock-step only, exactly as before), an int G (G near-equal env groups; at most 4 pay off where a process
+        gets 4 hardware queues) or explicit bounds [0, ..., n_envs]: enables step_async / step_wait per group."""
         self.batch = RegionBatch(regions, n_envs=n_envs, device=device, auto_reset=True, **batch_kw)
         self.n_envs = self.batch.n_envs
         self.device = self.batch.device
@@ -47,6 +54,14 @@ class XRouteVectorEnv:
             self.single_observation_space, self.single_action_space = xr_spaces.fixed_spaces(d, self.kmax)
             self.observation_space, _ = xr_spaces.fixed_spaces(d, self.kmax, batch=self.n_envs, row=int(self.batch.obs_env_stride))
             self.action_space = self.single_action_space
+        # env groups: one stream and one completion event per group; group g's rows are views [lo:hi] of the buffers above
+        self.group_streams, self.group_events = [], []
+        self.n_groups = 0
+        if groups is not None:
+            self.batch.set_groups(partition_bounds(groups, self.n_envs))
+            self.n_groups = self.batch.n_groups
+            self.group_streams = [torch.cuda.Stream(device=self.device) for _ in range(self.n_groups)]
+            self.group_events = [torch.cuda.Event() for _ in range(self.n_groups)]
 
     def observation_dict(self) -> dict:
         """The current observation as a member of `observation_space`: the grid buffer itself (no copy) + the legal mask."""
@@ -70,12 +85,20 @@ class XRouteVectorEnv:
         return (self.observation_dict() if self.dict_observation and self.with_observation else self.obs), self.reward, self.done, {"delta": self.delta, "nlegal": self.nlegal, "legal": self.legal,
                                                   "region": self.region, "record": self.record, "cum": self.cum}
 
+    def _join_groups(self):
+        """Order the current stream after every group's outstanding work (a whole-batch call follows all of it)."""
+        cur = torch.cuda.current_stream(self.device)
+        for ev in self.group_events:
+            cur.wait_event(ev)
+
     def reset(self):
+        self._join_groups()
         self.batch.reset(rotate=True)
         obs, _, _, info = self._collect(observe=True)
         return obs, info
 
     def step(self, actions: torch.Tensor):
+        self._join_groups()
         if self.with_observation:
             # route + observation of every env; self.obs is this env's own persistent buffer, so the in-place form applies:
             # only the planes that change are written (byte-identical to a full write; do not write into `obs` yourself)
@@ -86,3 +109,76 @@ class XRouteVectorEnv:
 
     def random_actions(self, seed: int, out: Optional[torch.Tensor] = None):
         return self.batch.random_actions(seed, out)
+
+    # ---- independent stepping of env groups -----------------------------------------------------------------------------
+    def _groups_of(self, group):
+        if not self.n_groups:
+            raise RuntimeError("step_async / step_wait / poll need XRouteVectorEnv(..., groups=...)")
+        if group is None:
+            return range(self.n_groups)
+        g = int(group)
+        if not 0 <= g < self.n_groups:
+            raise ValueError(f"group {group} outside 0..{self.n_groups - 1}")
+        return (g,)
+
+    def step_async(self, actions: torch.Tensor, group: Optional[int] = None):
+        """Enqueue the step of `group` (None: every group, each on its own stream) and return at once.  actions: int32 on the device,
+        the group's own [hi - lo] entries or all n_envs (the group's rows are taken).  The group's stream first waits for the current
+        stream (where the actions were made); collect the result with step_wait(group)."""
+        if actions.device != self.device or actions.dtype != torch.int32 or not actions.is_contiguous():
+            raise ValueError("actions must be a contiguous int32 tensor on the env's device")
+        groups = self._groups_of(group)
+        cur = torch.cuda.current_stream(self.device)
+        b = self.batch
+        for g in groups:
+            lo, hi = b.group_bounds(g)
+            if actions.numel() == self.n_envs:
+                act = actions[lo:hi]
+            elif group is not None and actions.numel() == hi - lo:
+                act = actions
+            else:
+                raise ValueError(f"actions must have n_envs = {self.n_envs} entries" + ("" if group is None else f" or the group's {hi - lo}"))
+            s = self.group_streams[g]
+            s.wait_stream(cur)
+            with torch.cuda.stream(s):
+                if self.with_observation:
+                    b.step_group(g, act, self.obs[lo:hi], inplace=True, stream=s)
+                else:
+                    b.step_group(g, act, stream=s)
+                b.fetch_group("record", g, self.record[lo:hi], stream=s)
+                b.fetch_group("done", g, self.done[lo:hi], stream=s)
+                b.fetch_group("legal", g, self.legal[lo:hi], stream=s)
+                b.fetch_group("region", g, self.region[lo:hi], stream=s)
+                self.group_events[g].record(s)
+            act.record_stream(s)                   # (the caching allocator must not hand the actions' memory out before s has read them)
+
+    def step_wait(self, group: Optional[int] = None):
+        """Make the current stream wait for the last step_async of `group` (None: every group) and return its
+        (obs, reward, done, info): views of rows [lo:hi] of the env's buffers — for group None exactly what step() returns."""
+        groups = self._groups_of(group)
+        cur = torch.cuda.current_stream(self.device)
+        for g in groups:
+            cur.wait_event(self.group_events[g])
+        if group is None:
+            return self._result(slice(0, self.n_envs))
+        lo, hi = self.batch.group_bounds(groups[0])
+        return self._result(slice(lo, hi))
+
+    def _result(self, sl: slice):
+        """(obs, reward, done, info) of rows `sl`: step()'s own tensors for the whole batch, views of them for a group."""
+        v = (lambda t: t) if (sl.start == 0 and sl.stop == self.n_envs) else (lambda t: t[sl])
+        obs = self.obs if self.obs is None else v(self.obs)
+        if self.dict_observation and self.with_observation:
+            obs = {"grid": obs, "legal_mask": v(self.legal_mask())}
+        info = {"delta": v(self.delta), "nlegal": v(self.nlegal), "legal": v(self.legal), "region": v(self.region),
+                "record": v(self.record), "cum": v(self.cum)}
+        return obs, v(self.reward), v(self.done), info
+
+    def poll(self, group: int) -> bool:
+        """True when the last step_async of `group` has finished on the device (non-blocking)."""
+        (g,) = self._groups_of(group)
+        return bool(self.group_events[g].query())
+
+    def ready_groups(self):
+        """The groups whose last step has finished (non-blocking)."""
+        return [g for g in range(self.n_groups) if self.group_events[g].query()]
