@@ -399,6 +399,30 @@ int32_t xr_batch_step_group(xr_batch* b, int32_t group, const int32_t* actions_d
 int32_t xr_batch_random_actions_group(xr_batch* b, int32_t group, int32_t* actions_dev, uint64_t seed, void* stream);
 int32_t xr_batch_fetch_group(xr_batch* b, int32_t group, int32_t what, void* dst_dev, size_t dst_bytes, void* stream);
 
+/* ---- uint8 observations: the same grid at one byte a value ------------------------------------- */
+/* Every value of the observation is a small integer: planes 0 and the 7K net planes hold 0 or 1, plane 1 the 1-based net ids (at most
+ * the region's n_nets).  These calls write byte i of an env's row = (uint8) of float i of the fp32 observation of the same state
+ * (xr_batch_observation / xr_batch_step_observe), for i < (2+7K)*N, in the same [2+7K, Z, Y, X] layout; bytes past (2+7K)*N are never
+ * written.  A quarter of the bytes: the step's write stream shrinks to match.
+ *   Requirements: every loaded region has n_nets <= 255 (else XR_ERR_RANGE, the batch untouched); out_dev 16-byte aligned and env_stride
+ *   (BYTES) a multiple of 16 (else XR_ERR_INVALID); env_stride >= (2+7*k_max)*n_max (else XR_ERR_RANGE).  Recommended stride:
+ *   (2+7*k_max)*n_max rounded up to 128 bytes (n_max as xr_batch_sizes reports it).
+ * xr_batch_step_observe_u8  the step of xr_batch_step_observe (group == -1: the whole batch) or xr_batch_step_group (group >= 0: env group
+ *                           `group`, actions_dev / out_dev rows start at the group's first slot), with the uint8 observation of the new
+ *                           state.  The step side is identical to the fp32 calls (records, hash chains, rotation, env_steps, router).  It
+ *                           always runs the queue form (XR_OBS_QUEUE): obs_mode, obs_helper_blocks and stream_per_region do not apply.
+ *                           flags & XR_OBS_U8_INPLACE: the in-place form (xr_batch_step_observe_inplace), valid when out_dev / env_stride
+ *                           received the previous uint8 observation of these slots; validity is tracked per (pointer, stride, dtype) and
+ *                           follows the fp32 rules for whole-batch and group calls (an fp32 write never validates a uint8 buffer, nor the
+ *                           reverse).  Other flag bits: XR_ERR_INVALID.  xr_batch_observe_timing reports XR_OBS_QUEUE (| 16 in place).
+ *                           Regions whose N % 16 != 0 keep two bits per node of one net in the step kernel's LDS: a region too large for
+ *                           that (~(n_max / 4) bytes beyond the router's LDS) is refused with XR_ERR_RANGE.
+ * xr_batch_observation_u8   build_3Dgrid of the current state of envs [env_lo, env_hi) as bytes (xr_batch_observation's twin). */
+#define XR_OBS_U8_INPLACE 1
+int32_t xr_batch_step_observe_u8(xr_batch* b, int32_t group, const int32_t* actions_dev, uint8_t* out_dev, int64_t env_stride, int32_t flags,
+                                 void* stream);
+int32_t xr_batch_observation_u8(xr_batch* b, uint8_t* out_dev, int64_t env_stride, int32_t env_lo, int32_t env_hi, void* stream);
+
 /* ---- XR-Maze v2: global-route guides (optional) ---------------------------------------------- */
 /* The reference's simulator runs with `-follow_guide 1` (ispd/ispd18_test1/run-net-ordering-training.tcl:3) on the guide file
  * it ships (ispd/ispd18_test1/ispd18_test1.input.guide: per net, rectangles per metal layer).  With xr_config.guide_cost > 0 a

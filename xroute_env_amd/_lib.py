@@ -31,6 +31,7 @@ SYMBOLS = [
     "xr_batch_state_row_bytes", "xr_batch_pack_state", "xr_batch_expand_state", "xr_batch_ingest_state",
     "xr_agent_obstacle_tower_weights", "xr_agent_obstacle_tower", "xr_agent_net_tower_weights", "xr_agent_matrix_mode", "xr_batch_net_vectors", "xr_agent_actor_weights", "xr_agent_actor", "xr_agent_actor_sample",
     "xr_batch_set_groups", "xr_batch_step_group", "xr_batch_random_actions_group", "xr_batch_fetch_group",
+    "xr_batch_step_observe_u8", "xr_batch_observation_u8",
     "xr_observation_from_records", "xr_proto_decode", "xr_proto_encode_response", "xr_proto_encode_request",
 ]
 
@@ -55,6 +56,7 @@ class XrStepRecord(C.Structure):          # include/xroute_hip.h xr_step_record 
 
 RECORD_BYTES = 48
 XR_MAX_GROUPS, XR_GROUP_INPLACE = 64, 1
+XR_OBS_U8_INPLACE = 1
 XR_ROUTER_SWEEP, XR_ROUTER_DIAL = 1, 2
 
 
@@ -117,6 +119,8 @@ def lib():
     L.xr_batch_ingest_state.argtypes = [vp, vp, vp, vp, vp]
     L.xr_batch_set_groups.argtypes = [vp, vp, C.c_int32]
     L.xr_batch_step_group.argtypes = [vp, C.c_int32, vp, vp, C.c_int64, C.c_int32, vp]
+    L.xr_batch_step_observe_u8.argtypes = [vp, C.c_int32, vp, vp, C.c_int64, C.c_int32, vp]
+    L.xr_batch_observation_u8.argtypes = [vp, vp, C.c_int64, C.c_int32, C.c_int32, vp]
     L.xr_batch_random_actions_group.argtypes = [vp, C.c_int32, vp, C.c_uint64, vp]
     L.xr_batch_fetch_group.argtypes = [vp, C.c_int32, C.c_int32, vp, C.c_size_t, vp]
     L.xr_agent_obstacle_tower_weights.argtypes = []

@@ -187,9 +187,12 @@ class RegionBatch:
             if obs_out is None:
                 _lib.check(self.L.xr_batch_step(self._h, C.c_void_p(actions.data_ptr()), _stream_ptr(self.device)))
             else:
-                if obs_out.device != self.device or obs_out.dtype != torch.float32 or not obs_out.is_contiguous() \
-                        or obs_out.dim() != 2 or obs_out.shape[0] < self.n_envs:
-                    raise ValueError("obs_out must be a contiguous fp32 [n_envs, stride] tensor on the batch device")
+                self._check_obs(obs_out, self.n_envs, "obs_out")
+                if obs_out.dtype == torch.uint8:           # the same step, the observation as bytes (xr_batch_step_observe_u8)
+                    _lib.check(self.L.xr_batch_step_observe_u8(self._h, -1, C.c_void_p(actions.data_ptr()), C.c_void_p(obs_out.data_ptr()),
+                                                               obs_out.shape[1], _lib.XR_OBS_U8_INPLACE if inplace else 0,
+                                                               _stream_ptr(self.device)))
+                    return obs_out
                 fn = self.L.xr_batch_step_observe_inplace if inplace else self.L.xr_batch_step_observe
                 _lib.check(fn(self._h, C.c_void_p(actions.data_ptr()), C.c_void_p(obs_out.data_ptr()), obs_out.shape[1],
                               _stream_ptr(self.device)))
@@ -230,10 +233,15 @@ class RegionBatch:
             raise ValueError("actions must be a contiguous int32 tensor of the group's size on the batch device")
         out_ptr, stride = None, 0
         if obs_out is not None:
-            if obs_out.device != self.device or obs_out.dtype != torch.float32 or not obs_out.is_contiguous() \
+            if obs_out.device != self.device or obs_out.dtype not in (torch.float32, torch.uint8) or not obs_out.is_contiguous() \
                     or obs_out.dim() != 2 or obs_out.shape[0] < hi - lo:
-                raise ValueError("obs_out must be a contiguous fp32 [group size, stride] tensor on the batch device")
+                raise ValueError("obs_out must be a contiguous fp32 or uint8 [group size, stride] tensor on the batch device")
             out_ptr, stride = C.c_void_p(obs_out.data_ptr()), int(obs_out.shape[1])
+            if obs_out.dtype == torch.uint8:
+                with torch.cuda.device(self.device):
+                    _lib.check(self.L.xr_batch_step_observe_u8(self._h, int(g), C.c_void_p(actions.data_ptr()), out_ptr, stride,
+                                                               _lib.XR_OBS_U8_INPLACE if inplace else 0, self._stream_arg(stream)))
+                return obs_out
         flags = _lib.XR_GROUP_INPLACE if (inplace and obs_out is not None) else 0
         with torch.cuda.device(self.device):
             _lib.check(self.L.xr_batch_step_group(self._h, int(g), C.c_void_p(actions.data_ptr()), out_ptr, stride, flags,
@@ -410,23 +418,36 @@ class RegionBatch:
                                                       C.c_uint64(seed & (2 ** 64 - 1)), _stream_ptr(self.device)))
         return out
 
-    def alloc_observation(self, n_envs: Optional[int] = None, env_stride: Optional[int] = None) -> torch.Tensor:
+    @property
+    def obs_env_stride_u8(self) -> int:
+        """Recommended row stride (bytes) of a uint8 observation buffer: (2+7*k_max)*n_max rounded up to 128 bytes."""
+        return ((2 + 7 * self.k_max) * self.n_max + 127) & ~127
+
+    def alloc_observation(self, n_envs: Optional[int] = None, env_stride: Optional[int] = None, dtype=torch.float32) -> torch.Tensor:
+        """[n_envs, stride] observation buffer: fp32 (stride in floats, obs_env_stride) or uint8 (stride in bytes, obs_env_stride_u8)."""
+        if dtype not in (torch.float32, torch.uint8):
+            raise ValueError(f"observation dtype must be torch.float32 or torch.uint8, not {dtype}")
         n = self.n_envs if n_envs is None else n_envs
-        stride = self.obs_env_stride if env_stride is None else env_stride
-        return torch.empty((n, stride), dtype=torch.float32, device=self.device)
+        default = self.obs_env_stride if dtype == torch.float32 else self.obs_env_stride_u8
+        stride = default if env_stride is None else env_stride
+        return torch.empty((n, stride), dtype=dtype, device=self.device)
+
+    def _check_obs(self, out: torch.Tensor, rows: int, what: str):
+        if out.device != self.device or out.dtype not in (torch.float32, torch.uint8) or not out.is_contiguous() or out.dim() != 2 \
+                or out.shape[0] < rows:
+            raise ValueError(f"{what} must be a contiguous fp32 or uint8 [{'n_envs' if rows == self.n_envs else 'rows'}, stride] tensor "
+                             "on the batch device")
 
     def observation(self, out: Optional[torch.Tensor] = None, env_lo: int = 0, env_hi: Optional[int] = None):
-        """build_3Dgrid of the current state of envs [env_lo, env_hi) into `out` ([n, stride] fp32).
-        Env i's observation is out[i, :(2+7K_i)*N_i] viewed as [2+7K_i, Z, Y, X]."""
+        """build_3Dgrid of the current state of envs [env_lo, env_hi) into `out` ([n, stride] fp32, or uint8: the same values as
+        bytes, xr_batch_observation_u8).  Env i's observation is out[i, :(2+7K_i)*N_i] viewed as [2+7K_i, Z, Y, X]."""
         env_hi = self.n_envs if env_hi is None else env_hi
         if out is None:
             out = self.alloc_observation(env_hi - env_lo)
-        if out.device != self.device or out.dtype != torch.float32 or not out.is_contiguous() or out.dim() != 2 \
-                or out.shape[0] < env_hi - env_lo:
-            raise ValueError("out must be a contiguous fp32 [n_envs, stride] tensor on the batch device")
+        self._check_obs(out, env_hi - env_lo, "out")
+        fn = self.L.xr_batch_observation_u8 if out.dtype == torch.uint8 else self.L.xr_batch_observation
         with torch.cuda.device(self.device):
-            _lib.check(self.L.xr_batch_observation(self._h, C.c_void_p(out.data_ptr()), out.shape[1], env_lo, env_hi,
-                                                   _stream_ptr(self.device)))
+            _lib.check(fn(self._h, C.c_void_p(out.data_ptr()), out.shape[1], env_lo, env_hi, _stream_ptr(self.device)))
         return out
 
     def env_observation(self, e: int, nlegal: Optional[int] = None) -> torch.Tensor:

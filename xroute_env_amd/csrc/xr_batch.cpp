@@ -159,15 +159,18 @@ struct xr_batch {
     int last_obs_mode = 0;
     int last_obs_inplace = 0;
     int last_obs_sweeps = 0;
-    const float* obs_valid_ptr = nullptr;       // buffer that holds the current observation of ALL env slots (in-place form)
+    const void* obs_valid_ptr = nullptr;        // buffer that holds the current observation of ALL env slots (in-place form)
     int64_t obs_valid_stride = 0;
+    bool obs_valid_u8 = false;                  // ... as uint8 (xr_batch_step_observe_u8 / xr_batch_observation_u8), else fp32
+    bool all_n_mult16 = true;                  // every region's N % 16 == 0 (uint8 unit writer without LDS)
     // env groups (xr_batch_set_groups): group g = slots [group_bounds[g], group_bounds[g + 1]); one group = the whole batch until set
     int n_groups = 1;
     int32_t group_bounds[XR_MAX_GROUPS + 1] = {};
     DevBuf<uint32_t> group_queue;               // [XR_MAX_GROUPS][2][4]: two banks of queue counters per group, alternating per group step
     int group_bank[XR_MAX_GROUPS] = {};
-    const float* group_valid_ptr[XR_MAX_GROUPS] = {};   // per group: buffer (row 0 = the group's first slot) that holds its observation
+    const void* group_valid_ptr[XR_MAX_GROUPS] = {};    // per group: buffer (row 0 = the group's first slot) that holds its observation
     int64_t group_valid_stride[XR_MAX_GROUPS] = {};
+    bool group_valid_u8[XR_MAX_GROUPS] = {};
     XrBatchDev dev{};
     ~xr_batch() {
         if (ev_fork) (void)hipEventDestroy(ev_fork);
@@ -842,6 +845,7 @@ int32_t xr_batch_load_regions(xr_batch* b, const xr_region_desc* regs, int32_t n
     d.dg_field = b->dg_field.p; d.dg_masks = b->dg_masks.p; d.dg_touch = b->dg_touch.p; d.dg_path = b->dg_path.p;
     d.dist_scratch = b->dist_scratch.p; d.cls_scratch = b->cls_scratch.p; d.list_scratch = b->list_scratch.p; d.phase_cycles = b->phase_cycles.p;
     d.obs_out = nullptr; d.obs_stride = 0; d.obs_vec4 = 0; d.obs_head_only = 0; d.obs_split_pm = 1000; d.obs_incremental = 0;
+    d.obs_out_u8 = nullptr;
     d.obs_lds_bytes = (int32_t)std::min<size_t>(b->route_lds, 1u << 30);      // (every launch of the default router carries route_lds)
     d.env_base = 0; d.env_count = 0;
     d.plan_region = b->plan_region.p; d.plan_units = b->plan_units.p; d.plan_unit_net = b->plan_unit_net.p; d.queue = b->queue.p; d.queue_quota_pm = 750;
@@ -1043,8 +1047,31 @@ int32_t xr_batch_step(xr_batch* b, const int32_t* actions_dev, void* stream) {
 }
 
 namespace {
-// group < 0: the whole batch (xr_batch_step_observe*); else env group `group` (xr_batch_step_group), its slot lo at row 0 of out_dev
-int32_t step_observe_impl(xr_batch* b, const int32_t* actions_dev, float* out_dev, int64_t env_stride, void* stream, bool inplace, int group = -1);
+// group < 0: the whole batch (xr_batch_step_observe*); else env group `group` (xr_batch_step_group), its slot lo at row 0 of out_dev.
+// out_u8 != null: the uint8 observation into out_u8 (xr_batch_step_observe_u8; out_dev unused, env_stride in bytes)
+int32_t step_observe_impl(xr_batch* b, const int32_t* actions_dev, float* out_dev, int64_t env_stride, void* stream, bool inplace, int group = -1,
+                          uint8_t* out_u8 = nullptr);
+
+// every loaded region's N % 16 == 0: the uint8 unit writer needs no LDS (xr_unit_u8_aligned), else it keeps the net's masks there
+bool all_n_mult16(const xr_batch* b) {
+    for (int r = 0; r < b->n_regions; r++)
+        if ((int64_t)b->h_dims[3 * r] * b->h_dims[3 * r + 1] * b->h_dims[3 * r + 2] % 16 != 0) return false;
+    return true;
+}
+
+// uint8 observation buffers: 16-byte aligned rows of env_stride bytes (a multiple of 16), each at least (2+7 k_max) n_max long; every
+// net id of every loaded region must fit a byte
+int32_t u8_check(const xr_batch* b, const uint8_t* out, int64_t env_stride, const char* fn) {
+    if ((reinterpret_cast<uintptr_t>(out) & 15) != 0 || env_stride % 16 != 0)
+        return fail(XR_ERR_INVALID, "%s: out_dev must be 16-byte aligned and env_stride (bytes) a multiple of 16, got %p / %lld", fn,
+                    static_cast<const void*>(out), (long long)env_stride);
+    if (env_stride < (int64_t)(2 + 7 * (int64_t)b->k_max) * b->n_max_nodes)
+        return fail(XR_ERR_RANGE, "%s: env_stride %lld < (2+7*k_max)*n_max = %lld bytes", fn, (long long)env_stride,
+                    (long long)((2 + 7 * (int64_t)b->k_max) * b->n_max_nodes));
+    if (b->k_max > 255)
+        return fail(XR_ERR_RANGE, "%s: a loaded region has %d nets; a uint8 observation holds net ids up to 255", fn, b->k_max);
+    return XR_OK;
+}
 }
 
 int32_t xr_batch_step_observe(xr_batch* b, const int32_t* actions_dev, float* out_dev, int64_t env_stride, void* stream) {
@@ -1056,9 +1083,13 @@ int32_t xr_batch_step_observe_inplace(xr_batch* b, const int32_t* actions_dev, f
 }
 
 namespace {
-int32_t step_observe_impl(xr_batch* b, const int32_t* actions_dev, float* out_dev, int64_t env_stride, void* stream, bool inplace, int group) {
-    if (!b || !actions_dev || !out_dev) return fail(XR_ERR_INVALID, "xr_batch_step_observe: null argument");
+int32_t step_observe_impl(xr_batch* b, const int32_t* actions_dev, float* out_dev, int64_t env_stride, void* stream, bool inplace, int group,
+                          uint8_t* out_u8) {
+    const bool u8 = out_u8 != nullptr;
+    if (!b || !actions_dev || (!out_dev && !u8)) return fail(XR_ERR_INVALID, "xr_batch_step_observe: null argument");
     if (!b->loaded) return fail(XR_ERR_STATE, "xr_batch_step_observe: load regions first");
+    if (u8)
+        if (const int32_t rc = u8_check(b, out_u8, env_stride, "xr_batch_step_observe_u8")) return rc;
     if (env_stride < (int64_t)(2 + 7 * (int64_t)b->k_max) * b->n_max_nodes)
         return fail(XR_ERR_RANGE, "xr_batch_step_observe: env_stride %lld < (2+7*k_max)*n_max = %lld", (long long)env_stride,
                     (long long)((2 + 7 * (int64_t)b->k_max) * b->n_max_nodes));
@@ -1068,8 +1099,26 @@ int32_t step_observe_impl(xr_batch* b, const int32_t* actions_dev, float* out_de
     const int lo = group < 0 ? 0 : b->group_bounds[group];
     const int n = group < 0 ? b->cfg.n_envs : b->group_bounds[group + 1] - lo;
     // in-place bookkeeping of this call: the batch-wide buffer, or the group's own
-    const float*& valid_ptr = group < 0 ? b->obs_valid_ptr : b->group_valid_ptr[group];
+    const void*& valid_ptr = group < 0 ? b->obs_valid_ptr : b->group_valid_ptr[group];
     int64_t& valid_stride = group < 0 ? b->obs_valid_stride : b->group_valid_stride[group];
+    bool& valid_u8 = group < 0 ? b->obs_valid_u8 : b->group_valid_u8[group];          // (validity is keyed on pointer, stride AND dtype)
+    const void* const out_key = u8 ? static_cast<const void*>(out_u8) : static_cast<const void*>(out_dev);
+    const bool u8_aligned = u8 && all_n_mult16(b);
+    if (u8) {
+        // the uint8 form always runs the queue form: its limits, and the LDS of the unit writer for planes that are not 16-byte aligned,
+        // are checked before anything changes
+        if (b->cfg.n_envs > (1 << 18) || b->k_max >= (1 << 14) || b->k_max < 1)
+            return fail(XR_ERR_RANGE, "xr_batch_step_observe_u8: the queue form needs 1 <= k_max < 16384 and n_envs <= 262144 (k_max %d, n_envs %d)",
+                        b->k_max, b->cfg.n_envs);
+        if (!u8_aligned) {
+            const bool inc = inplace && valid_ptr == out_key && valid_stride == env_stride && valid_u8;
+            const size_t klds = (b->sweep_full && !inc && n >= 4096) ? b->sweep_lds : b->route_lds;
+            const size_t need = ((size_t)(b->n_max + 15) / 16 + 2) * 4;
+            if (need > klds)
+                return fail(XR_ERR_RANGE, "xr_batch_step_observe_u8: regions with N %% 16 != 0 need %zu bytes of LDS for the unit writer's masks, the step "
+                            "kernel has %zu", need, klds);
+        }
+    }
     if (group < 0) {
         for (int g = 0; g < XR_MAX_GROUPS; g++) b->group_valid_ptr[g] = nullptr;      // every slot's state changes
     } else {
@@ -1077,21 +1126,24 @@ int32_t step_observe_impl(xr_batch* b, const int32_t* actions_dev, float* out_de
         d.env_base = lo; d.env_count = n;
         actions_dev = shift_back(actions_dev, lo);
     }
-    d.obs_out = group < 0 ? out_dev : shift_back(out_dev, (int64_t)lo * env_stride);
+    if (u8) d.obs_out_u8 = group < 0 ? out_u8 : shift_back(out_u8, (int64_t)lo * env_stride);
+    else d.obs_out = group < 0 ? out_dev : shift_back(out_dev, (int64_t)lo * env_stride);
     d.obs_stride = env_stride;
     // 1: aligned float4 (every N % 4 == 0), 2: shifted float4 (any N), 0: scalar (unaligned caller buffer)
     const bool aligned = (env_stride % 4 == 0) && ((reinterpret_cast<uintptr_t>(out_dev) & 15) == 0);
     d.obs_vec4 = aligned ? (b->all_n_mult4 ? 1 : (b->stream_ok ? 2 : 0)) : 0;
+    if (u8) d.obs_vec4 = u8_aligned ? 1 : 2;          // (uint8: 1 = every N % 16 == 0, 2 = LDS-mask writer)
     hipStream_t st = static_cast<hipStream_t>(stream);
     const bool can_split = (d.obs_vec4 == 1 || (d.obs_vec4 == 2 && b->n_max <= 60 * 1024)) && b->cfg.n_envs <= (1 << 18) && b->k_max < (1 << 14) && b->k_max >= 1;
     const bool split = can_split && b->cfg.obs_mode == XR_OBS_SPLIT && !b->cfg.stream_per_region;
-    if (can_split && (b->cfg.obs_mode == XR_OBS_QUEUE || b->cfg.obs_mode == 0) && !b->cfg.stream_per_region) {      // the default: measured fastest
+    // (uint8: always the queue form — obs_mode, obs_helper_blocks and stream_per_region do not apply)
+    if (u8 || (can_split && (b->cfg.obs_mode == XR_OBS_QUEUE || b->cfg.obs_mode == 0) && !b->cfg.stream_per_region)) {      // the default: measured fastest
         // plan, then one persistent launch: as many workgroups as the chip holds (occupancy x CUs) drain the two queues
         b->last_obs_mode = XR_OBS_QUEUE;
         d.obs_head_only = 1;
         d.obs_split_pm = 1000;
         // in-place form: only when THIS buffer holds the observation of the state before the step (else: a full write)
-        d.obs_incremental = (inplace && valid_ptr == out_dev && valid_stride == env_stride) ? 1 : 0;
+        d.obs_incremental = (inplace && valid_ptr == out_key && valid_stride == env_stride && valid_u8 == u8) ? 1 : 0;
         b->last_obs_inplace = d.obs_incremental;
         valid_ptr = nullptr;                        // (set again below once every launch of this call has been enqueued without error)
         d.queue_quota_pm = b->cfg.obs_split_permille > 0 ? b->cfg.obs_split_permille : 750;
@@ -1158,7 +1210,7 @@ int32_t step_observe_impl(xr_batch* b, const int32_t* actions_dev, float* out_de
         // helper writers (aligned planes only): LDS-free workgroups on the internal stream draining the same unit queue;
         // forked after the plan, joined before the call returns the stream (events, no host wait)
         // (an env group runs without them: the internal stream and its events are the batch's, and group steps may run concurrently)
-        const int helpers = d.obs_vec4 == 1 && b->cfg.obs_helper_blocks > 0 ? b->cfg.obs_helper_blocks : 0;
+        const int helpers = !u8 && d.obs_vec4 == 1 && b->cfg.obs_helper_blocks > 0 ? b->cfg.obs_helper_blocks : 0;
         const bool use_helpers = helpers > 0 && n >= 64 && group < 0;
         if (use_helpers) {
             XR_HIP(hipEventRecord(b->ev_fork, st));
@@ -1171,7 +1223,7 @@ int32_t step_observe_impl(xr_batch* b, const int32_t* actions_dev, float* out_de
             XR_HIP(hipEventRecord(b->ev_join, b->aux_stream));
             XR_HIP(hipStreamWaitEvent(st, b->ev_join, 0));
         }
-        valid_ptr = out_dev; valid_stride = env_stride;
+        valid_ptr = out_key; valid_stride = env_stride; valid_u8 = u8;
         return XR_OK;
     }
     // (an env group takes the fused form where the batch would split: the split form's writer stream and events are the batch's)
@@ -1181,7 +1233,7 @@ int32_t step_observe_impl(xr_batch* b, const int32_t* actions_dev, float* out_de
     valid_ptr = nullptr;
     if (!split_here) {
         const int32_t rc = launch_route_form(b, d, actions_dev, st);
-        if (rc == XR_OK) { valid_ptr = out_dev; valid_stride = env_stride; }
+        if (rc == XR_OK) { valid_ptr = out_dev; valid_stride = env_stride; valid_u8 = false; }
         return rc;
     }
     // plan (caller's stream) -> fork: net-plane writer on the internal stream || route kernel (+ planes 0..1) on the
@@ -1200,7 +1252,7 @@ int32_t step_observe_impl(xr_batch* b, const int32_t* actions_dev, float* out_de
                                b->aux_stream));
     XR_HIP(hipEventRecord(b->ev_w1, b->aux_stream));
     XR_HIP(hipStreamWaitEvent(st, b->ev_w1, 0));
-    b->obs_valid_ptr = out_dev; b->obs_valid_stride = env_stride;
+    b->obs_valid_ptr = out_dev; b->obs_valid_stride = env_stride; b->obs_valid_u8 = false;
     return XR_OK;
 }
 }  // namespace
@@ -1358,14 +1410,39 @@ int32_t xr_batch_observation(xr_batch* b, float* out_dev, int64_t env_stride, in
     XR_HIP(xr_launch_obs(&b->dev, out_dev, env_stride, env_lo, env_hi, b->n_max_nodes, vec4,
                          static_cast<hipStream_t>(stream)));
     if (env_lo == 0 && env_hi == b->cfg.n_envs && env_stride >= (int64_t)(2 + 7 * (int64_t)b->k_max) * b->n_max_nodes) {
-        b->obs_valid_ptr = out_dev; b->obs_valid_stride = env_stride;      // this buffer now holds every slot's observation
+        b->obs_valid_ptr = out_dev; b->obs_valid_stride = env_stride; b->obs_valid_u8 = false;     // this buffer now holds every slot's observation
     }
     if (env_stride >= (int64_t)(2 + 7 * (int64_t)b->k_max) * b->n_max_nodes)
         for (int g = 0; g < b->n_groups; g++)                                // ... and every group it covers, its slice of it
             if (env_lo <= b->group_bounds[g] && b->group_bounds[g + 1] <= env_hi) {
                 b->group_valid_ptr[g] = out_dev + (int64_t)(b->group_bounds[g] - env_lo) * env_stride;
                 b->group_valid_stride[g] = env_stride;
+                b->group_valid_u8[g] = false;
             }
+    return XR_OK;
+}
+
+int32_t xr_batch_observation_u8(xr_batch* b, uint8_t* out_dev, int64_t env_stride, int32_t env_lo, int32_t env_hi, void* stream) {
+    if (!b || !out_dev) return fail(XR_ERR_INVALID, "xr_batch_observation_u8: null argument");
+    if (!b->loaded) return fail(XR_ERR_STATE, "xr_batch_observation_u8: load regions first");
+    if (env_lo < 0 || env_hi > b->cfg.n_envs || env_lo > env_hi)
+        return fail(XR_ERR_RANGE, "xr_batch_observation_u8: env range [%d,%d) outside [0,%d)", env_lo, env_hi, b->cfg.n_envs);
+    if (const int32_t rc = u8_check(b, out_dev, env_stride, "xr_batch_observation_u8")) return rc;
+    XR_HIP(hipSetDevice(b->cfg.device));
+    XrBatchDev d = b->dev;
+    d.obs_out_u8 = out_dev;
+    d.obs_stride = env_stride;
+    // (xr_launch_obs dispatches on obs_out_u8; its `vec4` argument carries k_max for the uint8 form)
+    XR_HIP(xr_launch_obs(&d, nullptr, env_stride, env_lo, env_hi, b->n_max_nodes, b->k_max, static_cast<hipStream_t>(stream)));
+    if (env_lo == 0 && env_hi == b->cfg.n_envs) {
+        b->obs_valid_ptr = out_dev; b->obs_valid_stride = env_stride; b->obs_valid_u8 = true;
+    }
+    for (int g = 0; g < b->n_groups; g++)
+        if (env_lo <= b->group_bounds[g] && b->group_bounds[g + 1] <= env_hi) {
+            b->group_valid_ptr[g] = out_dev + (int64_t)(b->group_bounds[g] - env_lo) * env_stride;
+            b->group_valid_stride[g] = env_stride;
+            b->group_valid_u8[g] = true;
+        }
     return XR_OK;
 }
 
@@ -1526,6 +1603,15 @@ int32_t xr_batch_step_group(xr_batch* b, int32_t group, const int32_t* actions_d
     XrBatchDev d = b->dev;
     d.env_base = lo; d.env_count = b->group_bounds[group + 1] - lo;
     return launch_route_form(b, d, shift_back(actions_dev, lo), static_cast<hipStream_t>(stream));
+}
+
+int32_t xr_batch_step_observe_u8(xr_batch* b, int32_t group, const int32_t* actions_dev, uint8_t* out_dev, int64_t env_stride, int32_t flags,
+                                 void* stream) {
+    if (!b || !actions_dev || !out_dev) return fail(XR_ERR_INVALID, "xr_batch_step_observe_u8: null argument");
+    if (flags & ~XR_OBS_U8_INPLACE) return fail(XR_ERR_INVALID, "xr_batch_step_observe_u8: unknown flags 0x%x", flags);
+    if (group != -1)
+        if (const int32_t rc = group_check(b, group, "xr_batch_step_observe_u8")) return rc;
+    return step_observe_impl(b, actions_dev, nullptr, env_stride, stream, (flags & XR_OBS_U8_INPLACE) != 0, group, out_dev);
 }
 
 int32_t xr_batch_random_actions_group(xr_batch* b, int32_t group, int32_t* actions_dev, uint64_t seed, void* stream) {

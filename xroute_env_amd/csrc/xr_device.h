@@ -185,4 +185,8 @@ struct XrBatchDev {
     int32_t win_x, win_y, win_nmax, win_margin, win_ystep;
     uint32_t win_m24_yz, win_m24_z, win_m24_mw, win_s24;   // exact 24-bit magics of the window's Y*Z, of Z and of its mask-word count (shifts packed like XrRegionDev::s24)
     double w_violation, w_via, w_wirelength;
+    // uint8 observation output of the queue form / the stand-alone writer (null: the fp32 obs_out, if any).  When set, obs_stride is in
+    // bytes (a multiple of 16, row base 16-byte aligned) and obs_vec4 selects the unit writer: 1 = every region's N % 16 == 0
+    // (xr_unit_u8_aligned), 2 = any N (xr_unit_u8_stream, LDS masks)
+    uint8_t* obs_out_u8;
 };

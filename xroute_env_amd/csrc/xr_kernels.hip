@@ -1623,6 +1623,213 @@ __device__ __forceinline__ void xr_unit_stream(const XrBatchDev& b, int u, uint3
     xr_lds_barrier();
 }
 
+// ------------------------------------------------------------------------------------------------
+// uint8 observation (xr_batch_step_observe_u8 / xr_batch_observation_u8): byte i of an env's row = (uint8) of float i of the
+// fp32 observation — every value is 0, 1 or a net id <= 255 (the host refuses regions with more nets).  Same layout, a quarter
+// of the bytes.  Every lane packs 16 node bytes and writes them with one 16-byte non-temporal store (global_store_dwordx4);
+// only the ragged ends of a run (< 128 bytes before its first whole line, < 16 after its last slot) are written byte by byte.
+// XrBatchDev::obs_out_u8 selects it; obs_stride is then in bytes, a multiple of 16, and the row base 16-byte aligned.
+// ------------------------------------------------------------------------------------------------
+typedef unsigned xr_u4 __attribute__((ext_vector_type(4)));
+#ifndef XR_OBS_PLAIN_STORES
+#define XR_STU8(ptr, v) __builtin_nontemporal_store((v), reinterpret_cast<xr_u4*>(ptr))
+#else
+#define XR_STU8(ptr, v) (*reinterpret_cast<xr_u4*>(ptr) = (v))
+#endif
+// 4 mask bits (bit j = node j) -> 4 bytes 0 / 1
+__device__ __forceinline__ uint32_t xr_nib_bytes(uint32_t m) {
+    return (m & 1u) | ((m & 2u) << 7) | ((m & 4u) << 14) | ((m & 8u) << 21);
+}
+__device__ __forceinline__ xr_u4 xr_bits_bytes16(uint32_t m) {
+    return xr_u4{xr_nib_bytes(m), xr_nib_bytes(m >> 4), xr_nib_bytes(m >> 8), xr_nib_bytes(m >> 12)};
+}
+// 4 two-bit pairs (bit 2j = node j) -> 4 bytes 0 / 1
+__device__ __forceinline__ uint32_t xr_pair_bytes(uint32_t m) {
+    return (m & 1u) | ((m & 4u) << 6) | ((m & 16u) << 12) | ((m & 64u) << 18);
+}
+// obstacle bytes of 4 nodes from their node_net / owner halves (two int16 per word)
+__device__ __forceinline__ uint32_t xr_obst_bytes4(uint32_t n0, uint32_t n1, uint32_t w0, uint32_t w1) {
+    auto ob = [](uint32_t n, uint32_t w) -> uint32_t { return ((n & 0xFFFFu) == 0xFFFFu || (w & 0xFFFFu) != 0u) ? 1u : 0u; };
+    return ob(n0, w0) | (ob(n0 >> 16, w0 >> 16) << 8) | (ob(n1, w1) << 16) | (ob(n1 >> 16, w1 >> 16) << 24);
+}
+
+// planes 0..1 of env e's CURRENT state by the calling workgroup (queue form: the route task's epilogue).  Neither plane needs a
+// neighbour: byte f < N is the obstacle bit of node f, byte N + f the id of the net at rank f (f < K), else 0.
+__device__ __forceinline__ void xr_obs_head_u8(const XrBatchDev& b, int e, char* smem) {
+    __syncthreads();          // this workgroup's owner / legal / region writes are visible to all its threads
+    const XrRegionDev R = b.regions[b.env_region[e]];
+    int* s_ids = reinterpret_cast<int*>(smem);              // the field is dead: reuse its LDS
+    int* s_pref = s_ids + b.legal_words * 64;
+    const int tid = threadIdx.x, nthr = (int)blockDim.x;
+    int K;
+    if (b.legal_words <= nthr) {
+        const uint64_t my_m = tid < b.legal_words ? b.legal[(int64_t)e * b.legal_words + tid] : 0ull;
+        K = xr_legal_ids_pre(my_m, b.legal_words, s_ids, s_pref);
+    } else {
+        K = xr_legal_ids(b.legal + (int64_t)e * b.legal_words, b.legal_words, s_ids, s_pref);
+    }
+    const int16_t* __restrict__ nn = b.rg_node_net + R.node_off;      // (both rows 16-byte aligned: node_off and n_max are multiples of 8)
+    const int16_t* __restrict__ ow = b.owner + (int64_t)e * b.n_max;
+    uint8_t* __restrict__ out = b.obs_out_u8 + (int64_t)e * b.obs_stride;
+    const int N = R.N, total = 2 * N, nslot = total >> 4;
+    auto one = [&](int o) -> uint32_t {
+        if (o < N) return (nn[o] == -1 || ow[o] != 0) ? 1u : 0u;
+        return o - N < K ? ((uint32_t)s_ids[o - N] & 0xFFu) : 0u;
+    };
+    for (int s = tid; s < nslot; s += nthr) {
+        const int o = s << 4;
+        xr_u4 v;
+        if (o + 16 <= N) {                                    // 16 obstacle bytes: two 16-byte loads of each row
+            const int4 a0 = *reinterpret_cast<const int4*>(nn + o), a1 = *reinterpret_cast<const int4*>(nn + o + 8);
+            const int4 c0 = *reinterpret_cast<const int4*>(ow + o), c1 = *reinterpret_cast<const int4*>(ow + o + 8);
+            v = xr_u4{xr_obst_bytes4(a0.x, a0.y, c0.x, c0.y), xr_obst_bytes4(a0.z, a0.w, c0.z, c0.w),
+                      xr_obst_bytes4(a1.x, a1.y, c1.x, c1.y), xr_obst_bytes4(a1.z, a1.w, c1.z, c1.w)};
+        } else if (o >= N + K) {                              // past the ids: zeros
+            v = xr_u4{0u, 0u, 0u, 0u};
+        } else {
+            uint32_t w[4];
+#pragma unroll
+            for (int q = 0; q < 4; q++)
+                w[q] = one(o + 4 * q) | (one(o + 4 * q + 1) << 8) | (one(o + 4 * q + 2) << 16) | (one(o + 4 * q + 3) << 24);
+            v = xr_u4{w[0], w[1], w[2], w[3]};
+        }
+        XR_STU8(out + o, v);
+    }
+    const int tail0 = nslot << 4;                             // the last total % 16 bytes (the first net plane follows: not ours)
+    if (tid < total - tail0) out[tail0 + tid] = (uint8_t)one(tail0 + tid);
+}
+
+// one unit (the 7 planes of one remaining net of one env) as bytes, every region's N % 16 == 0: each plane starts 16-byte aligned, a lane
+// holds 16 nodes.  The masks come from the net's access-point list, as in xr_unit_aligned.  No LDS: works at any N.
+#define XR_NPU8_J 4          // 16-node groups per thread per tile: 256 threads * 16 * 4 = 16384 nodes
+__device__ __forceinline__ void xr_unit_u8_aligned(const XrBatchDev& b, int u) {
+    const int tid = threadIdx.x, nthr = (int)blockDim.x;
+    const uint32_t ent = b.plan_units[u];
+    const int id = b.plan_unit_net[u];
+    const int e = (int)(ent >> 14), rank = (int)(ent & 0x3FFFu);
+    const XrRegionDev R = b.regions[b.plan_region[e]];
+    const int N = R.N;
+    uint8_t* __restrict__ out = b.obs_out_u8 + (int64_t)e * b.obs_stride + (int64_t)(2 + 7 * rank) * N;
+    const int ngrp = N >> 4;
+    const int ap_lo = b.net_csr[R.net_off + id], ap_hi = b.net_csr[R.net_off + id + 1];
+    for (int g0 = 0; g0 < ngrp; g0 += nthr * XR_NPU8_J) {
+        uint32_t bits[XR_NPU8_J];                             // per group: AP mask (bits 0..15), neighbour mask (16..31)
+#pragma unroll
+        for (int j = 0; j < XR_NPU8_J; j++) bits[j] = 0;
+        for (int i = ap_lo; i < ap_hi; i++) {
+            const int v = b.ap_feat[R.ap_off + i];            // wave-uniform address
+            const int f = v & 0x7FFFFFFF;
+            const uint32_t m = (1u | (v < 0 ? 0x10000u : 0u)) << (f & 15);
+            const int g = (f >> 4) - g0 - tid;                // == j * nthr for the thread and slot that hold node f
+#pragma unroll
+            for (int j = 0; j < XR_NPU8_J; j++) bits[j] |= (g == j * nthr) ? m : 0u;
+        }
+#pragma unroll
+        for (int j = 0; j < XR_NPU8_J; j++) {
+            const int g = g0 + j * nthr + tid;
+            if (g < ngrp) {
+                uint8_t* __restrict__ pp = out + ((int64_t)g << 4);
+                const xr_u4 v0 = xr_bits_bytes16(bits[j]), v1 = xr_bits_bytes16(bits[j] >> 16);
+                XR_STU8(pp, v0);
+#pragma unroll
+                for (int pl = 1; pl < 7; pl++) XR_STU8(pp + (int64_t)pl * N, v1);
+            }
+        }
+    }
+}
+
+// The same unit for any N (xr_unit_stream's scheme): the two masks of the net go to LDS (2 bits per node, 16 nodes per word), and the
+// unit's 7*N contiguous bytes are written as 16-byte slots from its first 128-byte line on; a slot inside one plane is one funnel
+// shift of two mask words, a slot across two planes is resolved byte by byte.  s_m: LDS, (n_max / 16 + 2) words.  Ends with a barrier.
+__device__ __forceinline__ void xr_unit_u8_stream(const XrBatchDev& b, int u, uint32_t* s_m) {
+    const int tid = threadIdx.x, nthr = (int)blockDim.x;
+    const uint32_t ent = b.plan_units[u];
+    const int id = b.plan_unit_net[u];
+    const int e = (int)(ent >> 14), rank = (int)(ent & 0x3FFFu);
+    const XrRegionDev R = b.regions[b.plan_region[e]];
+    const int N = R.N;
+    const int nwords = (N + 15) >> 4;
+    const int ap_lo = b.net_csr[R.net_off + id], ap_hi = b.net_csr[R.net_off + id + 1];
+    for (int w = tid; w <= nwords; w += nthr) s_m[w] = 0u;    // one spare word: the funnel shift reads w + 1
+    xr_lds_barrier();
+    for (int i = ap_lo + tid; i < ap_hi; i += nthr) {
+        const int v = b.ap_feat[R.ap_off + i];
+        const int f = v & 0x7FFFFFFF;
+        atomicOr(&s_m[f >> 4], (v < 0 ? 3u : 1u) << ((f & 15) << 1));
+    }
+    xr_lds_barrier();
+    uint8_t* __restrict__ run = b.obs_out_u8 + (int64_t)e * b.obs_stride + (int64_t)(2 + 7 * rank) * N;
+    const int total = 7 * N;
+    const int head = min(total, (int)((128u - (uint32_t)(reinterpret_cast<uintptr_t>(run) & 127u)) & 127u));    // bytes before the first whole line
+    const int nslot = (total - head) >> 4;
+    auto one = [&](int o) -> uint32_t {       // byte at run offset o
+        const int pl = o / N, f = o - pl * N;
+        return (s_m[f >> 4] >> (((f & 15) << 1) + (pl ? 1 : 0))) & 1u;
+    };
+    for (int sl = tid; sl < nslot; sl += nthr) {
+        const int o = head + (sl << 4);
+        const int pl = o / N, f = o - pl * N;
+        xr_u4 v;
+        if (f + 15 < N) {                                     // 16 nodes of one plane
+            const int bit = f << 1, w = bit >> 5;
+            const uint32_t m = __funnelshift_r(s_m[w], s_m[w + 1], bit & 31) >> (pl ? 1 : 0);
+            v = xr_u4{xr_pair_bytes(m), xr_pair_bytes(m >> 8), xr_pair_bytes(m >> 16), xr_pair_bytes(m >> 24)};
+        } else {
+            uint32_t q4[4];
+#pragma unroll
+            for (int q = 0; q < 4; q++)
+                q4[q] = one(o + 4 * q) | (one(o + 4 * q + 1) << 8) | (one(o + 4 * q + 2) << 16) | (one(o + 4 * q + 3) << 24);
+            v = xr_u4{q4[0], q4[1], q4[2], q4[3]};
+        }
+        XR_STU8(run + o, v);
+    }
+    // ragged ends of the run
+    for (int i = tid; i < head; i += nthr) run[i] = (uint8_t)one(i);
+    const int tail0 = head + (nslot << 4);
+    for (int i = tail0 + tid; i < total; i += nthr) run[i] = (uint8_t)one(i);
+    xr_lds_barrier();
+}
+
+// stand-alone uint8 observation: workgroup (x, y) writes 16-byte slots [x * 256, x * 256 + 256) of the row of env env_lo + y.  Every
+// byte is the fp32 writer's value of its (plane, node) from xr_node_features, cast to a byte (not a hot path: the step writes its own).
+__global__ void __launch_bounds__(256) xr_obs_u8_kernel(XrBatchDev b, uint8_t* __restrict__ out, int64_t env_stride, int env_lo) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    int* s_ids = reinterpret_cast<int*>(smem);
+    int* s_pref = s_ids + b.legal_words * 64;
+    const int e = env_lo + blockIdx.y;
+    const XrRegionDev R = b.regions[b.env_region[e]];
+    const int N = R.N;
+    const int64_t slot0 = (int64_t)blockIdx.x * blockDim.x;
+    if ((slot0 << 4) >= (int64_t)(2 + 7 * (int64_t)R.n_nets) * N) return;        // (K <= n_nets: the whole workgroup is past the row)
+    const int K = xr_legal_ids(b.legal + (int64_t)e * b.legal_words, b.legal_words, s_ids, s_pref);
+    const int64_t total = (int64_t)(2 + 7 * (int64_t)K) * N;
+    const int64_t o = (slot0 + threadIdx.x) << 4;
+    if (o >= total) return;
+    XrStateSrc src{b.rg_node_net + R.node_off, b.owner + (int64_t)e * b.n_max};
+    uint8_t* __restrict__ row = out + (int64_t)blockIdx.y * env_stride;
+    int p = (int)(o / N), f = (int)(o - (int64_t)p * N);
+    uint32_t w[4] = {0u, 0u, 0u, 0u};
+    const int cnt = total - o < 16 ? (int)(total - o) : 16;
+    for (int j = 0; j < cnt; j++) {
+        float obst; int apnet; bool adj;
+        xr_node_features(src, f, R.X, R.Y, R.Z, N, obst, apnet, adj);
+        uint32_t v;
+        if (p == 0) v = obst != 0.f ? 1u : 0u;
+        else if (p == 1) v = f < K ? ((uint32_t)s_ids[f] & 0xFFu) : 0u;
+        else {
+            const int pi = p - 2, i = pi / 7, c = pi - 7 * i;
+            v = (apnet != 0 && apnet == s_ids[i] && (c == 0 || adj)) ? 1u : 0u;
+        }
+        w[j >> 2] |= v << ((j & 3) << 3);
+        if (++f == N) { f = 0; ++p; }
+    }
+    if (cnt == 16) {
+        XR_STU8(row + o, (xr_u4{w[0], w[1], w[2], w[3]}));
+    } else {                                                  // the row's last < 16 bytes
+        for (int j = 0; j < cnt; j++) row[o + j] = (uint8_t)(w[j >> 2] >> ((j & 3) << 3));
+    }
+}
+
 #ifndef XR_QUEUE_SKIP
 #define XR_QUEUE_SKIP 1
 #endif
@@ -1674,9 +1881,9 @@ __global__ void __launch_bounds__(256) xr_netplane_stream_kernel(XrBatchDev b) {
 #ifndef XR_QUEUE_WAVES_PER_SIMD
 #define XR_QUEUE_WAVES_PER_SIMD 4      // register budget of the persistent step kernel: 4 waves per SIMD = its own 4 workgroups per CU.
 #endif                                 // (6 = <= 80 VGPRs, room for helper-writer waves beside them: measured no faster)
-template <bool LDS_DIST, int ZCH>
-__global__ void __launch_bounds__(1024, XR_QUEUE_WAVES_PER_SIMD) xr_step_queue_kernel(XrBatchDev b, const int32_t* __restrict__ actions) {
-    extern __shared__ __attribute__((aligned(16))) char smem[];
+// (U8: the uint8 observation, XrBatchDev::obs_out_u8 — same tasks, same queues, byte writers; the fp32 kernel is the U8 = false body)
+template <bool LDS_DIST, int ZCH, bool U8>
+__device__ __forceinline__ void xr_step_queue_body(XrBatchDev& b, const int32_t* __restrict__ actions, char* smem) {
     __shared__ int s_task;
     const int tid = threadIdx.x;
     const int B = XR_ENV_END(b) - b.env_base;           // route tasks of this launch: task t = env env_base + t (the whole batch, or one env group)
@@ -1723,7 +1930,8 @@ __global__ void __launch_bounds__(1024, XR_QUEUE_WAVES_PER_SIMD) xr_step_queue_k
 #ifdef XR_ROUTE_PRIO
                 __builtin_amdgcn_s_setprio(0);
 #endif
-                xr_obs_epilogue(b, e, smem, true);
+                if constexpr (U8) xr_obs_head_u8(b, e, smem);
+                else xr_obs_epilogue(b, e, smem, true);
                 xr_lds_barrier();
 #ifdef XR_TIMELINE
                 tl_last_route = XR_TL_NOW(); tl_route += tl_last_route - t0; tl_nr++;
@@ -1754,8 +1962,13 @@ __global__ void __launch_bounds__(1024, XR_QUEUE_WAVES_PER_SIMD) xr_step_queue_k
 #endif
                 const int u1 = min(u0 + XR_QUEUE_BATCH, total);
                 for (int u = u0; u < u1; u++) {
-                    if (b.obs_vec4 == 1) xr_unit_aligned(b, u);
-                    else xr_unit_stream(b, u, reinterpret_cast<uint32_t*>(smem));
+                    if constexpr (U8) {
+                        if (b.obs_vec4 == 1) xr_unit_u8_aligned(b, u);
+                        else xr_unit_u8_stream(b, u, reinterpret_cast<uint32_t*>(smem));
+                    } else {
+                        if (b.obs_vec4 == 1) xr_unit_aligned(b, u);
+                        else xr_unit_stream(b, u, reinterpret_cast<uint32_t*>(smem));
+                    }
                 }
 #ifdef XR_TIMELINE
                 tl_unit += XR_TL_NOW() - t0; tl_nu += u1 - u0;
@@ -1770,6 +1983,18 @@ __global__ void __launch_bounds__(1024, XR_QUEUE_WAVES_PER_SIMD) xr_step_queue_k
         o[0] = tl_start; o[1] = XR_TL_NOW(); o[2] = tl_route; o[3] = tl_unit; o[4] = tl_nr; o[5] = tl_nu; o[6] = tl_last_route; o[7] = 1;
     }
 #endif
+}
+
+template <bool LDS_DIST, int ZCH>
+__global__ void __launch_bounds__(1024, XR_QUEUE_WAVES_PER_SIMD) xr_step_queue_kernel(XrBatchDev b, const int32_t* __restrict__ actions) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    xr_step_queue_body<LDS_DIST, ZCH, false>(b, actions, smem);
+}
+
+template <bool LDS_DIST, int ZCH>
+__global__ void __launch_bounds__(1024, XR_QUEUE_WAVES_PER_SIMD) xr_step_queue_u8_kernel(XrBatchDev b, const int32_t* __restrict__ actions) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    xr_step_queue_body<LDS_DIST, ZCH, true>(b, actions, smem);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -2065,6 +2290,20 @@ hipError_t xr_route_set_max_lds(size_t bytes) {
         e = hipFuncSetAttribute(qfns[i], hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
         if (e != hipSuccess) return e;
     }
+    // the uint8-observation step kernels (xr_batch_step_observe_u8): the same LDS as their fp32 twins
+    const void* u8fns[12] = {reinterpret_cast<const void*>(&xr_step_queue_u8_kernel<true, XR_ZCH_DIAL3V2>),
+                             reinterpret_cast<const void*>(&xr_step_queue_u8_kernel<true, XR_ZCH_DIAL3>),
+                             reinterpret_cast<const void*>(&xr_step_queue_u8_kernel<true, XR_ZCH_DIAL2>),
+                             reinterpret_cast<const void*>(&xr_step_queue_u8_kernel<false, XR_ZCH_DIAL2>),
+                             reinterpret_cast<const void*>(&xr_step_queue_u8_kernel<true, XR_ZCH_DIAL>),
+                             reinterpret_cast<const void*>(&xr_step_queue_u8_kernel<false, XR_ZCH_DIAL>),
+                             reinterpret_cast<const void*>(&xr_step_queue_u8_kernel<true, 0>), reinterpret_cast<const void*>(&xr_step_queue_u8_kernel<true, 9>),
+                             reinterpret_cast<const void*>(&xr_step_queue_u8_kernel<true, 12>), reinterpret_cast<const void*>(&xr_step_queue_u8_kernel<false, 0>),
+                             reinterpret_cast<const void*>(&xr_step_queue_u8_kernel<false, 9>), reinterpret_cast<const void*>(&xr_step_queue_u8_kernel<false, 12>)};
+    for (int i = 0; i < 12; i++) {
+        hipError_t e = hipFuncSetAttribute(u8fns[i], hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+        if (e != hipSuccess) return e;
+    }
     return hipSuccess;
 }
 
@@ -2140,10 +2379,36 @@ hipError_t xr_route_occupancy(int lds_dist, int zch, size_t lds_bytes, int threa
     return hipOccupancyMaxActiveBlocksPerMultiprocessor(wg_per_cu, fn, threads, lds_bytes);
 }
 
+// b->obs_out_u8 != null: the uint8-observation twin of every variant (xr_step_queue_u8_kernel)
+static void xr_launch_step_queue_u8(const XrBatchDev* b, const int32_t* actions, int lds_dist, int zch, size_t lds_bytes, dim3 g, dim3 t,
+                                    hipStream_t st) {
+    if (zch == XR_ZCH_DIAL3V2) {
+        hipLaunchKernelGGL((xr_step_queue_u8_kernel<true, XR_ZCH_DIAL3V2>), g, t, lds_bytes, st, *b, actions);
+    } else if (zch == XR_ZCH_DIAL3) {
+        hipLaunchKernelGGL((xr_step_queue_u8_kernel<true, XR_ZCH_DIAL3>), g, t, lds_bytes, st, *b, actions);
+    } else if (zch == XR_ZCH_DIAL2) {
+        if (lds_dist) hipLaunchKernelGGL((xr_step_queue_u8_kernel<true, XR_ZCH_DIAL2>), g, t, lds_bytes, st, *b, actions);
+        else hipLaunchKernelGGL((xr_step_queue_u8_kernel<false, XR_ZCH_DIAL2>), g, t, lds_bytes, st, *b, actions);
+    } else if (zch == XR_ZCH_DIAL) {
+        if (lds_dist) hipLaunchKernelGGL((xr_step_queue_u8_kernel<true, XR_ZCH_DIAL>), g, t, lds_bytes, st, *b, actions);
+        else hipLaunchKernelGGL((xr_step_queue_u8_kernel<false, XR_ZCH_DIAL>), g, t, lds_bytes, st, *b, actions);
+    } else if (lds_dist) {
+        if (zch == 9) hipLaunchKernelGGL((xr_step_queue_u8_kernel<true, 9>), g, t, lds_bytes, st, *b, actions);
+        else if (zch == 12) hipLaunchKernelGGL((xr_step_queue_u8_kernel<true, 12>), g, t, lds_bytes, st, *b, actions);
+        else hipLaunchKernelGGL((xr_step_queue_u8_kernel<true, 0>), g, t, lds_bytes, st, *b, actions);
+    } else {
+        if (zch == 9) hipLaunchKernelGGL((xr_step_queue_u8_kernel<false, 9>), g, t, lds_bytes, st, *b, actions);
+        else if (zch == 12) hipLaunchKernelGGL((xr_step_queue_u8_kernel<false, 12>), g, t, lds_bytes, st, *b, actions);
+        else hipLaunchKernelGGL((xr_step_queue_u8_kernel<false, 0>), g, t, lds_bytes, st, *b, actions);
+    }
+}
+
 hipError_t xr_launch_step_queue(const XrBatchDev* b, const int32_t* actions, int lds_dist, int zch, size_t lds_bytes,
                                 int threads, int blocks, hipStream_t st) {
     const dim3 g(blocks), t(threads);
-    if (zch == XR_ZCH_DIAL3V2) {
+    if (b->obs_out_u8) {
+        xr_launch_step_queue_u8(b, actions, lds_dist, zch, lds_bytes, g, t, st);
+    } else if (zch == XR_ZCH_DIAL3V2) {
         hipLaunchKernelGGL((xr_step_queue_kernel<true, XR_ZCH_DIAL3V2>), g, t, lds_bytes, st, *b, actions);
     } else if (zch == XR_ZCH_DIAL3) {
         hipLaunchKernelGGL((xr_step_queue_kernel<true, XR_ZCH_DIAL3>), g, t, lds_bytes, st, *b, actions);
@@ -2202,6 +2467,19 @@ hipError_t xr_launch_obs(const XrBatchDev* b, float* out, int64_t env_stride, in
     const int n_env = env_hi - env_lo;
     if (n_env <= 0) return hipSuccess;
     const size_t lds = (size_t)(b->legal_words * 64 + b->legal_words + 1) * sizeof(int);
+    if (b->obs_out_u8) {
+        // uint8 observation (xr_batch_observation_u8): rows at b->obs_out_u8, env_stride in bytes; `out` is unused and `vec4` carries
+        // k_max (the longest row: (2 + 7 k_max) n_max bytes, 256 slots of 16 bytes per workgroup)
+        const int64_t row = (int64_t)(2 + 7 * (int64_t)vec4) * n_max_nodes;
+        const int chunks = (int)((row + 4095) / 4096);
+        if (chunks <= 0) return hipSuccess;
+        for (int lo = env_lo; lo < env_hi; lo += 32768) {
+            const int cnt = (env_hi - lo) < 32768 ? (env_hi - lo) : 32768;
+            hipLaunchKernelGGL(xr_obs_u8_kernel, dim3(chunks, cnt), dim3(256), lds, st, *b, b->obs_out_u8 + (int64_t)(lo - env_lo) * env_stride,
+                               env_stride, lo);
+        }
+        return hipGetLastError();
+    }
     // gridDim.y <= 65535: slice the env range
     for (int lo = env_lo; lo < env_hi; lo += 32768) {
         const int cnt = (env_hi - lo) < 32768 ? (env_hi - lo) : 32768;

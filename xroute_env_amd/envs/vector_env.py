@@ -14,6 +14,7 @@ from __future__ import annotations
 
 from typing import Optional, Sequence
 
+import numpy as np
 import torch
 
 from ..batch import RegionBatch, partition_bounds
@@ -22,12 +23,17 @@ from ..dist import RECORD_BYTES, unpack_records
 
 class XRouteVectorEnv:
     def __init__(self, regions: Sequence, n_envs: Optional[int] = None, device="cuda:0", with_observation: bool = True,
-                 dict_observation: bool = False, groups=None, **batch_kw):
+                 dict_observation: bool = False, groups=None, obs_dtype=torch.float32, **batch_kw):
         """dict_observation: reset() / step() return the observation as the advertised Dict space's member
         {"grid": [B, stride] fp32, "legal_mask": [B, Kmax] u8} instead of the bare grid tensor (the default: the hot loop's
         consumers — agents.dqn_actions / ppo_actions — take the grid buffer and the legal bitmasks of `info` as they are).
         groups: None (lock-step only, exactly as before), an int G (G near-equal env groups; at most 4 pay off where a process
-        gets 4 hardware queues) or explicit bounds [0, ..., n_envs]: enables step_async / step_wait per group."""
+        gets 4 hardware queues) or explicit bounds [0, ..., n_envs]: enables step_async / step_wait per group.
+        obs_dtype: torch.float32 (default) or torch.uint8 — the same grid at one byte a value (a quarter of the bytes written per
+        step and kept per transition; xr_batch_step_observe_u8), rows of obs_env_stride_u8 bytes."""
+        if obs_dtype not in (torch.float32, torch.uint8):
+            raise ValueError(f"obs_dtype must be torch.float32 or torch.uint8, not {obs_dtype}")
+        self.obs_dtype = obs_dtype
         self.batch = RegionBatch(regions, n_envs=n_envs, device=device, auto_reset=True, **batch_kw)
         self.n_envs = self.batch.n_envs
         self.device = self.batch.device
@@ -35,7 +41,7 @@ class XRouteVectorEnv:
         self.dict_observation = bool(dict_observation)
         # (zeros, not empty: a row beyond its env's (2+7K)*N floats then only ever holds zeros or stale 0/1 planes of earlier steps —
         #  inside the Box's bounds; consumers go by nlegal / legal_mask)
-        self.obs = self.batch.alloc_observation().zero_() if with_observation else None
+        self.obs = self.batch.alloc_observation(dtype=obs_dtype).zero_() if with_observation else None
         # the 48-byte xr_step_record of every env, written by the step / reset kernels themselves: ONE copy per step;
         # reward / done / delta / nlegal below are views into it
         self.record = torch.empty((self.n_envs, RECORD_BYTES), dtype=torch.uint8, device=self.device)
@@ -51,8 +57,11 @@ class XRouteVectorEnv:
         self.single_observation_space = self.single_action_space = self.observation_space = self.action_space = None
         if len(dims) == 1:
             d = dims.pop()
-            self.single_observation_space, self.single_action_space = xr_spaces.fixed_spaces(d, self.kmax)
-            self.observation_space, _ = xr_spaces.fixed_spaces(d, self.kmax, batch=self.n_envs, row=int(self.batch.obs_env_stride))
+            u8 = obs_dtype == torch.uint8
+            dt = np.uint8 if u8 else None
+            self.single_observation_space, self.single_action_space = xr_spaces.fixed_spaces(d, self.kmax, dtype=dt)
+            row = int(self.batch.obs_env_stride_u8 if u8 else self.batch.obs_env_stride)
+            self.observation_space, _ = xr_spaces.fixed_spaces(d, self.kmax, batch=self.n_envs, row=row, dtype=dt)
             self.action_space = self.single_action_space
         # env groups: one stream and one completion event per group; group g's rows are views [lo:hi] of the buffers above
         self.group_streams, self.group_events = [], []
