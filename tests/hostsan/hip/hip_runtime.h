@@ -7,6 +7,7 @@
 // kernels do not exist: the launchers of stub_launch.cpp return success without computing anything.  No result of this build is ever
 // compared with anything — the parity tests run on the real library on a real GPU.
 #pragma once
+#define HIP_INCLUDE_HIP_HIP_RUNTIME_H        // (the real header's guard: xr_device.h declares the launchers only after it)
 #include <cstdint>
 #include <cstdlib>
 #include <cstring>

@@ -17,30 +17,6 @@
 #include "../../include/xroute_hip.h"
 #include "xr_device.h"
 
-extern "C" {
-hipError_t xr_launch_ingest(const uint32_t*, int16_t*, int16_t*, int64_t, hipStream_t);
-hipError_t xr_launch_reset(const XrBatchDev*, const uint8_t*, int, hipStream_t);
-hipError_t xr_route_set_max_lds(size_t);
-hipError_t xr_launch_route(const XrBatchDev*, const int32_t*, int, int, size_t, int, hipStream_t);
-hipError_t xr_route_occupancy(int, int, size_t, int, int*, size_t*);
-hipError_t xr_launch_plan(const XrBatchDev*, const int32_t*, uint32_t*, int32_t*, int*, hipStream_t);
-hipError_t xr_launch_route_order(const XrBatchDev*, const int32_t*, int32_t*, hipStream_t);
-hipError_t xr_launch_step_queue(const XrBatchDev*, const int32_t*, int, int, size_t, int, int, hipStream_t);
-hipError_t xr_launch_netplanes(const XrBatchDev*, int, int, hipStream_t);
-hipError_t xr_launch_order(const XrBatchDev*, const int32_t*, int, int32_t*, int, int, size_t, int, hipStream_t);
-hipError_t xr_launch_random_actions(const XrBatchDev*, int32_t*, uint64_t, hipStream_t);
-hipError_t xr_launch_obs(const XrBatchDev*, float*, int64_t, int, int, int, int, hipStream_t);
-hipError_t xr_launch_obs_records(const uint32_t*, int, int, int, const int32_t*, int, float*, int, hipStream_t);
-hipError_t xr_launch_unit_helpers(const XrBatchDev*, int, hipStream_t);
-hipError_t xr_launch_netplanes_pairs(const XrBatchDev*, const int32_t*, const int32_t*, int, float*, int64_t, int, hipStream_t);
-hipError_t xr_launch_pack_state(const XrBatchDev*, uint8_t*, int64_t, int, hipStream_t);
-hipError_t xr_launch_guide_masks(const XrBatchDev*, uint8_t*, int, hipStream_t);
-hipError_t xr_launch_expand_state(const XrBatchDev*, const uint8_t*, int64_t, int, float*, int64_t, int32_t*, int32_t*, int, hipStream_t);
-hipError_t xr_launch_ingest_state(const XrBatchDev*, const int16_t*, const uint64_t*, const int32_t*, hipStream_t);
-hipError_t xr_launch_net_tower(const void*, const int32_t*, const int32_t*, int32_t, const int32_t*, const int32_t*, int32_t, int32_t, int32_t, int32_t, const float*, const float*,
-                               float*, int32_t*, int32_t, hipStream_t, int32_t*);
-}
-
 namespace {
 
 thread_local std::string g_err;
@@ -91,6 +67,17 @@ T* shift_back(T* p, int64_t elems) {
     return reinterpret_cast<T*>(reinterpret_cast<uintptr_t>(p) - (uintptr_t)(elems * (int64_t)sizeof(T)));
 }
 
+// Which caller buffer holds the current observation of a set of slots (what the in-place form may build on): keyed on pointer, row
+// stride AND dtype (uint8: xr_batch_step_observe_u8 / xr_batch_observation_u8, else fp32)
+struct ObsValid {
+    const void* ptr = nullptr;
+    int64_t stride = 0;
+    bool u8 = false;
+    void clear() { ptr = nullptr; }
+    void set(const void* p, int64_t s, bool u) { ptr = p; stride = s; u8 = u; }
+    bool holds(const void* p, int64_t s, bool u) const { return ptr == p && stride == s && u8 == u; }
+};
+
 }  // namespace
 
 struct xr_batch {
@@ -110,6 +97,7 @@ struct xr_batch {
     int path_cap = 0;
     int x_max = 0, y_max = 0;
     bool all_n_mult4 = true;
+    bool all_n_mult16 = true;   // every region's N % 16 == 0: the uint8 unit writer needs no LDS (xr_unit_u8_aligned), else it keeps the net's masks there
     bool lds_dist = true;
     bool stream_ok = false;   // ids + 2 bytes/node of the largest region fit the LDS of the observation stream form
     size_t route_lds = 0;
@@ -159,18 +147,13 @@ struct xr_batch {
     int last_obs_mode = 0;
     int last_obs_inplace = 0;
     int last_obs_sweeps = 0;
-    const void* obs_valid_ptr = nullptr;        // buffer that holds the current observation of ALL env slots (in-place form)
-    int64_t obs_valid_stride = 0;
-    bool obs_valid_u8 = false;                  // ... as uint8 (xr_batch_step_observe_u8 / xr_batch_observation_u8), else fp32
-    bool all_n_mult16 = true;                  // every region's N % 16 == 0 (uint8 unit writer without LDS)
+    ObsValid obs_valid;                         // buffer that holds the current observation of ALL env slots (in-place form)
     // env groups (xr_batch_set_groups): group g = slots [group_bounds[g], group_bounds[g + 1]); one group = the whole batch until set
     int n_groups = 1;
     int32_t group_bounds[XR_MAX_GROUPS + 1] = {};
     DevBuf<uint32_t> group_queue;               // [XR_MAX_GROUPS][2][4]: two banks of queue counters per group, alternating per group step
     int group_bank[XR_MAX_GROUPS] = {};
-    const void* group_valid_ptr[XR_MAX_GROUPS] = {};    // per group: buffer (row 0 = the group's first slot) that holds its observation
-    int64_t group_valid_stride[XR_MAX_GROUPS] = {};
-    bool group_valid_u8[XR_MAX_GROUPS] = {};
+    ObsValid group_valid[XR_MAX_GROUPS];        // per group: buffer (row 0 = the group's first slot) that holds its observation
     XrBatchDev dev{};
     ~xr_batch() {
         if (ev_fork) (void)hipEventDestroy(ev_fork);
@@ -182,6 +165,51 @@ struct xr_batch {
         for (hipStream_t s : region_streams) (void)hipStreamDestroy(s);
     }
 };
+
+namespace {
+
+// the longest observation row: planes 0..1 and seven planes per net of the largest region (floats; bytes of the uint8 form)
+int64_t full_row(const xr_batch* b) { return (2 + 7 * (int64_t)b->k_max) * b->n_max_nodes; }
+
+// how the fp32 observation is stored into a caller's rows: 1 = aligned float4 (every N % 4 == 0), 2 = shifted float4 (any N), 0 = scalar
+// (unaligned caller buffer)
+int obs_store_mode(const xr_batch* b, const void* ptr, int64_t stride) {
+    const bool aligned = stride % 4 == 0 && (reinterpret_cast<uintptr_t>(ptr) & 15) == 0;
+    return aligned ? (b->all_n_mult4 ? 1 : (b->stream_ok ? 2 : 0)) : 0;
+}
+
+// The router variant of a launch: the batch's default, or (sweep: only where xr_batch::sweep_full) the line-segment sweeps the auto router
+// takes for the full rewrite of a large batch
+XrRouteVariant route_variant(const xr_batch* b, bool sweep = false) {
+    if (sweep) return {1, b->zch, b->sweep_lds, b->route_threads};
+    return {b->lds_dist ? 1 : 0, b->kzch, b->route_lds, b->route_threads};
+}
+
+// d becomes the view of env group `group`: its slots [lo, lo + env_count) alone.  Returns lo — the caller shifts its per-env buffers back
+// by it (shift_back)
+int group_view(const xr_batch* b, int group, XrBatchDev& d) {
+    const int lo = b->group_bounds[group];
+    d.env_base = lo; d.env_count = b->group_bounds[group + 1] - lo;
+    return lo;
+}
+
+// A whole-batch call that changes env state: no caller buffer holds the current observation any more (batch-wide or per group).
+void drop_obs_valid(xr_batch* b) {
+    b->obs_valid.clear();
+    for (ObsValid& v : b->group_valid) v.clear();
+}
+
+// `out` (row 0 = slot env_lo; rows of `stride` floats, or bytes when u8) now holds the observation of slots [env_lo, env_hi): mark the
+// batch if those are all of them, and every group the range covers, its slice of it
+void mark_obs_valid(xr_batch* b, const void* out, int64_t stride, bool u8, int env_lo, int env_hi) {
+    const int64_t row_bytes = stride * (u8 ? 1 : (int64_t)sizeof(float));
+    if (env_lo == 0 && env_hi == b->cfg.n_envs) b->obs_valid.set(out, stride, u8);
+    for (int g = 0; g < b->n_groups; g++)
+        if (env_lo <= b->group_bounds[g] && b->group_bounds[g + 1] <= env_hi)
+            b->group_valid[g].set(static_cast<const char*>(out) + (b->group_bounds[g] - env_lo) * row_bytes, stride, u8);
+}
+
+}  // namespace
 
 extern "C" {
 
@@ -276,12 +304,6 @@ int32_t xr_batch_destroy(xr_batch* b) {
 
 static int32_t build_guide_masks(xr_batch* b, hipStream_t st);
 
-// A whole-batch call that changes env state: no caller buffer holds the current observation any more (batch-wide or per group).
-static void drop_obs_valid(xr_batch* b) {
-    b->obs_valid_ptr = nullptr;
-    for (int g = 0; g < XR_MAX_GROUPS; g++) b->group_valid_ptr[g] = nullptr;
-}
-
 int32_t xr_batch_load_regions(xr_batch* b, const xr_region_desc* regs, int32_t n_regions, void* stream) {
     if (!b || !regs || n_regions < 1) return fail(XR_ERR_INVALID, "xr_batch_load_regions: bad argument");
     XR_HIP(hipSetDevice(b->cfg.device));
@@ -326,7 +348,7 @@ int32_t xr_batch_load_regions(xr_batch* b, const xr_region_desc* regs, int32_t n
     };
     int n_max_nodes = 0, k_max = 0, x_max = 0, y_max = 0, n_lds = 0, tracks_max = 0, lines_max = 0, bits_max = 0, z_min = 1 << 30, z_max = 0, ncol_max = 0;
     size_t gmask_bytes = 0;        // XR-Maze v2: bytes of the static guide masks of every (region, net) (XrRegionDev::gmask_off)
-    bool mult4 = true;
+    bool mult4 = true, mult16 = true;
     for (int r = 0; r < n_regions; r++) {
         const xr_region_desc& d = regs[r];
         if (d.dim_x < 1 || d.dim_y < 1 || d.dim_z < 1 || d.dim_z > XR_MAX_LAYERS)
@@ -522,6 +544,7 @@ int32_t xr_batch_load_regions(xr_batch* b, const xr_region_desc* regs, int32_t n
         x_max = std::max(x_max, d.dim_x);
         y_max = std::max(y_max, d.dim_y);
         if (N % 4) mult4 = false;
+        if (N % 16) mult16 = false;
         {   // padded field: l = x*SX + y*SY + z, SY = Z|1, SX = (Y*SY)|1 (xr_route_kernel)
             const int64_t sy = d.dim_z | 1, sx = ((int64_t)d.dim_y * sy) | 1;
             const int64_t words = (int64_t)d.dim_x * sx;
@@ -561,6 +584,7 @@ int32_t xr_batch_load_regions(xr_batch* b, const xr_region_desc* regs, int32_t n
     b->x_max = x_max;
     b->y_max = y_max;
     b->all_n_mult4 = mult4;
+    b->all_n_mult16 = mult16;
     b->path_cap = b->cfg.path_cap > 0 ? b->cfg.path_cap : std::min(n_max_nodes, 4096);
 
     // route kernel placement: distance field in LDS when it fits.  Worklist items are (line, chunk of 8 nodes) pairs:
@@ -998,19 +1022,19 @@ int32_t launch_route_form(xr_batch* b, const XrBatchDev& d, const int32_t* actio
                 XR_HIP(hipGetDeviceProperties(&prop, b->cfg.device));
                 int per_cu = 0;
                 size_t stat = 0;
-                XR_HIP(xr_route_occupancy(b->lds_dist ? 1 : 0, b->kzch, b->route_lds, b->route_threads, &per_cu, &stat));
+                XR_HIP(xr_route_occupancy(route_variant(b), &per_cu, &stat));
                 b->route_slots = std::max(1, per_cu) * prop.multiProcessorCount;
             }
             lpt = n > b->route_slots;
         }
         if (!lpt) {
-            XR_HIP(xr_launch_route(&d, actions_dev, b->lds_dist ? 1 : 0, b->kzch, b->route_lds, b->route_threads, st));
+            XR_HIP(xr_launch_route(&d, actions_dev, route_variant(b), st));
             return XR_OK;
         }
         XrBatchDev dl = d;
         XR_HIP(xr_launch_route_order(&dl, actions_dev, b->route_order.p + lo, st));
         dl.route_order = b->route_order.p + lo;
-        XR_HIP(xr_launch_route(&dl, actions_dev, b->lds_dist ? 1 : 0, b->kzch, b->route_lds, b->route_threads, st));
+        XR_HIP(xr_launch_route(&dl, actions_dev, route_variant(b), st));
         return XR_OK;
     }
     if (b->region_streams.empty()) {
@@ -1028,7 +1052,7 @@ int32_t launch_route_form(xr_batch* b, const XrBatchDev& d, const int32_t* actio
     for (int e = lo; e < lo + n; e++) {
         XrBatchDev de = d;
         de.env_base = e; de.env_count = 1;
-        XR_HIP(xr_launch_route(&de, actions_dev, b->lds_dist ? 1 : 0, b->kzch, b->route_lds, b->route_threads, b->region_streams[e % ns]));
+        XR_HIP(xr_launch_route(&de, actions_dev, route_variant(b), b->region_streams[e % ns]));
     }
     for (int i = 0; i < ns; i++) {
         XR_HIP(hipEventRecord(b->region_events[i], b->region_streams[i]));
@@ -1052,22 +1076,14 @@ namespace {
 int32_t step_observe_impl(xr_batch* b, const int32_t* actions_dev, float* out_dev, int64_t env_stride, void* stream, bool inplace, int group = -1,
                           uint8_t* out_u8 = nullptr);
 
-// every loaded region's N % 16 == 0: the uint8 unit writer needs no LDS (xr_unit_u8_aligned), else it keeps the net's masks there
-bool all_n_mult16(const xr_batch* b) {
-    for (int r = 0; r < b->n_regions; r++)
-        if ((int64_t)b->h_dims[3 * r] * b->h_dims[3 * r + 1] * b->h_dims[3 * r + 2] % 16 != 0) return false;
-    return true;
-}
-
 // uint8 observation buffers: 16-byte aligned rows of env_stride bytes (a multiple of 16), each at least (2+7 k_max) n_max long; every
 // net id of every loaded region must fit a byte
 int32_t u8_check(const xr_batch* b, const uint8_t* out, int64_t env_stride, const char* fn) {
     if ((reinterpret_cast<uintptr_t>(out) & 15) != 0 || env_stride % 16 != 0)
         return fail(XR_ERR_INVALID, "%s: out_dev must be 16-byte aligned and env_stride (bytes) a multiple of 16, got %p / %lld", fn,
                     static_cast<const void*>(out), (long long)env_stride);
-    if (env_stride < (int64_t)(2 + 7 * (int64_t)b->k_max) * b->n_max_nodes)
-        return fail(XR_ERR_RANGE, "%s: env_stride %lld < (2+7*k_max)*n_max = %lld bytes", fn, (long long)env_stride,
-                    (long long)((2 + 7 * (int64_t)b->k_max) * b->n_max_nodes));
+    if (env_stride < full_row(b))
+        return fail(XR_ERR_RANGE, "%s: env_stride %lld < (2+7*k_max)*n_max = %lld bytes", fn, (long long)env_stride, (long long)full_row(b));
     if (b->k_max > 255)
         return fail(XR_ERR_RANGE, "%s: a loaded region has %d nets; a uint8 observation holds net ids up to 255", fn, b->k_max);
     return XR_OK;
@@ -1088,51 +1104,49 @@ int32_t step_observe_impl(xr_batch* b, const int32_t* actions_dev, float* out_de
     const bool u8 = out_u8 != nullptr;
     if (!b || !actions_dev || (!out_dev && !u8)) return fail(XR_ERR_INVALID, "xr_batch_step_observe: null argument");
     if (!b->loaded) return fail(XR_ERR_STATE, "xr_batch_step_observe: load regions first");
-    if (u8)
+    if (u8) {
         if (const int32_t rc = u8_check(b, out_u8, env_stride, "xr_batch_step_observe_u8")) return rc;
-    if (env_stride < (int64_t)(2 + 7 * (int64_t)b->k_max) * b->n_max_nodes)
-        return fail(XR_ERR_RANGE, "xr_batch_step_observe: env_stride %lld < (2+7*k_max)*n_max = %lld", (long long)env_stride,
-                    (long long)((2 + 7 * (int64_t)b->k_max) * b->n_max_nodes));
+    } else if (env_stride < full_row(b)) {
+        return fail(XR_ERR_RANGE, "xr_batch_step_observe: env_stride %lld < (2+7*k_max)*n_max = %lld", (long long)env_stride, (long long)full_row(b));
+    }
     XR_HIP(hipSetDevice(b->cfg.device));
     XrBatchDev d = b->dev;
     // the slots of this call: [lo, lo + n).  Every host decision below that a batch takes by its size takes the call's size.
-    const int lo = group < 0 ? 0 : b->group_bounds[group];
-    const int n = group < 0 ? b->cfg.n_envs : b->group_bounds[group + 1] - lo;
+    const int lo = group < 0 ? 0 : group_view(b, group, d);
+    const int n = group < 0 ? b->cfg.n_envs : d.env_count;
     // in-place bookkeeping of this call: the batch-wide buffer, or the group's own
-    const void*& valid_ptr = group < 0 ? b->obs_valid_ptr : b->group_valid_ptr[group];
-    int64_t& valid_stride = group < 0 ? b->obs_valid_stride : b->group_valid_stride[group];
-    bool& valid_u8 = group < 0 ? b->obs_valid_u8 : b->group_valid_u8[group];          // (validity is keyed on pointer, stride AND dtype)
+    ObsValid& valid = group < 0 ? b->obs_valid : b->group_valid[group];
     const void* const out_key = u8 ? static_cast<const void*>(out_u8) : static_cast<const void*>(out_dev);
-    const bool u8_aligned = u8 && all_n_mult16(b);
+    // in-place for this call: only when THIS buffer holds the observation of the state before the step (else: a full write)
+    const bool inc = inplace && valid.holds(out_key, env_stride, u8);
+    // which router runs the route tasks of a queue-form launch (auto: sweeps for the full rewrite of a large batch, see load; a group
+    // takes them only when it is that large itself)
+    const bool use_sweep = b->sweep_full && !inc && n >= 4096;
+    const XrRouteVariant qv = route_variant(b, use_sweep);
     if (u8) {
         // the uint8 form always runs the queue form: its limits, and the LDS of the unit writer for planes that are not 16-byte aligned,
         // are checked before anything changes
         if (b->cfg.n_envs > (1 << 18) || b->k_max >= (1 << 14) || b->k_max < 1)
             return fail(XR_ERR_RANGE, "xr_batch_step_observe_u8: the queue form needs 1 <= k_max < 16384 and n_envs <= 262144 (k_max %d, n_envs %d)",
                         b->k_max, b->cfg.n_envs);
-        if (!u8_aligned) {
-            const bool inc = inplace && valid_ptr == out_key && valid_stride == env_stride && valid_u8;
-            const size_t klds = (b->sweep_full && !inc && n >= 4096) ? b->sweep_lds : b->route_lds;
+        if (!b->all_n_mult16) {
             const size_t need = ((size_t)(b->n_max + 15) / 16 + 2) * 4;
-            if (need > klds)
+            if (need > qv.lds_bytes)
                 return fail(XR_ERR_RANGE, "xr_batch_step_observe_u8: regions with N %% 16 != 0 need %zu bytes of LDS for the unit writer's masks, the step "
-                            "kernel has %zu", need, klds);
+                            "kernel has %zu", need, qv.lds_bytes);
         }
     }
     if (group < 0) {
-        for (int g = 0; g < XR_MAX_GROUPS; g++) b->group_valid_ptr[g] = nullptr;      // every slot's state changes
+        for (ObsValid& v : b->group_valid) v.clear();      // every slot's state changes
     } else {
-        b->obs_valid_ptr = nullptr;                 // the batch-wide buffer no longer holds this group's state
-        d.env_base = lo; d.env_count = n;
+        b->obs_valid.clear();                       // the batch-wide buffer no longer holds this group's state
         actions_dev = shift_back(actions_dev, lo);
     }
-    if (u8) d.obs_out_u8 = group < 0 ? out_u8 : shift_back(out_u8, (int64_t)lo * env_stride);
-    else d.obs_out = group < 0 ? out_dev : shift_back(out_dev, (int64_t)lo * env_stride);
+    if (u8) d.obs_out_u8 = shift_back(out_u8, (int64_t)lo * env_stride);
+    else d.obs_out = shift_back(out_dev, (int64_t)lo * env_stride);
     d.obs_stride = env_stride;
-    // 1: aligned float4 (every N % 4 == 0), 2: shifted float4 (any N), 0: scalar (unaligned caller buffer)
-    const bool aligned = (env_stride % 4 == 0) && ((reinterpret_cast<uintptr_t>(out_dev) & 15) == 0);
-    d.obs_vec4 = aligned ? (b->all_n_mult4 ? 1 : (b->stream_ok ? 2 : 0)) : 0;
-    if (u8) d.obs_vec4 = u8_aligned ? 1 : 2;          // (uint8: 1 = every N % 16 == 0, 2 = LDS-mask writer)
+    d.obs_vec4 = u8 ? (b->all_n_mult16 ? 1 : 2)          // (uint8: 1 = every N % 16 == 0, 2 = LDS-mask writer)
+                    : obs_store_mode(b, out_dev, env_stride);
     hipStream_t st = static_cast<hipStream_t>(stream);
     const bool can_split = (d.obs_vec4 == 1 || (d.obs_vec4 == 2 && b->n_max <= 60 * 1024)) && b->cfg.n_envs <= (1 << 18) && b->k_max < (1 << 14) && b->k_max >= 1;
     const bool split = can_split && b->cfg.obs_mode == XR_OBS_SPLIT && !b->cfg.stream_per_region;
@@ -1142,10 +1156,9 @@ int32_t step_observe_impl(xr_batch* b, const int32_t* actions_dev, float* out_de
         b->last_obs_mode = XR_OBS_QUEUE;
         d.obs_head_only = 1;
         d.obs_split_pm = 1000;
-        // in-place form: only when THIS buffer holds the observation of the state before the step (else: a full write)
-        d.obs_incremental = (inplace && valid_ptr == out_key && valid_stride == env_stride && valid_u8 == u8) ? 1 : 0;
+        d.obs_incremental = inc ? 1 : 0;
         b->last_obs_inplace = d.obs_incremental;
-        valid_ptr = nullptr;                        // (set again below once every launch of this call has been enqueued without error)
+        valid.clear();                              // (set again below once every launch of this call has been enqueued without error)
         d.queue_quota_pm = b->cfg.obs_split_permille > 0 ? b->cfg.obs_split_permille : 750;
         {
             // which workgroups start with units instead of a route: bit 5 of the workgroup index.  Bit 0 (rounds 1-2) put every
@@ -1160,11 +1173,11 @@ int32_t step_observe_impl(xr_batch* b, const int32_t* actions_dev, float* out_de
             XR_HIP(hipGetDeviceProperties(&prop, b->cfg.device));
             int per_cu = 0;
             size_t stat = 0;
-            XR_HIP(xr_route_occupancy(b->lds_dist ? 1 : 0, b->kzch, b->route_lds, b->route_threads, &per_cu, &stat));
+            XR_HIP(xr_route_occupancy(route_variant(b), &per_cu, &stat));
             b->n_cus = prop.multiProcessorCount;
             b->queue_blocks = std::max(1, per_cu) * b->n_cus;
             if (b->sweep_full) {
-                XR_HIP(xr_route_occupancy(1, b->zch, b->sweep_lds, b->route_threads, &per_cu, &stat));
+                XR_HIP(xr_route_occupancy(route_variant(b, true), &per_cu, &stat));
                 b->queue_blocks_sweep = std::max(1, per_cu) * b->n_cus;
             }
         }
@@ -1199,13 +1212,8 @@ int32_t step_observe_impl(xr_batch* b, const int32_t* actions_dev, float* out_de
             if (!order_done) XR_HIP(xr_launch_route_order(&d, actions_dev, order, st));
             d.route_order = order;
         }
-        // which router runs the route tasks of this launch (auto: sweeps for the full rewrite of a large batch, see load; a group
-        // takes them only when it is that large itself)
-        const bool use_sweep = b->sweep_full && !d.obs_incremental && n >= 4096;
         b->last_obs_sweeps = use_sweep ? 1 : 0;
-        const int kz = use_sweep ? b->zch : b->kzch;
-        const size_t klds = use_sweep ? b->sweep_lds : b->route_lds;
-        d.obs_lds_bytes = (int32_t)std::min<size_t>(klds, 1u << 30);
+        d.obs_lds_bytes = (int32_t)std::min<size_t>(qv.lds_bytes, 1u << 30);
         const int blocks = b->cfg.obs_writer_blocks > 0 ? b->cfg.obs_writer_blocks : (use_sweep ? b->queue_blocks_sweep : b->queue_blocks);
         // helper writers (aligned planes only): LDS-free workgroups on the internal stream draining the same unit queue;
         // forked after the plan, joined before the call returns the stream (events, no host wait)
@@ -1217,23 +1225,23 @@ int32_t step_observe_impl(xr_batch* b, const int32_t* actions_dev, float* out_de
             XR_HIP(hipStreamWaitEvent(b->aux_stream, b->ev_fork, 0));
         }
         d.queue_grid = std::min(blocks, 4 * n);
-        XR_HIP(xr_launch_step_queue(&d, actions_dev, b->lds_dist ? 1 : 0, kz, klds, b->route_threads, d.queue_grid, st));
+        XR_HIP(xr_launch_step_queue(&d, actions_dev, qv, d.queue_grid, st));
         if (use_helpers) {
             XR_HIP(xr_launch_unit_helpers(&d, helpers, b->aux_stream));
             XR_HIP(hipEventRecord(b->ev_join, b->aux_stream));
             XR_HIP(hipStreamWaitEvent(st, b->ev_join, 0));
         }
-        valid_ptr = out_key; valid_stride = env_stride; valid_u8 = u8;
+        valid.set(out_key, env_stride, u8);
         return XR_OK;
     }
     // (an env group takes the fused form where the batch would split: the split form's writer stream and events are the batch's)
     const bool split_here = split && group < 0;
     b->last_obs_mode = split_here ? XR_OBS_SPLIT : XR_OBS_FUSED;
     b->last_obs_inplace = 0;                                  // the fused and split forms always write the whole observation
-    valid_ptr = nullptr;
+    valid.clear();
     if (!split_here) {
         const int32_t rc = launch_route_form(b, d, actions_dev, st);
-        if (rc == XR_OK) { valid_ptr = out_dev; valid_stride = env_stride; valid_u8 = false; }
+        if (rc == XR_OK) valid.set(out_dev, env_stride, false);
         return rc;
     }
     // plan (caller's stream) -> fork: net-plane writer on the internal stream || route kernel (+ planes 0..1) on the
@@ -1246,13 +1254,13 @@ int32_t step_observe_impl(xr_batch* b, const int32_t* actions_dev, float* out_de
     b->queue_last = d.queue;
     XR_HIP(hipEventRecord(b->ev_fork, st));
     XR_HIP(hipStreamWaitEvent(b->aux_stream, b->ev_fork, 0));
-    XR_HIP(xr_launch_route(&d, actions_dev, b->lds_dist ? 1 : 0, b->kzch, b->route_lds, b->route_threads, st));
+    XR_HIP(xr_launch_route(&d, actions_dev, route_variant(b), st));
     XR_HIP(hipEventRecord(b->ev_w0, b->aux_stream));
     XR_HIP(xr_launch_netplanes(&d, b->cfg.obs_writer_blocks > 0 ? b->cfg.obs_writer_blocks : 512, d.obs_vec4 == 1 ? 1 : 0,
                                b->aux_stream));
     XR_HIP(hipEventRecord(b->ev_w1, b->aux_stream));
     XR_HIP(hipStreamWaitEvent(st, b->ev_w1, 0));
-    b->obs_valid_ptr = out_dev; b->obs_valid_stride = env_stride; b->obs_valid_u8 = false;
+    valid.set(out_dev, env_stride, false);
     return XR_OK;
 }
 }  // namespace
@@ -1267,8 +1275,7 @@ int32_t xr_batch_step_compact(xr_batch* b, const int32_t* actions_dev, float* he
     XrBatchDev d = b->dev;
     d.obs_out = head_out_dev;
     d.obs_stride = head_stride;
-    const bool aligned = (head_stride % 4 == 0) && ((reinterpret_cast<uintptr_t>(head_out_dev) & 15) == 0);
-    d.obs_vec4 = aligned ? (b->all_n_mult4 ? 1 : (b->stream_ok ? 2 : 0)) : 0;
+    d.obs_vec4 = obs_store_mode(b, head_out_dev, head_stride);
     if (d.obs_vec4 == 0)        // (the scalar epilogue has no head-only form)
         return fail(XR_ERR_INVALID, "xr_batch_step_compact: head_out_dev must be 16-byte aligned and head_stride a multiple of 4");
     drop_obs_valid(b);
@@ -1357,7 +1364,7 @@ int32_t xr_batch_route_occupancy(xr_batch* b, int32_t* workgroups_per_cu, int64_
     XR_HIP(hipSetDevice(b->cfg.device));
     int n = 0;
     size_t stat = 0;
-    XR_HIP(xr_route_occupancy(b->lds_dist ? 1 : 0, b->kzch, b->route_lds, b->route_threads, &n, &stat));
+    XR_HIP(xr_route_occupancy(route_variant(b), &n, &stat));
     *workgroups_per_cu = n;
     *lds_bytes_per_workgroup = (int64_t)(b->route_lds + stat);
     return XR_OK;
@@ -1383,8 +1390,7 @@ int32_t xr_batch_route_order(xr_batch* b, const int32_t* orders_dev, int32_t str
         return fail(XR_ERR_RANGE, "xr_batch_route_order: stride %d < k_max %d", stride, b->k_max);
     XR_HIP(hipSetDevice(b->cfg.device));
     drop_obs_valid(b);
-    XR_HIP(xr_launch_order(&b->dev, orders_dev, stride, net_stats_dev, b->lds_dist ? 1 : 0, b->kzch, b->route_lds,
-                           b->route_threads, static_cast<hipStream_t>(stream)));
+    XR_HIP(xr_launch_order(&b->dev, orders_dev, stride, net_stats_dev, route_variant(b), static_cast<hipStream_t>(stream)));
     return XR_OK;
 }
 
@@ -1405,20 +1411,9 @@ int32_t xr_batch_observation(xr_batch* b, float* out_dev, int64_t env_stride, in
     if (env_stride < (int64_t)2 * b->n_max_nodes)
         return fail(XR_ERR_RANGE, "xr_batch_observation: env_stride %lld too small", (long long)env_stride);
     XR_HIP(hipSetDevice(b->cfg.device));
-    const bool aligned = (env_stride % 4 == 0) && ((reinterpret_cast<uintptr_t>(out_dev) & 15) == 0);
-    const int vec4 = aligned ? (b->all_n_mult4 ? 1 : (b->stream_ok ? 2 : 0)) : 0;
-    XR_HIP(xr_launch_obs(&b->dev, out_dev, env_stride, env_lo, env_hi, b->n_max_nodes, vec4,
+    XR_HIP(xr_launch_obs(&b->dev, out_dev, env_stride, env_lo, env_hi, b->n_max_nodes, obs_store_mode(b, out_dev, env_stride),
                          static_cast<hipStream_t>(stream)));
-    if (env_lo == 0 && env_hi == b->cfg.n_envs && env_stride >= (int64_t)(2 + 7 * (int64_t)b->k_max) * b->n_max_nodes) {
-        b->obs_valid_ptr = out_dev; b->obs_valid_stride = env_stride; b->obs_valid_u8 = false;     // this buffer now holds every slot's observation
-    }
-    if (env_stride >= (int64_t)(2 + 7 * (int64_t)b->k_max) * b->n_max_nodes)
-        for (int g = 0; g < b->n_groups; g++)                                // ... and every group it covers, its slice of it
-            if (env_lo <= b->group_bounds[g] && b->group_bounds[g + 1] <= env_hi) {
-                b->group_valid_ptr[g] = out_dev + (int64_t)(b->group_bounds[g] - env_lo) * env_stride;
-                b->group_valid_stride[g] = env_stride;
-                b->group_valid_u8[g] = false;
-            }
+    if (env_stride >= full_row(b)) mark_obs_valid(b, out_dev, env_stride, false, env_lo, env_hi);      // (a shorter row cannot hold every region's observation)
     return XR_OK;
 }
 
@@ -1432,50 +1427,58 @@ int32_t xr_batch_observation_u8(xr_batch* b, uint8_t* out_dev, int64_t env_strid
     XrBatchDev d = b->dev;
     d.obs_out_u8 = out_dev;
     d.obs_stride = env_stride;
-    // (xr_launch_obs dispatches on obs_out_u8; its `vec4` argument carries k_max for the uint8 form)
-    XR_HIP(xr_launch_obs(&d, nullptr, env_stride, env_lo, env_hi, b->n_max_nodes, b->k_max, static_cast<hipStream_t>(stream)));
-    if (env_lo == 0 && env_hi == b->cfg.n_envs) {
-        b->obs_valid_ptr = out_dev; b->obs_valid_stride = env_stride; b->obs_valid_u8 = true;
-    }
-    for (int g = 0; g < b->n_groups; g++)
-        if (env_lo <= b->group_bounds[g] && b->group_bounds[g + 1] <= env_hi) {
-            b->group_valid_ptr[g] = out_dev + (int64_t)(b->group_bounds[g] - env_lo) * env_stride;
-            b->group_valid_stride[g] = env_stride;
-            b->group_valid_u8[g] = true;
-        }
+    XR_HIP(xr_launch_obs_u8(&d, out_dev, env_stride, env_lo, env_hi, b->n_max_nodes, b->k_max, static_cast<hipStream_t>(stream)));
+    mark_obs_valid(b, out_dev, env_stride, true, env_lo, env_hi);
     return XR_OK;
 }
+
+namespace {
+// One device array of the batch as the fetch / store entry points see it (selector XR_FETCH_*)
+struct ArrayRef {
+    void* p;
+    size_t row;            // bytes per env slot; 0: one scalar for the whole batch
+    size_t bytes;          // the whole array
+    bool store, group;     // admitted by xr_batch_store (part of the env state) / by xr_batch_fetch_group (a per-env array a group may slice)
+};
+
+bool array_ref(const xr_batch* b, int32_t what, ArrayRef& a) {
+    const bool S = true, G = true;      // admitted by xr_batch_store / by xr_batch_fetch_group (!S, !G: not)
+    switch (what) {
+    case XR_FETCH_CUM: a = {b->cum.p, 3 * sizeof(int32_t), 0, S, G}; break;
+    case XR_FETCH_DELTA: a = {b->delta.p, 3 * sizeof(int32_t), 0, S, G}; break;
+    case XR_FETCH_REWARD: a = {b->reward.p, sizeof(double), 0, S, G}; break;
+    case XR_FETCH_DONE: a = {b->done.p, 1, 0, S, G}; break;
+    case XR_FETCH_NLEGAL: a = {b->nlegal.p, sizeof(int32_t), 0, S, G}; break;
+    case XR_FETCH_STATUS: a = {b->status.p, sizeof(int32_t), 0, S, G}; break;
+    case XR_FETCH_LEGAL: a = {b->legal.p, (size_t)b->legal_words * sizeof(uint64_t), 0, S, G}; break;
+    case XR_FETCH_PATH_LEN: a = {b->path_len.p, sizeof(int32_t), 0, S, G}; break;
+    case XR_FETCH_PATH: a = {b->path.p, (size_t)b->path_cap * sizeof(int32_t), 0, !S, G}; break;
+    case XR_FETCH_OWNER: a = {b->owner.p, (size_t)b->n_max * sizeof(int16_t), 0, S, G}; break;
+    case XR_FETCH_HASH: a = {b->hash.p, sizeof(uint64_t), 0, S, G}; break;
+    case XR_FETCH_REGION: a = {b->env_region.p, sizeof(int32_t), 0, S, G}; break;
+    case XR_FETCH_STEPS: a = {b->total_steps.p, 0, sizeof(int64_t), S, !G}; break;
+    case XR_FETCH_SWEEPS: a = {b->sweeps.p, sizeof(int32_t), 0, !S, G}; break;
+    case XR_FETCH_UNITS: a = {(b->queue_last ? b->queue_last : b->queue.p) + 2, 0, sizeof(uint32_t), !S, !G}; break;
+    case XR_FETCH_ROUTE_ORDER: a = {b->route_order.p, sizeof(int32_t), 0, !S, !G}; break;
+    case XR_FETCH_TOUCHED: a = {b->touched.p, sizeof(int32_t), 0, !S, !G}; break;
+    case XR_FETCH_RECORD: a = {b->records.p, sizeof(XrStepRecord), 0, S, G}; break;
+    case XR_FETCH_PHASES: a = {b->phase_cycles.p, 8 * sizeof(long long), 0, !S, !G}; break;
+    case XR_FETCH_REPLAY: a = {b->env_replay.p, sizeof(int32_t), 0, S, G}; break;
+    case XR_FETCH_ENV_STEPS: a = {b->env_steps.p, sizeof(int64_t), 0, S, G}; break;
+    default: return false;
+    }
+    if (a.row) a.bytes = (size_t)b->cfg.n_envs * a.row;
+    return true;
+}
+}  // namespace
 
 int32_t xr_batch_fetch(xr_batch* b, int32_t what, void* dst_dev, size_t dst_bytes, void* stream) {
     if (!b || !dst_dev) return fail(XR_ERR_INVALID, "xr_batch_fetch: null argument");
     if (!b->loaded) return fail(XR_ERR_STATE, "xr_batch_fetch: load regions first");
-    const size_t B = (size_t)b->cfg.n_envs;
-    const void* src = nullptr;
-    size_t bytes = 0;
-    switch (what) {
-    case XR_FETCH_CUM: src = b->cum.p; bytes = B * 3 * sizeof(int32_t); break;
-    case XR_FETCH_DELTA: src = b->delta.p; bytes = B * 3 * sizeof(int32_t); break;
-    case XR_FETCH_REWARD: src = b->reward.p; bytes = B * sizeof(double); break;
-    case XR_FETCH_DONE: src = b->done.p; bytes = B; break;
-    case XR_FETCH_NLEGAL: src = b->nlegal.p; bytes = B * sizeof(int32_t); break;
-    case XR_FETCH_STATUS: src = b->status.p; bytes = B * sizeof(int32_t); break;
-    case XR_FETCH_LEGAL: src = b->legal.p; bytes = B * b->legal_words * sizeof(uint64_t); break;
-    case XR_FETCH_PATH_LEN: src = b->path_len.p; bytes = B * sizeof(int32_t); break;
-    case XR_FETCH_PATH: src = b->path.p; bytes = B * b->path_cap * sizeof(int32_t); break;
-    case XR_FETCH_OWNER: src = b->owner.p; bytes = B * b->n_max * sizeof(int16_t); break;
-    case XR_FETCH_HASH: src = b->hash.p; bytes = B * sizeof(uint64_t); break;
-    case XR_FETCH_REGION: src = b->env_region.p; bytes = B * sizeof(int32_t); break;
-    case XR_FETCH_STEPS: src = b->total_steps.p; bytes = sizeof(int64_t); break;
-    case XR_FETCH_SWEEPS: src = b->sweeps.p; bytes = B * sizeof(int32_t); break;
-    case XR_FETCH_UNITS: src = (b->queue_last ? b->queue_last : b->queue.p) + 2; bytes = sizeof(uint32_t); break;
-    case XR_FETCH_ROUTE_ORDER: src = b->route_order.p; bytes = B * sizeof(int32_t); break;
-    case XR_FETCH_TOUCHED: src = b->touched.p; bytes = B * sizeof(int32_t); break;
-    case XR_FETCH_RECORD: src = b->records.p; bytes = B * sizeof(XrStepRecord); break;
-    case XR_FETCH_PHASES: src = b->phase_cycles.p; bytes = B * 8 * sizeof(long long); break;
-    case XR_FETCH_REPLAY: src = b->env_replay.p; bytes = B * sizeof(int32_t); break;
-    case XR_FETCH_ENV_STEPS: src = b->env_steps.p; bytes = B * sizeof(int64_t); break;
-    default: return fail(XR_ERR_INVALID, "xr_batch_fetch: unknown selector %d", what);
-    }
+    ArrayRef a;
+    if (!array_ref(b, what, a)) return fail(XR_ERR_INVALID, "xr_batch_fetch: unknown selector %d", what);
+    const void* const src = a.p;
+    const size_t bytes = a.bytes;
     if (dst_bytes < bytes)
         return fail(XR_ERR_RANGE, "xr_batch_fetch(%d): destination holds %zu bytes, need %zu", what, dst_bytes, bytes);
     XR_HIP(hipSetDevice(b->cfg.device));
@@ -1489,26 +1492,10 @@ int32_t xr_batch_store(xr_batch* b, int32_t what, const void* src_dev, size_t sr
     if (!b || !src_dev) return fail(XR_ERR_INVALID, "xr_batch_store: null argument");
     if (!b->loaded) return fail(XR_ERR_STATE, "xr_batch_store: load regions first");
     const size_t B = (size_t)b->cfg.n_envs;
-    void* dst = nullptr;
-    size_t bytes = 0;
-    switch (what) {
-    case XR_FETCH_CUM: dst = b->cum.p; bytes = B * 3 * sizeof(int32_t); break;
-    case XR_FETCH_DELTA: dst = b->delta.p; bytes = B * 3 * sizeof(int32_t); break;
-    case XR_FETCH_REWARD: dst = b->reward.p; bytes = B * sizeof(double); break;
-    case XR_FETCH_DONE: dst = b->done.p; bytes = B; break;
-    case XR_FETCH_NLEGAL: dst = b->nlegal.p; bytes = B * sizeof(int32_t); break;
-    case XR_FETCH_STATUS: dst = b->status.p; bytes = B * sizeof(int32_t); break;
-    case XR_FETCH_LEGAL: dst = b->legal.p; bytes = B * b->legal_words * sizeof(uint64_t); break;
-    case XR_FETCH_PATH_LEN: dst = b->path_len.p; bytes = B * sizeof(int32_t); break;
-    case XR_FETCH_OWNER: dst = b->owner.p; bytes = B * b->n_max * sizeof(int16_t); break;
-    case XR_FETCH_HASH: dst = b->hash.p; bytes = B * sizeof(uint64_t); break;
-    case XR_FETCH_REGION: dst = b->env_region.p; bytes = B * sizeof(int32_t); break;
-    case XR_FETCH_REPLAY: dst = b->env_replay.p; bytes = B * sizeof(int32_t); break;
-    case XR_FETCH_ENV_STEPS: dst = b->env_steps.p; bytes = B * sizeof(int64_t); break;
-    case XR_FETCH_RECORD: dst = b->records.p; bytes = B * sizeof(XrStepRecord); break;
-    case XR_FETCH_STEPS: dst = b->total_steps.p; bytes = sizeof(int64_t); break;
-    default: return fail(XR_ERR_INVALID, "xr_batch_store: selector %d is not part of the env state", what);
-    }
+    ArrayRef a;
+    if (!array_ref(b, what, a) || !a.store) return fail(XR_ERR_INVALID, "xr_batch_store: selector %d is not part of the env state", what);
+    void* const dst = a.p;
+    const size_t bytes = a.bytes;
     if (src_bytes != bytes)
         return fail(XR_ERR_RANGE, "xr_batch_store(%d): source holds %zu bytes, the array has %zu", what, src_bytes, bytes);
     XR_HIP(hipSetDevice(b->cfg.device));
@@ -1579,7 +1566,7 @@ int32_t xr_batch_set_groups(xr_batch* b, const int32_t* bounds_host, int32_t n_g
     if (b->group_queue.p) XR_HIP(hipMemset(b->group_queue.p, 0, (size_t)XR_MAX_GROUPS * 8 * sizeof(uint32_t)));
     b->n_groups = n_groups;
     for (int g = 0; g <= n_groups; g++) b->group_bounds[g] = bounds_host[g];
-    for (int g = 0; g < XR_MAX_GROUPS; g++) { b->group_bank[g] = 0; b->group_valid_ptr[g] = nullptr; }
+    for (int g = 0; g < XR_MAX_GROUPS; g++) { b->group_bank[g] = 0; b->group_valid[g].clear(); }
     return XR_OK;
 }
 
@@ -1597,11 +1584,10 @@ int32_t xr_batch_step_group(xr_batch* b, int32_t group, const int32_t* actions_d
     if (flags & ~XR_GROUP_INPLACE) return fail(XR_ERR_INVALID, "xr_batch_step_group: unknown flags 0x%x", flags);
     if (out_dev) return step_observe_impl(b, actions_dev, out_dev, env_stride, stream, (flags & XR_GROUP_INPLACE) != 0, group);
     XR_HIP(hipSetDevice(b->cfg.device));
-    const int lo = b->group_bounds[group];
-    b->obs_valid_ptr = nullptr;
-    b->group_valid_ptr[group] = nullptr;
+    b->obs_valid.clear();
+    b->group_valid[group].clear();
     XrBatchDev d = b->dev;
-    d.env_base = lo; d.env_count = b->group_bounds[group + 1] - lo;
+    const int lo = group_view(b, group, d);
     return launch_route_form(b, d, shift_back(actions_dev, lo), static_cast<hipStream_t>(stream));
 }
 
@@ -1618,9 +1604,8 @@ int32_t xr_batch_random_actions_group(xr_batch* b, int32_t group, int32_t* actio
     if (!b || !actions_dev) return fail(XR_ERR_INVALID, "xr_batch_random_actions_group: null argument");
     if (const int32_t rc = group_check(b, group, "xr_batch_random_actions_group")) return rc;
     XR_HIP(hipSetDevice(b->cfg.device));
-    const int lo = b->group_bounds[group];
     XrBatchDev d = b->dev;
-    d.env_base = lo; d.env_count = b->group_bounds[group + 1] - lo;
+    const int lo = group_view(b, group, d);
     XR_HIP(xr_launch_random_actions(&d, shift_back(actions_dev, lo), seed, static_cast<hipStream_t>(stream)));
     return XR_OK;
 }
@@ -1628,27 +1613,10 @@ int32_t xr_batch_random_actions_group(xr_batch* b, int32_t group, int32_t* actio
 int32_t xr_batch_fetch_group(xr_batch* b, int32_t group, int32_t what, void* dst_dev, size_t dst_bytes, void* stream) {
     if (!b || !dst_dev) return fail(XR_ERR_INVALID, "xr_batch_fetch_group: null argument");
     if (const int32_t rc = group_check(b, group, "xr_batch_fetch_group")) return rc;
-    const char* src = nullptr;         // the array's row 0, and bytes per env row
-    size_t row = 0;
-    switch (what) {
-    case XR_FETCH_RECORD: src = reinterpret_cast<const char*>(b->records.p); row = sizeof(XrStepRecord); break;
-    case XR_FETCH_REWARD: src = reinterpret_cast<const char*>(b->reward.p); row = sizeof(double); break;
-    case XR_FETCH_DONE: src = reinterpret_cast<const char*>(b->done.p); row = 1; break;
-    case XR_FETCH_NLEGAL: src = reinterpret_cast<const char*>(b->nlegal.p); row = sizeof(int32_t); break;
-    case XR_FETCH_STATUS: src = reinterpret_cast<const char*>(b->status.p); row = sizeof(int32_t); break;
-    case XR_FETCH_LEGAL: src = reinterpret_cast<const char*>(b->legal.p); row = (size_t)b->legal_words * sizeof(uint64_t); break;
-    case XR_FETCH_DELTA: src = reinterpret_cast<const char*>(b->delta.p); row = 3 * sizeof(int32_t); break;
-    case XR_FETCH_CUM: src = reinterpret_cast<const char*>(b->cum.p); row = 3 * sizeof(int32_t); break;
-    case XR_FETCH_PATH_LEN: src = reinterpret_cast<const char*>(b->path_len.p); row = sizeof(int32_t); break;
-    case XR_FETCH_PATH: src = reinterpret_cast<const char*>(b->path.p); row = (size_t)b->path_cap * sizeof(int32_t); break;
-    case XR_FETCH_OWNER: src = reinterpret_cast<const char*>(b->owner.p); row = (size_t)b->n_max * sizeof(int16_t); break;
-    case XR_FETCH_HASH: src = reinterpret_cast<const char*>(b->hash.p); row = sizeof(uint64_t); break;
-    case XR_FETCH_REGION: src = reinterpret_cast<const char*>(b->env_region.p); row = sizeof(int32_t); break;
-    case XR_FETCH_SWEEPS: src = reinterpret_cast<const char*>(b->sweeps.p); row = sizeof(int32_t); break;
-    case XR_FETCH_REPLAY: src = reinterpret_cast<const char*>(b->env_replay.p); row = sizeof(int32_t); break;
-    case XR_FETCH_ENV_STEPS: src = reinterpret_cast<const char*>(b->env_steps.p); row = sizeof(int64_t); break;
-    default: return fail(XR_ERR_INVALID, "xr_batch_fetch_group: selector %d is not a per-env array", what);
-    }
+    ArrayRef a;
+    if (!array_ref(b, what, a) || !a.group) return fail(XR_ERR_INVALID, "xr_batch_fetch_group: selector %d is not a per-env array", what);
+    const char* const src = static_cast<const char*>(a.p);         // the array's row 0, and bytes per env row
+    const size_t row = a.row;
     const int lo = b->group_bounds[group], n = b->group_bounds[group + 1] - lo;
     const size_t bytes = (size_t)n * row;
     if (dst_bytes != bytes)

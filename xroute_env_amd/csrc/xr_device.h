@@ -190,3 +190,44 @@ struct XrBatchDev {
     // (xr_unit_u8_aligned), 2 = any N (xr_unit_u8_stream, LDS masks)
     uint8_t* obs_out_u8;
 };
+
+// Which instantiation of the route / order / step-queue kernels a launch takes, and its launch shape (xr_kernels.hip maps
+// (lds_dist, zch) to <LDS_DIST, ZCH> in one place: xr_with_variant)
+struct XrRouteVariant {
+    int lds_dist;            // distance field in LDS (1) or in HBM scratch (0)
+    int zch;                 // 9 / 12: every region has that many layers (sweep router); 0: any; < 0: the frontier routers (XR_ZCH_*)
+    size_t lds_bytes;        // dynamic LDS of the launch
+    int threads;             // workgroup size
+};
+
+// The kernel launchers (xr_kernels.hip, xr_agent.hip; stand-ins that do nothing in tests/hostsan/stub_launch.cpp), declared once: every
+// definition and every caller is checked against these.  Seen only after a HIP runtime header (hipError_t, hipStream_t).
+#ifdef HIP_INCLUDE_HIP_HIP_RUNTIME_H
+extern "C" {
+hipError_t xr_launch_ingest(const uint32_t* rec, int16_t* node_net, int16_t* owner0, int64_t total, hipStream_t st);
+hipError_t xr_launch_reset(const XrBatchDev* b, const uint8_t* mask, int rotate, hipStream_t st);
+hipError_t xr_route_set_max_lds(size_t bytes);
+hipError_t xr_launch_route(const XrBatchDev* b, const int32_t* actions, XrRouteVariant v, hipStream_t st);
+hipError_t xr_launch_order(const XrBatchDev* b, const int32_t* orders, int stride, int32_t* net_stats, XrRouteVariant v, hipStream_t st);
+hipError_t xr_route_occupancy(XrRouteVariant v, int* wg_per_cu, size_t* static_lds);
+hipError_t xr_launch_step_queue(const XrBatchDev* b, const int32_t* actions, XrRouteVariant v, int blocks, hipStream_t st);
+hipError_t xr_launch_route_order(const XrBatchDev* b, const int32_t* actions, int32_t* order, hipStream_t st);
+hipError_t xr_launch_plan(const XrBatchDev* b, const int32_t* actions, uint32_t* next_queue, int32_t* order, int* order_done, hipStream_t st);
+hipError_t xr_launch_netplanes(const XrBatchDev* b, int blocks, int aligned, hipStream_t st);
+hipError_t xr_launch_random_actions(const XrBatchDev* b, int32_t* actions, uint64_t seed, hipStream_t st);
+hipError_t xr_launch_obs(const XrBatchDev* b, float* out, int64_t env_stride, int env_lo, int env_hi, int n_max_nodes, int vec4, hipStream_t st);
+hipError_t xr_launch_obs_u8(const XrBatchDev* b, uint8_t* out, int64_t env_stride, int env_lo, int env_hi, int n_max_nodes, int k_max, hipStream_t st);
+hipError_t xr_launch_unit_helpers(const XrBatchDev* b, int blocks, hipStream_t st);
+hipError_t xr_launch_netplanes_pairs(const XrBatchDev* b, const int32_t* pair_region, const int32_t* pair_net, int n_pairs, float* out, int64_t pair_stride,
+                                     int vec4, hipStream_t st);
+hipError_t xr_launch_guide_masks(const XrBatchDev* b, uint8_t* masks, int k_max, hipStream_t st);
+hipError_t xr_launch_ingest_state(const XrBatchDev* b, const int16_t* owner_in, const uint64_t* legal_in, const int32_t* cum_in, hipStream_t st);
+hipError_t xr_launch_pack_state(const XrBatchDev* b, uint8_t* rows, int64_t row_bytes, int region_base, hipStream_t st);
+hipError_t xr_launch_expand_state(const XrBatchDev* b, const uint8_t* rows, int64_t row_bytes, int n_rows, float* head, int64_t head_stride,
+                                  int32_t* nlegal_out, int32_t* region_out, int vec4, hipStream_t st);
+hipError_t xr_launch_obs_records(const uint32_t* rec, int X, int Y, int Z, const int32_t* nets, int K, float* out, int vec4, hipStream_t st);
+hipError_t xr_launch_net_tower(const void* regions, const int32_t* net_csr, const int32_t* ap_feat, int32_t n_regions, const int32_t* pair_region_dev,
+                               const int32_t* pair_net_dev, int32_t n_pairs, int32_t D, int32_t H, int32_t W, const float* weights_dev, const float* bg_dev,
+                               float* out_dev, int32_t* flags_dev, int32_t normalize, hipStream_t st, int32_t* status);
+}
+#endif

@@ -18,6 +18,7 @@
 // field, and wave64-wide relaxation.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <initializer_list>
 #include <type_traits>
 
 #include "xr_device.h"
@@ -2227,6 +2228,38 @@ __global__ void __launch_bounds__(256) xr_expand_state_kernel(XrBatchDev b, cons
 // ------------------------------------------------------------------------------------------------
 // host-callable launchers (kept here so that only this TU needs the <<<>>> syntax)
 // ------------------------------------------------------------------------------------------------
+// The router variants, in one place: runtime (lds_dist, zch) -> f(std::bool_constant<LDS_DIST>, std::integral_constant<int, ZCH>).  The
+// two round-3 LDS forms exist with the field in LDS only; every other zch in both forms; a zch that is not listed is 0 (any layer count).
+template <int ZCH, class F>
+static auto xr_with_lds(int lds_dist, F&& f) {
+    if constexpr (ZCH != XR_ZCH_DIAL3V2 && ZCH != XR_ZCH_DIAL3) {
+        if (!lds_dist) return f(std::false_type{}, std::integral_constant<int, ZCH>{});
+    }
+    return f(std::true_type{}, std::integral_constant<int, ZCH>{});
+}
+template <class F>
+static auto xr_with_variant(int lds_dist, int zch, F&& f) {
+    switch (zch) {
+    case XR_ZCH_DIAL3V2: return xr_with_lds<XR_ZCH_DIAL3V2>(lds_dist, f);
+    case XR_ZCH_DIAL3: return xr_with_lds<XR_ZCH_DIAL3>(lds_dist, f);
+    case XR_ZCH_DIAL2: return xr_with_lds<XR_ZCH_DIAL2>(lds_dist, f);
+    case XR_ZCH_DIAL: return xr_with_lds<XR_ZCH_DIAL>(lds_dist, f);
+    case 9: return xr_with_lds<9>(lds_dist, f);
+    case 12: return xr_with_lds<12>(lds_dist, f);
+    default: return xr_with_lds<0>(lds_dist, f);
+    }
+}
+// every variant once (12 of them: an LDS-only one answers both values of lds_dist and is visited under 1); stops at the first error
+template <class F>
+static hipError_t xr_each_variant(F&& f) {
+    for (int zch : {XR_ZCH_DIAL3V2, XR_ZCH_DIAL3, XR_ZCH_DIAL2, XR_ZCH_DIAL, 0, 9, 12})
+        for (int lds_dist = 1; lds_dist >= 0; lds_dist--) {
+            const hipError_t e = xr_with_variant(lds_dist, zch, [&](auto L, auto Z) { return L.value == (lds_dist != 0) ? f(L, Z) : hipSuccess; });
+            if (e != hipSuccess) return e;
+        }
+    return hipSuccess;
+}
+
 extern "C" {
 
 hipError_t xr_launch_ingest(const uint32_t* rec, int16_t* node_net, int16_t* owner0, int64_t total, hipStream_t st) {
@@ -2243,190 +2276,48 @@ hipError_t xr_launch_reset(const XrBatchDev* b, const uint8_t* mask, int rotate,
 }
 
 hipError_t xr_route_set_max_lds(size_t bytes) {
-    const void* d2fns[6] = {reinterpret_cast<const void*>(&xr_route_kernel<true, XR_ZCH_DIAL2>),
-                            reinterpret_cast<const void*>(&xr_step_queue_kernel<true, XR_ZCH_DIAL2>),
-                            reinterpret_cast<const void*>(&xr_order_kernel<true, XR_ZCH_DIAL2>),
-                            reinterpret_cast<const void*>(&xr_route_kernel<false, XR_ZCH_DIAL2>),
-                            reinterpret_cast<const void*>(&xr_step_queue_kernel<false, XR_ZCH_DIAL2>),
-                            reinterpret_cast<const void*>(&xr_order_kernel<false, XR_ZCH_DIAL2>)};
-    for (int i = 0; i < 6; i++) {
-        hipError_t e = hipFuncSetAttribute(d2fns[i], hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
-        if (e != hipSuccess) return e;
-    }
-    const void* d3fns[6] = {reinterpret_cast<const void*>(&xr_route_kernel<true, XR_ZCH_DIAL3>),
-                            reinterpret_cast<const void*>(&xr_step_queue_kernel<true, XR_ZCH_DIAL3>),
-                            reinterpret_cast<const void*>(&xr_order_kernel<true, XR_ZCH_DIAL3>),
-                            reinterpret_cast<const void*>(&xr_route_kernel<true, XR_ZCH_DIAL3V2>),
-                            reinterpret_cast<const void*>(&xr_step_queue_kernel<true, XR_ZCH_DIAL3V2>),
-                            reinterpret_cast<const void*>(&xr_order_kernel<true, XR_ZCH_DIAL3V2>)};
-    for (int i = 0; i < 6; i++) {
-        hipError_t e = hipFuncSetAttribute(d3fns[i], hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
-        if (e != hipSuccess) return e;
-    }
-    const void* dfns[6] = {reinterpret_cast<const void*>(&xr_route_kernel<true, XR_ZCH_DIAL>),
-                           reinterpret_cast<const void*>(&xr_step_queue_kernel<true, XR_ZCH_DIAL>),
-                           reinterpret_cast<const void*>(&xr_order_kernel<true, XR_ZCH_DIAL>),
-                           reinterpret_cast<const void*>(&xr_route_kernel<false, XR_ZCH_DIAL>),
-                           reinterpret_cast<const void*>(&xr_step_queue_kernel<false, XR_ZCH_DIAL>),
-                           reinterpret_cast<const void*>(&xr_order_kernel<false, XR_ZCH_DIAL>)};
-    for (int i = 0; i < 6; i++) {
-        hipError_t e = hipFuncSetAttribute(dfns[i], hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
-        if (e != hipSuccess) return e;
-    }
-    const void* fns[6] = {reinterpret_cast<const void*>(&xr_route_kernel<true, 0>), reinterpret_cast<const void*>(&xr_route_kernel<true, 9>),
-                          reinterpret_cast<const void*>(&xr_route_kernel<true, 12>), reinterpret_cast<const void*>(&xr_route_kernel<false, 0>),
-                          reinterpret_cast<const void*>(&xr_route_kernel<false, 9>), reinterpret_cast<const void*>(&xr_route_kernel<false, 12>)};
-    const void* qfns[6] = {reinterpret_cast<const void*>(&xr_step_queue_kernel<true, 0>), reinterpret_cast<const void*>(&xr_step_queue_kernel<true, 9>),
-                           reinterpret_cast<const void*>(&xr_step_queue_kernel<true, 12>), reinterpret_cast<const void*>(&xr_step_queue_kernel<false, 0>),
-                           reinterpret_cast<const void*>(&xr_step_queue_kernel<false, 9>), reinterpret_cast<const void*>(&xr_step_queue_kernel<false, 12>)};
-    const void* ofns[6] = {reinterpret_cast<const void*>(&xr_order_kernel<true, 0>), reinterpret_cast<const void*>(&xr_order_kernel<true, 9>),
-                           reinterpret_cast<const void*>(&xr_order_kernel<true, 12>), reinterpret_cast<const void*>(&xr_order_kernel<false, 0>),
-                           reinterpret_cast<const void*>(&xr_order_kernel<false, 9>), reinterpret_cast<const void*>(&xr_order_kernel<false, 12>)};
-    for (int i = 0; i < 6; i++) {
-        hipError_t e = hipFuncSetAttribute(fns[i], hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
-        if (e != hipSuccess) return e;
-        e = hipFuncSetAttribute(ofns[i], hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
-        if (e != hipSuccess) return e;
-        e = hipFuncSetAttribute(qfns[i], hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
-        if (e != hipSuccess) return e;
-    }
-    // the uint8-observation step kernels (xr_batch_step_observe_u8): the same LDS as their fp32 twins
-    const void* u8fns[12] = {reinterpret_cast<const void*>(&xr_step_queue_u8_kernel<true, XR_ZCH_DIAL3V2>),
-                             reinterpret_cast<const void*>(&xr_step_queue_u8_kernel<true, XR_ZCH_DIAL3>),
-                             reinterpret_cast<const void*>(&xr_step_queue_u8_kernel<true, XR_ZCH_DIAL2>),
-                             reinterpret_cast<const void*>(&xr_step_queue_u8_kernel<false, XR_ZCH_DIAL2>),
-                             reinterpret_cast<const void*>(&xr_step_queue_u8_kernel<true, XR_ZCH_DIAL>),
-                             reinterpret_cast<const void*>(&xr_step_queue_u8_kernel<false, XR_ZCH_DIAL>),
-                             reinterpret_cast<const void*>(&xr_step_queue_u8_kernel<true, 0>), reinterpret_cast<const void*>(&xr_step_queue_u8_kernel<true, 9>),
-                             reinterpret_cast<const void*>(&xr_step_queue_u8_kernel<true, 12>), reinterpret_cast<const void*>(&xr_step_queue_u8_kernel<false, 0>),
-                             reinterpret_cast<const void*>(&xr_step_queue_u8_kernel<false, 9>), reinterpret_cast<const void*>(&xr_step_queue_u8_kernel<false, 12>)};
-    for (int i = 0; i < 12; i++) {
-        hipError_t e = hipFuncSetAttribute(u8fns[i], hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
-        if (e != hipSuccess) return e;
-    }
-    return hipSuccess;
+    return xr_each_variant([&](auto L, auto Z) {
+        const void* fns[4] = {reinterpret_cast<const void*>(&xr_route_kernel<L.value, Z.value>), reinterpret_cast<const void*>(&xr_order_kernel<L.value, Z.value>),
+                              reinterpret_cast<const void*>(&xr_step_queue_kernel<L.value, Z.value>),
+                              reinterpret_cast<const void*>(&xr_step_queue_u8_kernel<L.value, Z.value>)};
+        for (const void* fn : fns) {
+            const hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+            if (e != hipSuccess) return e;
+        }
+        return hipSuccess;
+    });
 }
 
-// zch: 9 / 12 when every region of the batch has exactly that many layers, else 0
-hipError_t xr_launch_route(const XrBatchDev* b, const int32_t* actions, int lds_dist, int zch, size_t lds_bytes,
-                           int threads, hipStream_t st) {
-    const dim3 g(b->env_count > 0 ? b->env_count : b->n_envs), t(threads);
-    if (zch == XR_ZCH_DIAL3V2) {
-        hipLaunchKernelGGL((xr_route_kernel<true, XR_ZCH_DIAL3V2>), g, t, lds_bytes, st, *b, actions);
-    } else if (zch == XR_ZCH_DIAL3) {
-        hipLaunchKernelGGL((xr_route_kernel<true, XR_ZCH_DIAL3>), g, t, lds_bytes, st, *b, actions);
-    } else if (zch == XR_ZCH_DIAL2) {
-        if (lds_dist) hipLaunchKernelGGL((xr_route_kernel<true, XR_ZCH_DIAL2>), g, t, lds_bytes, st, *b, actions);
-        else hipLaunchKernelGGL((xr_route_kernel<false, XR_ZCH_DIAL2>), g, t, lds_bytes, st, *b, actions);
-    } else if (zch == XR_ZCH_DIAL) {
-        if (lds_dist) hipLaunchKernelGGL((xr_route_kernel<true, XR_ZCH_DIAL>), g, t, lds_bytes, st, *b, actions);
-        else hipLaunchKernelGGL((xr_route_kernel<false, XR_ZCH_DIAL>), g, t, lds_bytes, st, *b, actions);
-    } else if (lds_dist) {
-        if (zch == 9) hipLaunchKernelGGL((xr_route_kernel<true, 9>), g, t, lds_bytes, st, *b, actions);
-        else if (zch == 12) hipLaunchKernelGGL((xr_route_kernel<true, 12>), g, t, lds_bytes, st, *b, actions);
-        else hipLaunchKernelGGL((xr_route_kernel<true, 0>), g, t, lds_bytes, st, *b, actions);
-    } else {
-        if (zch == 9) hipLaunchKernelGGL((xr_route_kernel<false, 9>), g, t, lds_bytes, st, *b, actions);
-        else if (zch == 12) hipLaunchKernelGGL((xr_route_kernel<false, 12>), g, t, lds_bytes, st, *b, actions);
-        else hipLaunchKernelGGL((xr_route_kernel<false, 0>), g, t, lds_bytes, st, *b, actions);
-    }
+hipError_t xr_launch_route(const XrBatchDev* b, const int32_t* actions, XrRouteVariant v, hipStream_t st) {
+    const dim3 g(b->env_count > 0 ? b->env_count : b->n_envs), t(v.threads);
+    xr_with_variant(v.lds_dist, v.zch, [&](auto L, auto Z) { hipLaunchKernelGGL((xr_route_kernel<L.value, Z.value>), g, t, v.lds_bytes, st, *b, actions); });
     return hipGetLastError();
 }
 
-hipError_t xr_launch_order(const XrBatchDev* b, const int32_t* orders, int stride, int32_t* net_stats, int lds_dist, int zch,
-                           size_t lds_bytes, int threads, hipStream_t st) {
-    const dim3 g(b->n_envs), t(threads);
-    if (zch == XR_ZCH_DIAL3V2) {
-        hipLaunchKernelGGL((xr_order_kernel<true, XR_ZCH_DIAL3V2>), g, t, lds_bytes, st, *b, orders, stride, net_stats);
-    } else if (zch == XR_ZCH_DIAL3) {
-        hipLaunchKernelGGL((xr_order_kernel<true, XR_ZCH_DIAL3>), g, t, lds_bytes, st, *b, orders, stride, net_stats);
-    } else if (zch == XR_ZCH_DIAL2) {
-        if (lds_dist) hipLaunchKernelGGL((xr_order_kernel<true, XR_ZCH_DIAL2>), g, t, lds_bytes, st, *b, orders, stride, net_stats);
-        else hipLaunchKernelGGL((xr_order_kernel<false, XR_ZCH_DIAL2>), g, t, lds_bytes, st, *b, orders, stride, net_stats);
-    } else if (zch == XR_ZCH_DIAL) {
-        if (lds_dist) hipLaunchKernelGGL((xr_order_kernel<true, XR_ZCH_DIAL>), g, t, lds_bytes, st, *b, orders, stride, net_stats);
-        else hipLaunchKernelGGL((xr_order_kernel<false, XR_ZCH_DIAL>), g, t, lds_bytes, st, *b, orders, stride, net_stats);
-    } else if (lds_dist) {
-        if (zch == 9) hipLaunchKernelGGL((xr_order_kernel<true, 9>), g, t, lds_bytes, st, *b, orders, stride, net_stats);
-        else if (zch == 12) hipLaunchKernelGGL((xr_order_kernel<true, 12>), g, t, lds_bytes, st, *b, orders, stride, net_stats);
-        else hipLaunchKernelGGL((xr_order_kernel<true, 0>), g, t, lds_bytes, st, *b, orders, stride, net_stats);
-    } else {
-        if (zch == 9) hipLaunchKernelGGL((xr_order_kernel<false, 9>), g, t, lds_bytes, st, *b, orders, stride, net_stats);
-        else if (zch == 12) hipLaunchKernelGGL((xr_order_kernel<false, 12>), g, t, lds_bytes, st, *b, orders, stride, net_stats);
-        else hipLaunchKernelGGL((xr_order_kernel<false, 0>), g, t, lds_bytes, st, *b, orders, stride, net_stats);
-    }
+hipError_t xr_launch_order(const XrBatchDev* b, const int32_t* orders, int stride, int32_t* net_stats, XrRouteVariant v, hipStream_t st) {
+    const dim3 g(b->n_envs), t(v.threads);
+    xr_with_variant(v.lds_dist, v.zch,
+                    [&](auto L, auto Z) { hipLaunchKernelGGL((xr_order_kernel<L.value, Z.value>), g, t, v.lds_bytes, st, *b, orders, stride, net_stats); });
     return hipGetLastError();
 }
 
 // resident workgroups per CU of the step kernel as the runtime would place it, and its static LDS
-hipError_t xr_route_occupancy(int lds_dist, int zch, size_t lds_bytes, int threads, int* wg_per_cu, size_t* static_lds) {
-    const void* fn = zch == XR_ZCH_DIAL3V2 ? reinterpret_cast<const void*>(&xr_route_kernel<true, XR_ZCH_DIAL3V2>)
-                     : zch == XR_ZCH_DIAL3 ? reinterpret_cast<const void*>(&xr_route_kernel<true, XR_ZCH_DIAL3>)
-                     : zch == XR_ZCH_DIAL2 ? (lds_dist ? reinterpret_cast<const void*>(&xr_route_kernel<true, XR_ZCH_DIAL2>)
-                                                     : reinterpret_cast<const void*>(&xr_route_kernel<false, XR_ZCH_DIAL2>))
-                     : zch == XR_ZCH_DIAL ? (lds_dist ? reinterpret_cast<const void*>(&xr_route_kernel<true, XR_ZCH_DIAL>)
-                                                    : reinterpret_cast<const void*>(&xr_route_kernel<false, XR_ZCH_DIAL>))
-                     : lds_dist ? (zch == 9 ? reinterpret_cast<const void*>(&xr_route_kernel<true, 9>)
-                                 : zch == 12 ? reinterpret_cast<const void*>(&xr_route_kernel<true, 12>)
-                                             : reinterpret_cast<const void*>(&xr_route_kernel<true, 0>))
-                              : (zch == 9 ? reinterpret_cast<const void*>(&xr_route_kernel<false, 9>)
-                                 : zch == 12 ? reinterpret_cast<const void*>(&xr_route_kernel<false, 12>)
-                                             : reinterpret_cast<const void*>(&xr_route_kernel<false, 0>));
+hipError_t xr_route_occupancy(XrRouteVariant v, int* wg_per_cu, size_t* static_lds) {
+    const void* fn = xr_with_variant(v.lds_dist, v.zch, [](auto L, auto Z) { return reinterpret_cast<const void*>(&xr_route_kernel<L.value, Z.value>); });
     hipFuncAttributes attr;
     hipError_t e = hipFuncGetAttributes(&attr, fn);
     if (e != hipSuccess) return e;
     *static_lds = attr.sharedSizeBytes;
-    return hipOccupancyMaxActiveBlocksPerMultiprocessor(wg_per_cu, fn, threads, lds_bytes);
+    return hipOccupancyMaxActiveBlocksPerMultiprocessor(wg_per_cu, fn, v.threads, v.lds_bytes);
 }
 
-// b->obs_out_u8 != null: the uint8-observation twin of every variant (xr_step_queue_u8_kernel)
-static void xr_launch_step_queue_u8(const XrBatchDev* b, const int32_t* actions, int lds_dist, int zch, size_t lds_bytes, dim3 g, dim3 t,
-                                    hipStream_t st) {
-    if (zch == XR_ZCH_DIAL3V2) {
-        hipLaunchKernelGGL((xr_step_queue_u8_kernel<true, XR_ZCH_DIAL3V2>), g, t, lds_bytes, st, *b, actions);
-    } else if (zch == XR_ZCH_DIAL3) {
-        hipLaunchKernelGGL((xr_step_queue_u8_kernel<true, XR_ZCH_DIAL3>), g, t, lds_bytes, st, *b, actions);
-    } else if (zch == XR_ZCH_DIAL2) {
-        if (lds_dist) hipLaunchKernelGGL((xr_step_queue_u8_kernel<true, XR_ZCH_DIAL2>), g, t, lds_bytes, st, *b, actions);
-        else hipLaunchKernelGGL((xr_step_queue_u8_kernel<false, XR_ZCH_DIAL2>), g, t, lds_bytes, st, *b, actions);
-    } else if (zch == XR_ZCH_DIAL) {
-        if (lds_dist) hipLaunchKernelGGL((xr_step_queue_u8_kernel<true, XR_ZCH_DIAL>), g, t, lds_bytes, st, *b, actions);
-        else hipLaunchKernelGGL((xr_step_queue_u8_kernel<false, XR_ZCH_DIAL>), g, t, lds_bytes, st, *b, actions);
-    } else if (lds_dist) {
-        if (zch == 9) hipLaunchKernelGGL((xr_step_queue_u8_kernel<true, 9>), g, t, lds_bytes, st, *b, actions);
-        else if (zch == 12) hipLaunchKernelGGL((xr_step_queue_u8_kernel<true, 12>), g, t, lds_bytes, st, *b, actions);
-        else hipLaunchKernelGGL((xr_step_queue_u8_kernel<true, 0>), g, t, lds_bytes, st, *b, actions);
-    } else {
-        if (zch == 9) hipLaunchKernelGGL((xr_step_queue_u8_kernel<false, 9>), g, t, lds_bytes, st, *b, actions);
-        else if (zch == 12) hipLaunchKernelGGL((xr_step_queue_u8_kernel<false, 12>), g, t, lds_bytes, st, *b, actions);
-        else hipLaunchKernelGGL((xr_step_queue_u8_kernel<false, 0>), g, t, lds_bytes, st, *b, actions);
-    }
-}
-
-hipError_t xr_launch_step_queue(const XrBatchDev* b, const int32_t* actions, int lds_dist, int zch, size_t lds_bytes,
-                                int threads, int blocks, hipStream_t st) {
-    const dim3 g(blocks), t(threads);
-    if (b->obs_out_u8) {
-        xr_launch_step_queue_u8(b, actions, lds_dist, zch, lds_bytes, g, t, st);
-    } else if (zch == XR_ZCH_DIAL3V2) {
-        hipLaunchKernelGGL((xr_step_queue_kernel<true, XR_ZCH_DIAL3V2>), g, t, lds_bytes, st, *b, actions);
-    } else if (zch == XR_ZCH_DIAL3) {
-        hipLaunchKernelGGL((xr_step_queue_kernel<true, XR_ZCH_DIAL3>), g, t, lds_bytes, st, *b, actions);
-    } else if (zch == XR_ZCH_DIAL2) {
-        if (lds_dist) hipLaunchKernelGGL((xr_step_queue_kernel<true, XR_ZCH_DIAL2>), g, t, lds_bytes, st, *b, actions);
-        else hipLaunchKernelGGL((xr_step_queue_kernel<false, XR_ZCH_DIAL2>), g, t, lds_bytes, st, *b, actions);
-    } else if (zch == XR_ZCH_DIAL) {
-        if (lds_dist) hipLaunchKernelGGL((xr_step_queue_kernel<true, XR_ZCH_DIAL>), g, t, lds_bytes, st, *b, actions);
-        else hipLaunchKernelGGL((xr_step_queue_kernel<false, XR_ZCH_DIAL>), g, t, lds_bytes, st, *b, actions);
-    } else if (lds_dist) {
-        if (zch == 9) hipLaunchKernelGGL((xr_step_queue_kernel<true, 9>), g, t, lds_bytes, st, *b, actions);
-        else if (zch == 12) hipLaunchKernelGGL((xr_step_queue_kernel<true, 12>), g, t, lds_bytes, st, *b, actions);
-        else hipLaunchKernelGGL((xr_step_queue_kernel<true, 0>), g, t, lds_bytes, st, *b, actions);
-    } else {
-        if (zch == 9) hipLaunchKernelGGL((xr_step_queue_kernel<false, 9>), g, t, lds_bytes, st, *b, actions);
-        else if (zch == 12) hipLaunchKernelGGL((xr_step_queue_kernel<false, 12>), g, t, lds_bytes, st, *b, actions);
-        else hipLaunchKernelGGL((xr_step_queue_kernel<false, 0>), g, t, lds_bytes, st, *b, actions);
-    }
+// b->obs_out_u8 != null: the uint8-observation twin of the variant (xr_step_queue_u8_kernel)
+hipError_t xr_launch_step_queue(const XrBatchDev* b, const int32_t* actions, XrRouteVariant v, int blocks, hipStream_t st) {
+    const dim3 g(blocks), t(v.threads);
+    xr_with_variant(v.lds_dist, v.zch, [&](auto L, auto Z) {
+        if (b->obs_out_u8) hipLaunchKernelGGL((xr_step_queue_u8_kernel<L.value, Z.value>), g, t, v.lds_bytes, st, *b, actions);
+        else hipLaunchKernelGGL((xr_step_queue_kernel<L.value, Z.value>), g, t, v.lds_bytes, st, *b, actions);
+    });
     return hipGetLastError();
 }
 
@@ -2462,24 +2353,9 @@ hipError_t xr_launch_random_actions(const XrBatchDev* b, int32_t* actions, uint6
     return hipGetLastError();
 }
 
-hipError_t xr_launch_obs(const XrBatchDev* b, float* out, int64_t env_stride, int env_lo, int env_hi, int n_max_nodes,
-                         int vec4, hipStream_t st) {
-    const int n_env = env_hi - env_lo;
-    if (n_env <= 0) return hipSuccess;
+hipError_t xr_launch_obs(const XrBatchDev* b, float* out, int64_t env_stride, int env_lo, int env_hi, int n_max_nodes, int vec4, hipStream_t st) {
+    if (env_hi <= env_lo) return hipSuccess;
     const size_t lds = (size_t)(b->legal_words * 64 + b->legal_words + 1) * sizeof(int);
-    if (b->obs_out_u8) {
-        // uint8 observation (xr_batch_observation_u8): rows at b->obs_out_u8, env_stride in bytes; `out` is unused and `vec4` carries
-        // k_max (the longest row: (2 + 7 k_max) n_max bytes, 256 slots of 16 bytes per workgroup)
-        const int64_t row = (int64_t)(2 + 7 * (int64_t)vec4) * n_max_nodes;
-        const int chunks = (int)((row + 4095) / 4096);
-        if (chunks <= 0) return hipSuccess;
-        for (int lo = env_lo; lo < env_hi; lo += 32768) {
-            const int cnt = (env_hi - lo) < 32768 ? (env_hi - lo) : 32768;
-            hipLaunchKernelGGL(xr_obs_u8_kernel, dim3(chunks, cnt), dim3(256), lds, st, *b, b->obs_out_u8 + (int64_t)(lo - env_lo) * env_stride,
-                               env_stride, lo);
-        }
-        return hipGetLastError();
-    }
     // gridDim.y <= 65535: slice the env range
     for (int lo = env_lo; lo < env_hi; lo += 32768) {
         const int cnt = (env_hi - lo) < 32768 ? (env_hi - lo) : 32768;
@@ -2494,6 +2370,20 @@ hipError_t xr_launch_obs(const XrBatchDev* b, float* out, int64_t env_stride, in
             const int chunks = (n_max_nodes + 255) / 256;
             hipLaunchKernelGGL(xr_obs_kernel<1>, dim3(chunks, cnt), dim3(256), lds, st, *b, o, env_stride, lo);
         }
+    }
+    return hipGetLastError();
+}
+
+// uint8 observation (xr_batch_observation_u8): rows of env_stride bytes at `out` (what b->obs_out_u8 / obs_stride say too: the kernel reads
+// those); the longest row is (2 + 7 k_max) n_max bytes, 256 slots of 16 bytes per workgroup
+hipError_t xr_launch_obs_u8(const XrBatchDev* b, uint8_t* out, int64_t env_stride, int env_lo, int env_hi, int n_max_nodes, int k_max, hipStream_t st) {
+    if (env_hi <= env_lo) return hipSuccess;
+    const size_t lds = (size_t)(b->legal_words * 64 + b->legal_words + 1) * sizeof(int);
+    const int chunks = (int)(((2 + 7 * (int64_t)k_max) * n_max_nodes + 4095) / 4096);
+    if (chunks <= 0) return hipSuccess;
+    for (int lo = env_lo; lo < env_hi; lo += 32768) {
+        const int cnt = (env_hi - lo) < 32768 ? (env_hi - lo) : 32768;
+        hipLaunchKernelGGL(xr_obs_u8_kernel, dim3(chunks, cnt), dim3(256), lds, st, *b, out + (int64_t)(lo - env_lo) * env_stride, env_stride, lo);
     }
     return hipGetLastError();
 }
