@@ -12,6 +12,7 @@ import numpy as np
 import pytest
 import torch
 
+from tests.helpers import assert_rows_match_oracle
 from xroute_env_amd import _lib
 from xroute_env_amd.batch import RegionBatch
 from xroute_env_amd.regions import config_regions, generate_region
@@ -133,6 +134,10 @@ def test_step_u8_equals_fp32_twin(which, inplace):
         _assert_state_equal(_state(a), _state(b), (which, inplace, t))
         assert a.legal_sets() == b.legal_sets()
         _assert_rows_cast(ub, fa, _lens(a), (which, inplace, t))
+        # and both against the oracle, not only against each other; the buffers started as zeros and are not refilled between steps, so
+        # older planes may remain up to the longest row: behind that, stride padding included, the zeros must still be there
+        assert_rows_match_oracle(b, ub, 0, n, 0, False, (which, inplace, t, "u8"))
+        assert_rows_match_oracle(a, fa, 0, n, 0.0, False, (which, inplace, t, "fp32"))
         seen.add(tuple(a.fetch("region").cpu().tolist()))
     assert len(seen) > 1                            # episodes ended, auto-reset and rotated on the way
 
@@ -240,6 +245,7 @@ def test_u8_group_steps_equal_lockstep():
         got = ua[lo:hi].cpu().numpy()
         for i, m in enumerate(lens):
             assert np.array_equal(got[i, :m], rows[i, :m]), (g, i)
+    assert_rows_match_oracle(a, ua, 0, n, 0, False, "groups")        # the twin runs the same kernel: the oracle does not
 
 
 # ---- 5. config-5 size (HBM-scratch route) ------------------------------------------------------------------------------------------

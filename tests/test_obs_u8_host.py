@@ -44,3 +44,43 @@ def test_fixed_spaces_uint8():
     vec, _ = sp.fixed_spaces((24, 40, 9), 36, batch=8, sp=sp, row=254 * 8640, dtype=np.uint8)
     assert vec["grid"].dtype == np.uint8 and vec["grid"].shape == (8, 254 * 8640)
     assert sp.fixed_spaces((24, 40, 9), 36, sp=sp)[0]["grid"].dtype == np.float32      # the default keeps today's spaces
+
+
+def test_obs_writer_shape_table_reaches_every_class():
+    """The shape table of tests/test_gpu_obs_writers.py (tests/helpers.py) still reaches every class the observation writers branch
+    on — conditions on the table and the generator, not measurements: an edit that drops a class fails here, without a GPU."""
+    from oracle import xr_oracle as orc
+    from tests import helpers as H
+    regions = {name: H.obs_set_regions(name) for name in H.OBS_SETS}
+    for name, rs in regions.items():
+        assert rs and all(r.n_nets >= 1 for r in rs), name                      # every generated region has at least one net
+        for r in rs:
+            orc.OracleEnv(r)                                                     # and the oracle takes it
+    ns = sorted({r.n_nodes for rs in regions.values() for r in rs})
+    assert {d[0] * d[1] * d[2] for ds in H.OBS_SHAPE_SETS.values() for d in ds} <= set(ns)
+    # where a unit starts in its 16-byte slot: all sixteen residues, odd ones included
+    assert {((2 + 7 * rank) * n) % 16 for n in ns for rank in range(9)} == set(range(16))
+    assert {n % 2 for n in ns if n >= 128} == {0, 1}
+    assert any(2 * n < 16 for n in ns) and any(7 * n < 128 for n in ns)         # planes 0..1 without a whole slot, a unit without a whole line
+    assert any(n % 4 == 0 and n % 16 != 0 for n in ns)                          # fp32 aligned, uint8 not
+    assert any(n % 16 == 0 for n in ns) and any(n % 4 for n in ns)
+    assert any(n > 1024 and n % 2 for n in ns)
+    # the mixed batch: aligned regions beside others, so that the aligned ones take the stream writers too
+    mixed = [r.n_nodes for r in regions["mixed"]]
+    assert any(n % 16 == 0 for n in mixed) and any(n % 4 for n in mixed) and any(n % 4 == 0 and n % 16 for n in mixed + ns)
+    assert len(set(mixed)) > 4
+    # ids of 128 and more, three legal words and more
+    many = regions["many_nets"]
+    assert all(128 < r.n_nets <= 255 for r in many) and all((r.n_nets + 63) // 64 >= 3 for r in many)
+    # exactly 255 nets: the uint8 limit itself, once with every net legal after a reset and once only declared (the region of the
+    # 256-net refusal test); the oracle builds the observation, ids up to 255
+    r255, declared = regions["exactly_255"][:2]
+    assert r255.n_nets == 255 and declared.n_nets == 255 and max(r.n_nets for r in regions["exactly_255"]) == 255
+    ids = np.arange(1, 256, dtype=np.int32)
+    assert np.array_equal(orc.OracleEnv(r255).legal(), ids) and 0 < orc.OracleEnv(declared).nlegal() < 255
+    for r in (r255, declared):
+        obs = orc.build_observation(r.dims, r.nodes, ids)
+        planes = obs.reshape(obs.shape[0], r.n_nodes)
+        assert obs.shape[0] == 2 + 7 * 255 and np.array_equal(planes[1, :255], ids.astype(np.float32))
+        assert planes[2:9].any() and planes[2 + 7 * 254:].any() == (r is r255)   # a net without access points: seven planes of zeros
+        assert (obs == np.round(obs)).all() and obs.min() >= 0 and obs.max() == 255
