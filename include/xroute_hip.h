@@ -423,6 +423,35 @@ int32_t xr_batch_step_observe_u8(xr_batch* b, int32_t group, const int32_t* acti
                                  void* stream);
 int32_t xr_batch_observation_u8(xr_batch* b, uint8_t* out_dev, int64_t env_stride, int32_t env_lo, int32_t env_hi, void* stream);
 
+/* ---- lookahead: what every candidate net would cost, without stepping ---- */
+/* From the state every env is in now: the metric deltas, status and reward xr_batch_step would publish for each net the env may still
+ * pick — the one-ply expansion of the reference's MCTS trainer (baseline/xroute/trainer4/dispatcher.py:113-118 re-routes the region from
+ * scratch per selection), the greedy cost baseline, the exact one-step target of a DQN.  Every (env, candidate) pair is routed by the same
+ * router the step takes (xr_config.router, dial_mult, the XR-Maze v2 knobs and loaded guides included) in a throw-away copy of the slot.
+ *   group            -1: the whole batch, rows [0, n_envs).  >= 0: that env group (xr_batch_set_groups); rows start at the group's first
+ *                    slot, as in xr_batch_step_observe_u8, and the work is enqueued on `stream` only.
+ *   cand_mask_dev    NULL: every legal net.  Else uint64 [rows][legal_words]: the candidates of an env are legal & mask (bits beyond the
+ *                    region's nets are ignored).
+ *   out_dev          int32 [rows][k_cap][4], k_cap >= k_max.  The entry of net n (1-based) is at index n - 1: {d_violation, d_wirelength,
+ *                    d_via, status} = exactly the delta and the XR_ENV_* status xr_batch_step would publish for this env if n were its
+ *                    action now.  Every entry that is not a candidate (net not legal, masked out, index beyond the region's nets) is
+ *                    {0, 0, 0, -1}.  An env that is done (no legal net) gets only such rows: lookahead does not look through an auto-reset.
+ *   reward_out_dev   NULL, or double [rows][k_cap]: the trainers' reward -(w_violation*dv + w_via*dvia + w_wirelength*dwl) with the bits
+ *                    the step's record would carry; -inf for non-candidates, so an arg-max over a row is the greedy action.
+ * Errors (the batch is untouched after any of them): XR_ERR_INVALID null b / out_dev, or a group outside -1 .. n_groups - 1; XR_ERR_STATE
+ * before xr_batch_load_regions; XR_ERR_RANGE k_cap < k_max; XR_ERR_RANGE for batches whose distance field does not fit LDS (the
+ * HBM-scratch router forms, force_scratch_field included) and for stream_per_region: the shadow slots have no scratch rows of their own.
+ * Contract.  Lookahead never synchronises: it only enqueues on `stream` (a planning kernel, then one persistent launch).  It may allocate
+ * its private memory (shadow slots: about workgroups x (2*n_max + 4*path_cap) bytes, a task list, counters) on the first call, per batch
+ * and per group.  It leaves NO TRACE in the batch: every array xr_batch_fetch returns (owner, legal, cum, delta, reward, done, status, path,
+ * path_len, hash, region, replay, env_steps, steps, sweeps, records, ...) is only read, and the validity of the in-place observation
+ * buffers (fp32 and uint8, batch-wide and per group) is kept — an xr_batch_step_observe_inplace after a lookahead still takes the in-place
+ * path.  Lookaheads of DIFFERENT groups may be in flight at once on different streams, under the concurrency contract of
+ * xr_batch_step_group (each group has shadow slots and counters of its own; no workgroup waits for another); a lookahead of one group and
+ * steps of the SAME group are ordered by the caller, and so are a whole-batch lookahead and any step. */
+int32_t xr_batch_lookahead(xr_batch* b, int32_t group, const uint64_t* cand_mask_dev, int32_t* out_dev, int32_t k_cap, double* reward_out_dev,
+                           void* stream);
+
 /* ---- XR-Maze v2: global-route guides (optional) ---------------------------------------------- */
 /* The reference's simulator runs with `-follow_guide 1` (ispd/ispd18_test1/run-net-ordering-training.tcl:3) on the guide file
  * it ships (ispd/ispd18_test1/ispd18_test1.input.guide: per net, rectangles per metal layer).  With xr_config.guide_cost > 0 a

@@ -32,6 +32,7 @@ SYMBOLS = [
     "xr_agent_obstacle_tower_weights", "xr_agent_obstacle_tower", "xr_agent_net_tower_weights", "xr_agent_matrix_mode", "xr_batch_net_vectors", "xr_agent_actor_weights", "xr_agent_actor", "xr_agent_actor_sample",
     "xr_batch_set_groups", "xr_batch_step_group", "xr_batch_random_actions_group", "xr_batch_fetch_group",
     "xr_batch_step_observe_u8", "xr_batch_observation_u8",
+    "xr_batch_lookahead",
     "xr_observation_from_records", "xr_proto_decode", "xr_proto_encode_response", "xr_proto_encode_request",
 ]
 
@@ -121,6 +122,7 @@ def lib():
     L.xr_batch_step_group.argtypes = [vp, C.c_int32, vp, vp, C.c_int64, C.c_int32, vp]
     L.xr_batch_step_observe_u8.argtypes = [vp, C.c_int32, vp, vp, C.c_int64, C.c_int32, vp]
     L.xr_batch_observation_u8.argtypes = [vp, vp, C.c_int64, C.c_int32, C.c_int32, vp]
+    L.xr_batch_lookahead.argtypes = [vp, C.c_int32, vp, vp, C.c_int32, vp, vp]
     L.xr_batch_random_actions_group.argtypes = [vp, C.c_int32, vp, C.c_uint64, vp]
     L.xr_batch_fetch_group.argtypes = [vp, C.c_int32, C.c_int32, vp, C.c_size_t, vp]
     L.xr_agent_obstacle_tower_weights.argtypes = []

@@ -282,6 +282,41 @@ class RegionBatch:
                                                    self._stream_arg(stream)))
         return out
 
+    # ---- lookahead: what every candidate net would cost, without stepping (xr_batch_lookahead) ---------------------------------
+    def lookahead(self, mask: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None, reward_out: Optional[torch.Tensor] = None,
+                  group: Optional[int] = None, stream=None):
+        """From the state every env is in now, price every net it may still pick; the batch is left exactly as it was.  Returns
+        (delta_status int32 [rows, k_max, 4], reward float64 [rows, k_max]) as device tensors: entry n - 1 of an env's row holds
+        {d_violation, d_wirelength, d_via, status} and the reward step() would publish if net n were its action now; nets that are not
+        candidates hold {0, 0, 0, -1} and -inf (an arg-max over a reward row is the greedy action; a done env has no candidate).
+        mask: optional int64 / uint64 [rows, legal_words] bitmasks, the candidates are legal & mask.  group: an env group (rows = its
+        slots, enqueued on `stream`, default the current stream); None: the whole batch."""
+        if group is None:
+            g, rows = -1, self.n_envs
+        else:
+            lo, hi = self.group_bounds(group)
+            g, rows = int(group), hi - lo
+        k = max(int(self.k_max), 1)
+        if out is None or reward_out is None:
+            with torch.cuda.stream(stream if stream is not None else torch.cuda.current_stream(self.device)):
+                out = torch.empty((rows, k, 4), dtype=torch.int32, device=self.device) if out is None else out
+                reward_out = torch.empty((rows, k), dtype=torch.float64, device=self.device) if reward_out is None else reward_out
+        if out.device != self.device or out.dtype != torch.int32 or not out.is_contiguous() or tuple(out.shape) != (rows, k, 4):
+            raise ValueError(f"out must be a contiguous int32 [{rows}, {k}, 4] tensor on the batch device")
+        if reward_out.device != self.device or reward_out.dtype != torch.float64 or not reward_out.is_contiguous() \
+                or tuple(reward_out.shape) != (rows, k):
+            raise ValueError(f"reward_out must be a contiguous float64 [{rows}, {k}] tensor on the batch device")
+        mp = None
+        if mask is not None:
+            if mask.device != self.device or mask.dtype not in (torch.int64, torch.uint64) or not mask.is_contiguous() \
+                    or tuple(mask.shape) != (rows, self.legal_words):
+                raise ValueError(f"mask must be a contiguous 64-bit [{rows}, {self.legal_words}] tensor on the batch device")
+            mp = C.c_void_p(mask.data_ptr())
+        with torch.cuda.device(self.device):
+            _lib.check(self.L.xr_batch_lookahead(self._h, g, mp, C.c_void_p(out.data_ptr()), k, C.c_void_p(reward_out.data_ptr()),
+                                                 self._stream_arg(stream)))
+        return out, reward_out
+
     def alloc_head(self) -> torch.Tensor:
         """[n_envs, 2*n_max] fp32 buffer for the compact-consumer step (planes 0..1 of every env)."""
         return torch.empty((self.n_envs, 2 * self.n_max), dtype=torch.float32, device=self.device)

@@ -154,6 +154,16 @@ struct xr_batch {
     DevBuf<uint32_t> group_queue;               // [XR_MAX_GROUPS][2][4]: two banks of queue counters per group, alternating per group step
     int group_bank[XR_MAX_GROUPS] = {};
     ObsValid group_valid[XR_MAX_GROUPS];        // per group: buffer (row 0 = the group's first slot) that holds its observation
+    // lookahead (xr_batch_lookahead): private memory of the callers that have used it — [0] the whole batch, [1 + g] env group g.  One pool =
+    // the rows of look_grid shadow slots (everything a router writes per env), the task list and two banks of {tasks listed, next task}
+    struct LookPool {
+        DevBuf<uint8_t> mem;
+        DevBuf<uint32_t> tasks, ctr;
+        int bank = 0;
+        XrBatchDev shadow{};
+        void release() { mem.release(); tasks.release(); ctr.release(); bank = 0; }
+    } look[1 + XR_MAX_GROUPS];
+    int look_grid = 0;                          // workgroups of the persistent lookahead launch the chip holds at once (0: not asked yet)
     XrBatchDev dev{};
     ~xr_batch() {
         if (ev_fork) (void)hipEventDestroy(ev_fork);
@@ -315,6 +325,8 @@ int32_t xr_batch_load_regions(xr_batch* b, const xr_region_desc* regs, int32_t n
     drop_obs_valid(b);
     b->n_cus = 0;
     b->route_slots = 0;
+    for (xr_batch::LookPool& lp : b->look) lp.release();         // shadow slots are sized for the regions they were allocated under
+    b->look_grid = 0;
     b->guide_csr.release(); b->guide_box.release(); b->guide_mask.release(); b->guide_mask_bytes = 0;        // guides belong to the regions they were loaded for
     memset(&b->dev, 0, sizeof(b->dev));
 
@@ -1623,6 +1635,99 @@ int32_t xr_batch_fetch_group(xr_batch* b, int32_t group, int32_t what, void* dst
         return fail(XR_ERR_RANGE, "xr_batch_fetch_group(%d): destination holds %zu bytes, the group's slice has %zu", what, dst_bytes, bytes);
     XR_HIP(hipSetDevice(b->cfg.device));
     XR_HIP(hipMemcpyAsync(dst_dev, src + (size_t)lo * row, bytes, hipMemcpyDefault, static_cast<hipStream_t>(stream)));
+    return XR_OK;
+}
+
+// ---- lookahead -------------------------------------------------------------------------------------------------------------------
+namespace {
+// The pool of one caller (whole batch / one env group), allocated on its first lookahead: look_grid shadow slots carved out of one
+// allocation (every row starts on a 16-byte boundary), a task list for every (slot, net) pair the batch can hold, two banks of counters.
+int32_t look_pool(xr_batch* b, xr_batch::LookPool& lp, hipStream_t st) {
+    if (lp.mem.p) return XR_OK;
+    const size_t G = (size_t)b->look_grid;
+    size_t off = 0;
+    auto carve = [&](size_t bytes) { const size_t o = off; off += (bytes + 15) & ~(size_t)15; return o; };
+    const size_t o_owner = carve(G * b->n_max * sizeof(int16_t)), o_path = carve(G * b->path_cap * sizeof(int32_t));
+    const size_t o_legal = carve(G * b->legal_words * sizeof(uint64_t)), o_hash = carve(G * sizeof(uint64_t));
+    const size_t o_reward = carve(G * sizeof(double)), o_steps = carve(G * sizeof(int64_t)), o_total = carve(sizeof(unsigned long long));
+    const size_t o_phase = carve(G * 8 * sizeof(long long)), o_rec = carve(G * sizeof(XrStepRecord));
+    const size_t o_cum = carve(G * 3 * sizeof(int32_t)), o_delta = carve(G * 3 * sizeof(int32_t));
+    const size_t o_nlegal = carve(G * sizeof(int32_t)), o_status = carve(G * sizeof(int32_t)), o_plen = carve(G * sizeof(int32_t));
+    const size_t o_sweeps = carve(G * sizeof(int32_t)), o_touched = carve(G * sizeof(int32_t)), o_region = carve(G * sizeof(int32_t));
+    const size_t o_replay = carve(G * sizeof(int32_t)), o_done = carve(G);
+    hipError_t e = lp.mem.alloc(off);
+    if (e == hipSuccess) e = lp.tasks.alloc((size_t)b->cfg.n_envs * std::max(1, b->k_max));
+    if (e == hipSuccess) e = lp.ctr.alloc(4);
+    if (e != hipSuccess) {
+        lp.release();
+        return fail(XR_ERR_NOMEM, "xr_batch_lookahead: hipMalloc of %zu bytes of shadow slots failed: %s", off, hipGetErrorString(e));
+    }
+    if (hipMemsetAsync(lp.ctr.p, 0, 4 * sizeof(uint32_t), st) != hipSuccess ||          // both banks start clean; every plan zeroes the other bank
+        hipMemsetAsync(lp.mem.p, 0, off, st) != hipSuccess) {
+        lp.release();
+        return fail(XR_ERR_HIP, "xr_batch_lookahead: clearing the shadow slots failed");
+    }
+    uint8_t* const m = lp.mem.p;
+    XrBatchDev& d = lp.shadow;
+    d = b->dev;
+    d.owner = reinterpret_cast<int16_t*>(m + o_owner); d.path = reinterpret_cast<int32_t*>(m + o_path);
+    d.legal = reinterpret_cast<uint64_t*>(m + o_legal); d.hash = reinterpret_cast<uint64_t*>(m + o_hash);
+    d.reward = reinterpret_cast<double*>(m + o_reward); d.env_steps = reinterpret_cast<int64_t*>(m + o_steps);
+    d.total_steps = reinterpret_cast<unsigned long long*>(m + o_total); d.phase_cycles = reinterpret_cast<long long*>(m + o_phase);
+    d.records = reinterpret_cast<XrStepRecord*>(m + o_rec);
+    d.cum = reinterpret_cast<int32_t*>(m + o_cum); d.delta = reinterpret_cast<int32_t*>(m + o_delta);
+    d.nlegal = reinterpret_cast<int32_t*>(m + o_nlegal); d.status = reinterpret_cast<int32_t*>(m + o_status);
+    d.path_len = reinterpret_cast<int32_t*>(m + o_plen); d.sweeps = reinterpret_cast<int32_t*>(m + o_sweeps);
+    d.touched = reinterpret_cast<int32_t*>(m + o_touched); d.env_region = reinterpret_cast<int32_t*>(m + o_region);
+    d.env_replay = reinterpret_cast<int32_t*>(m + o_replay); d.done = m + o_done;
+    return XR_OK;
+}
+}  // namespace
+
+int32_t xr_batch_lookahead(xr_batch* b, int32_t group, const uint64_t* cand_mask_dev, int32_t* out_dev, int32_t k_cap, double* reward_out_dev,
+                           void* stream) {
+    if (!b || !out_dev) return fail(XR_ERR_INVALID, "xr_batch_lookahead: null argument");
+    if (!b->loaded) return fail(XR_ERR_STATE, "xr_batch_lookahead: load regions first");
+    if (group < -1 || group >= b->n_groups) return fail(XR_ERR_INVALID, "xr_batch_lookahead: group %d outside -1..%d", group, b->n_groups - 1);
+    if (k_cap < b->k_max) return fail(XR_ERR_RANGE, "xr_batch_lookahead: k_cap %d < k_max %d", k_cap, b->k_max);
+    if (!b->lds_dist || b->cfg.stream_per_region)
+        return fail(XR_ERR_RANGE, "xr_batch_lookahead: not available for batches whose distance field lives in HBM scratch (regions too large for LDS, "
+                                  "force_scratch_field) or with stream_per_region");
+    const int lo = group < 0 ? 0 : b->group_bounds[group];
+    const int rows = group < 0 ? b->cfg.n_envs : b->group_bounds[group + 1] - lo;
+    if ((int64_t)b->cfg.n_envs * std::max(1, b->k_max) >= ((int64_t)1 << 31) || (int64_t)rows * k_cap >= ((int64_t)1 << 31))
+        return fail(XR_ERR_RANGE, "xr_batch_lookahead: n_envs x k_max (or rows x k_cap) does not fit 31 bits");
+    if (!xr_lookahead_occupancy || !xr_launch_lookahead_plan || !xr_launch_lookahead)
+        return fail(XR_ERR_STATE, "xr_batch_lookahead: lookahead kernels not linked");
+    XR_HIP(hipSetDevice(b->cfg.device));
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const XrRouteVariant v = route_variant(b);
+    if (b->look_grid == 0) {          // once per load: CUs x resident workgroups per CU of the persistent kernel, at most one per possible task
+        hipDeviceProp_t prop;
+        XR_HIP(hipGetDeviceProperties(&prop, b->cfg.device));
+        int per_cu = 0;
+        XR_HIP(xr_lookahead_occupancy(v, &per_cu));
+        const int64_t pairs = (int64_t)b->cfg.n_envs * std::max(1, b->k_max);
+        b->look_grid = (int)std::min<int64_t>((int64_t)std::max(1, per_cu) * prop.multiProcessorCount, pairs);
+    }
+    xr_batch::LookPool& lp = b->look[group + 1];
+    if (const int32_t rc = look_pool(b, lp, st)) return rc;
+    // the shadow view: the batch as it is configured NOW (guides may have been loaded since the pool was made), rows of the shadow slots
+    XrBatchDev sh = b->dev;
+    const XrBatchDev& p = lp.shadow;
+    sh.owner = p.owner; sh.path = p.path; sh.legal = p.legal; sh.hash = p.hash; sh.reward = p.reward; sh.env_steps = p.env_steps;
+    sh.total_steps = p.total_steps; sh.phase_cycles = p.phase_cycles; sh.records = p.records; sh.cum = p.cum; sh.delta = p.delta;
+    sh.nlegal = p.nlegal; sh.status = p.status; sh.path_len = p.path_len; sh.sweeps = p.sweeps; sh.touched = p.touched;
+    sh.env_region = p.env_region; sh.env_replay = p.env_replay; sh.done = p.done;
+    sh.auto_reset = 0; sh.net_meas = nullptr; sh.obs_out = nullptr; sh.obs_out_u8 = nullptr; sh.route_order = nullptr;
+    sh.n_envs = b->look_grid; sh.env_base = 0; sh.env_count = 0;
+    uint32_t* const ctr = lp.ctr.p + 2 * lp.bank;
+    uint32_t* const next_ctr = lp.ctr.p + 2 * (lp.bank ^ 1);
+    lp.bank ^= 1;
+    XR_HIP(xr_launch_lookahead_plan(&b->dev, lo, rows, cand_mask_dev, out_dev, reward_out_dev, k_cap, b->k_max, lp.tasks.p, ctr, next_ctr, st));
+    if (b->k_max < 1) return XR_OK;          // (no region has a net: the fill is the whole answer)
+    const int blocks = (int)std::min<int64_t>(b->look_grid, (int64_t)rows * b->k_max);
+    XR_HIP(xr_launch_lookahead(&b->dev, &sh, lo, lp.tasks.p, ctr, out_dev, reward_out_dev, k_cap, b->k_max, v, blocks, st));
     return XR_OK;
 }
 

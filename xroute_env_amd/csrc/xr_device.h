@@ -220,6 +220,13 @@ hipError_t xr_launch_obs_u8(const XrBatchDev* b, uint8_t* out, int64_t env_strid
 hipError_t xr_launch_unit_helpers(const XrBatchDev* b, int blocks, hipStream_t st);
 hipError_t xr_launch_netplanes_pairs(const XrBatchDev* b, const int32_t* pair_region, const int32_t* pair_net, int n_pairs, float* out, int64_t pair_stride,
                                      int vec4, hipStream_t st);
+// lookahead (xr_lookahead.h).  Weak: a build of the host side without them (tests/hostsan) links and loads, and xr_batch_lookahead answers
+// XR_ERR_STATE there after it has validated its arguments
+hipError_t xr_lookahead_occupancy(XrRouteVariant v, int* wg_per_cu) __attribute__((weak));
+hipError_t xr_launch_lookahead_plan(const XrBatchDev* b, int env_lo, int rows, const uint64_t* cand_mask, int32_t* out, double* reward_out, int k_cap,
+                                    int k_max, uint32_t* tasks, uint32_t* ctr, uint32_t* next_ctr, hipStream_t st) __attribute__((weak));
+hipError_t xr_launch_lookahead(const XrBatchDev* src, const XrBatchDev* shadow, int env_lo, const uint32_t* tasks, uint32_t* ctr, int32_t* out,
+                               double* reward_out, int k_cap, int k_max, XrRouteVariant v, int blocks, hipStream_t st) __attribute__((weak));
 hipError_t xr_launch_guide_masks(const XrBatchDev* b, uint8_t* masks, int k_max, hipStream_t st);
 hipError_t xr_launch_ingest_state(const XrBatchDev* b, const int16_t* owner_in, const uint64_t* legal_in, const int32_t* cum_in, hipStream_t st);
 hipError_t xr_launch_pack_state(const XrBatchDev* b, uint8_t* rows, int64_t row_bytes, int region_base, hipStream_t st);

@@ -11,6 +11,7 @@
 //   xr_plan_kernel + xr_step_queue_kernel   the step with its observation, default form (XR_OBS_QUEUE): one persistent
 //                         launch draining route tasks and net-plane units
 //   xr_netplane_kernel, xr_netplane_stream_kernel   the writer of the split form (XR_OBS_SPLIT)
+//   xr_lookahead_plan_kernel + xr_lookahead_kernel   (xr_lookahead.h) every candidate net of every env routed in a throw-away copy of its slot
 //   xr_random_action_kernel
 //
 // Integer / index work throughout: no MFMA.  What matters here is coalescing (every sweep is
@@ -2225,6 +2226,8 @@ __global__ void __launch_bounds__(256) xr_expand_state_kernel(XrBatchDev b, cons
     }
 }
 
+#include "xr_lookahead.h"
+
 // ------------------------------------------------------------------------------------------------
 // host-callable launchers (kept here so that only this TU needs the <<<>>> syntax)
 // ------------------------------------------------------------------------------------------------
@@ -2277,9 +2280,10 @@ hipError_t xr_launch_reset(const XrBatchDev* b, const uint8_t* mask, int rotate,
 
 hipError_t xr_route_set_max_lds(size_t bytes) {
     return xr_each_variant([&](auto L, auto Z) {
-        const void* fns[4] = {reinterpret_cast<const void*>(&xr_route_kernel<L.value, Z.value>), reinterpret_cast<const void*>(&xr_order_kernel<L.value, Z.value>),
+        const void* fns[5] = {reinterpret_cast<const void*>(&xr_route_kernel<L.value, Z.value>), reinterpret_cast<const void*>(&xr_order_kernel<L.value, Z.value>),
                               reinterpret_cast<const void*>(&xr_step_queue_kernel<L.value, Z.value>),
-                              reinterpret_cast<const void*>(&xr_step_queue_u8_kernel<L.value, Z.value>)};
+                              reinterpret_cast<const void*>(&xr_step_queue_u8_kernel<L.value, Z.value>),
+                              reinterpret_cast<const void*>(&xr_lookahead_kernel<L.value, Z.value>)};
         for (const void* fn : fns) {
             const hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
             if (e != hipSuccess) return e;
@@ -2317,6 +2321,28 @@ hipError_t xr_launch_step_queue(const XrBatchDev* b, const int32_t* actions, XrR
     xr_with_variant(v.lds_dist, v.zch, [&](auto L, auto Z) {
         if (b->obs_out_u8) hipLaunchKernelGGL((xr_step_queue_u8_kernel<L.value, Z.value>), g, t, v.lds_bytes, st, *b, actions);
         else hipLaunchKernelGGL((xr_step_queue_kernel<L.value, Z.value>), g, t, v.lds_bytes, st, *b, actions);
+    });
+    return hipGetLastError();
+}
+
+// lookahead (xr_lookahead.h): resident workgroups per CU of its persistent kernel; the planning pass; the persistent launch
+hipError_t xr_lookahead_occupancy(XrRouteVariant v, int* wg_per_cu) {
+    const void* fn = xr_with_variant(v.lds_dist, v.zch, [](auto L, auto Z) { return reinterpret_cast<const void*>(&xr_lookahead_kernel<L.value, Z.value>); });
+    return hipOccupancyMaxActiveBlocksPerMultiprocessor(wg_per_cu, fn, v.threads, v.lds_bytes);
+}
+
+hipError_t xr_launch_lookahead_plan(const XrBatchDev* b, int env_lo, int rows, const uint64_t* cand_mask, int32_t* out, double* reward_out, int k_cap,
+                                    int k_max, uint32_t* tasks, uint32_t* ctr, uint32_t* next_ctr, hipStream_t st) {
+    hipLaunchKernelGGL(xr_lookahead_plan_kernel, dim3((rows + 3) / 4), dim3(256), 0, st, *b, env_lo, rows, cand_mask, out, reward_out, k_cap, k_max, tasks, ctr,
+                       next_ctr);
+    return hipGetLastError();
+}
+
+hipError_t xr_launch_lookahead(const XrBatchDev* src, const XrBatchDev* shadow, int env_lo, const uint32_t* tasks, uint32_t* ctr, int32_t* out,
+                               double* reward_out, int k_cap, int k_max, XrRouteVariant v, int blocks, hipStream_t st) {
+    const dim3 g(blocks), t(v.threads);
+    xr_with_variant(v.lds_dist, v.zch, [&](auto L, auto Z) {
+        hipLaunchKernelGGL((xr_lookahead_kernel<L.value, Z.value>), g, t, v.lds_bytes, st, *src, *shadow, env_lo, tasks, ctr, out, reward_out, k_cap, k_max);
     });
     return hipGetLastError();
 }

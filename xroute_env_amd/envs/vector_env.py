@@ -119,6 +119,45 @@ class XRouteVectorEnv:
     def random_actions(self, seed: int, out: Optional[torch.Tensor] = None):
         return self.batch.random_actions(seed, out)
 
+    # ---- lookahead: every candidate net priced from the current state, the env untouched ------------------------------------------
+    def lookahead(self, group: Optional[int] = None):
+        """(delta_status int32 [rows, k_max, 4], reward float64 [rows, k_max]) of RegionBatch.lookahead: what step() would publish for
+        every net an env may pick now (-1 status / -inf reward where a net is no candidate).  group None: the whole batch, after every
+        group's outstanding work.  A group: on that group's stream, after the current stream and the group's last step; the group's
+        event then covers it, so step_wait(group) / poll(group) order a consumer after the result."""
+        if group is None:
+            self._join_groups()
+            return self.batch.lookahead()
+        (g,) = self._groups_of(group)
+        s = self.group_streams[g]
+        s.wait_stream(torch.cuda.current_stream(self.device))
+        with torch.cuda.stream(s):
+            res = self.batch.lookahead(group=g, stream=s)
+            self.group_events[g].record(s)
+        return res
+
+    def greedy_actions(self, group: Optional[int] = None) -> torch.Tensor:
+        """int32 actions [rows]: per env the net with the highest lookahead reward (the cheapest next route), the first maximum in
+        ascending net id; 0 for a done env, like random_actions."""
+        if group is None:
+            _, reward = self.lookahead()
+            return self._argmax_first(reward)
+        (g,) = self._groups_of(group)
+        _, reward = self.lookahead(g)
+        s = self.group_streams[g]
+        with torch.cuda.stream(s):
+            act = self._argmax_first(reward)
+            self.group_events[g].record(s)
+        return act
+
+    @staticmethod
+    def _argmax_first(reward: torch.Tensor) -> torch.Tensor:
+        best = reward.max(dim=1, keepdim=True).values
+        k = reward.shape[1]
+        idx = torch.arange(k, device=reward.device).expand_as(reward)
+        first = torch.where(reward == best, idx, torch.full_like(idx, k)).min(dim=1).values      # (argmax does not promise the first maximum)
+        return torch.where(best.squeeze(1) == float("-inf"), torch.zeros_like(first), first + 1).to(torch.int32)
+
     # ---- independent stepping of env groups -----------------------------------------------------------------------------
     def _groups_of(self, group):
         if not self.n_groups:
