@@ -3,8 +3,7 @@ nets-left distribution.  python tools/ab_router.py [envs=4096] ; variants = (lib
 import os, subprocess, sys, json
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 B = sys.argv[1] if len(sys.argv) > 1 else "4096"
-variants = [("libxroute_hip.so", 0, 0), ("libxroute_hip_noastar.so", 0, 0), ("libxroute_hip_nochain.so", 0, 0), ("libxroute_hip.so", 1, 0),
-            ("libxroute_hip.so", 0, 2), ("libxroute_hip.so", 0, 8)]
+variants = [("libxroute_hip.so", 0, 0), ("libxroute_hip.so", 1, 0), ("libxroute_hip.so", 0, 2), ("libxroute_hip.so", 0, 8)]
 res = {}
 for rep in range(2):
     for lib, router, mult in variants:

@@ -158,9 +158,6 @@ __device__ __forceinline__ void xt_load_half(const float* __restrict__ cell, con
 // variant its epilogue's registers on top spill all 72 weights (stage 79 k), and with 768 threads (no spill) the epilogue's align2 weights can no longer be asked
 // for ahead of a slice's matrix instructions (31 k)
 template <int N> struct xt_ic { static constexpr int value = N; };
-#ifndef XT_AL1_TC
-#define XT_AL1_TC 4
-#endif
 template <bool NET, int MM> constexpr bool xt_reuse_b() { return NET && MM != 0; }
 template <bool NET, int MM, int BT> constexpr bool xt_reuse_b2() { return MM != 0 && (NET || BT <= 768); }      // the second stage: see the launcher's thread count
 __device__ __forceinline__ xt_f4 xt_mm3b(const xt_u4 ah, const xt_u4 al, const xt_u4 bh, const xt_u4 bl, xt_f4 acc) {
@@ -540,11 +537,7 @@ __global__ void __launch_bounds__(BT) xr_ob_tower_kernel(const float* __restrict
                         }
                         int* o = accB + ((dz * oh + th) * ow + tw) * 7;
 #pragma unroll
-#ifdef XN_PLAIN_RMW      /* timing experiment only (racy): what the scatter costs without the atomics */
-                        for (int co = 0; co < 7; co++) o[co] += __float2int_rn(acc[co >> 1][co & 1] * scale);
-#else
                         for (int co = 0; co < 7; co++) atomicAdd(o + co, __float2int_rn(acc[co >> 1][co & 1] * scale));
-#endif
                     }
                 }
             }
@@ -693,7 +686,7 @@ __global__ void __launch_bounds__(BT) xr_ob_tower_kernel(const float* __restrict
                 if (ok[j] && w < ow) xt_store_half(bufB + ((dz * oh + hz) * ow + w) * 7, co0 >> 2, acc[j][0], acc[j][1], acc[j][2], acc[j][3]);
             }
         };
-        constexpr int TC = XT_AL1_TC;
+        constexpr int TC = 4;
         for (int t0 = wv; t0 < ntile; t0 += nw * TC) {
             const int nt = min(TC, (ntile - t0 + nw - 1) / nw);                         // (wave-uniform)
             if (nt >= 6) al1_round(xt_ic<(TC >= 6 ? 6 : 1)>{}, t0);

@@ -40,41 +40,11 @@
 // Two placements: LDS_FIELD (field + bitmasks in LDS: 38.2 KB at 24x40x9, 4 workgroups per CU) and the HBM-scratch form
 // for large regions (see xr_dial_route_env_big below).
 #pragma once
-// XR-Maze v2's rip-up-and-reroute loop is computed as ONE attempt at the last attempt's penalty (proof: xr_dial3.h);
-// -DXR3_V2_ALL_ATTEMPTS keeps round 4's attempt-by-attempt form (same results)
-#ifdef XR3_V2_ALL_ATTEMPTS
-#define XR3_ALL_ATTEMPTS true
-#else
-#define XR3_ALL_ATTEMPTS false
-#endif
-
 
 #define XR_DIAL_INF 0xFFFFFFFFu
-#ifndef XR_DIAL_ASTAR
-#define XR_DIAL_ASTAR 1          // LDS form: bucket keys f = d + h (0: plain Dijkstra order, keys = d) — A/B switch
-#endif
-#if defined(XR_PHASE_TIMING) && defined(XR_PROBE_SETUP)
-#define XR_MARK(n) do { if ((n) == XR_PROBE_SETUP && threadIdx.x == XR_TIMING_TID) _ph[7] += clock64() - _t; } while (0)
-#else
-#define XR_MARK(n) do {} while (0)
-#endif
-#ifndef XR_BIG_SPEC_FLAGS
-#define XR_BIG_SPEC_FLAGS 1     // HBM-scratch form: load node_net / owner of a neighbour together with its field word
-#endif
-#ifndef XR_POCKET_MASK
-#define XR_POCKET_MASK 1        // LDS form: pocket flood with a bitmask as its visited set
-#endif
-#ifndef XR_DIAL_QUAD
-#define XR_DIAL_QUAD 1         // LDS form: the nodes of a bucket are expanded by quads of lanes (one lane per direction)
-#endif
-#ifndef XR_SCAN_UNROLL
-#define XR_SCAN_UNROLL 2      // open nodes of a mask word classified per loop iteration
-#endif
+constexpr int XR_SCAN_UNROLL = 2;   // open nodes of a mask word classified per loop iteration
 #define XR_HB_MAX 6          // pin boxes of the search heuristic (HBM-scratch form; xr_dial3.h)
 #define XR_QUAD_POOL 128       // nodes of a bucket queued per workgroup for the quads (split evenly over the waves); no room: next round
-#ifndef XR_DIAL_CHAIN
-#define XR_DIAL_CHAIN 1
-#endif
 
 // n / d and n % d with magic = floor(2^32 / d) (d >= 2) or 0xFFFFFFFF (d == 1); exact for n < 2^30
 __device__ __forceinline__ void xr_divmod(uint32_t n, uint32_t d, uint32_t magic, uint32_t& q, uint32_t& r) {
@@ -199,9 +169,7 @@ __device__ __forceinline__ void xr_step_epilogue(const XrBatchDev& b, const int 
 // searches skip it.  Same results by construction (the pocket's boundary is static), nothing explored for nothing.
 // ------------------------------------------------------------------------------------------------
 #define XR_POCKET_CAP 12        // storage per wave (also the quads' node queue of the LDS form: do not shrink)
-#ifndef XR_POCKET_BUDGET_LDS
-#define XR_POCKET_BUDGET_LDS 12     // nodes a flood may visit before the pocket counts as open (<= XR_POCKET_CAP), LDS form
-#endif
+constexpr int XR_POCKET_BUDGET_LDS = 12;   // nodes a flood may visit before the pocket counts as open (<= XR_POCKET_CAP), LDS form
 #define XR_POCKET_BUDGET_BIG 12     // ... HBM-scratch form (BASELINE config 5 has pockets of more than 4 nodes)
 template <class ApT, class BlockedFn>
 __device__ __forceinline__ void xr_mark_isolated_pins(int nap, const ApT* ap_f_of, const short* s_ap_pin, unsigned char* s_ap_conn,
@@ -331,7 +299,7 @@ __device__ __forceinline__ void xr_dial_route_env(const XrBatchDev& b, const int
     __shared__ int s_hb[6];                                   // bounding box of the unconnected targets: x, y (coordinates x4), z
     __shared__ int s_remaining, s_target_i, s_first_pin, s_npins, s_niso, s_src_iso;
     __shared__ int s_pocket[4][XR_POCKET_CAP + 8];
-    __shared__ int s_gb[4], s_retry, s_ngb;                   // XR-Maze v2: bounding box of the net's access points (track indices), rip-up decision
+    __shared__ int s_gb[4], s_ngb;                            // XR-Maze v2: bounding box of the net's access points (track indices)
     __shared__ int4 s_gbx[XR_GUIDE_MAX_BOXES];                // ... and its guide (xr_guide_load)
     __shared__ int s_abort;                                   // a hop loop hit the round cap
 
@@ -373,7 +341,7 @@ __device__ __forceinline__ void xr_dial_route_env(const XrBatchDev& b, const int
 
     // ---- grid build: field word of every node for THIS net.  node_net / owner rows are padded to multiples of 8
     // elements (16-byte loads); pad slots and blockages become 0.  Loads of four chunks are issued before the first use.
-    // (a lambda: XR-Maze v2 rebuilds the field for every rip-up-and-reroute attempt)
+    // (called once; written out in place of the lambda it compiles to different code in ten kernels, so it stays one: LAB_NOTES.md §8)
     auto build_field = [&]() {
     {
         const int nchunk = (N + 7) >> 3;
@@ -409,24 +377,18 @@ __device__ __forceinline__ void xr_dial_route_env(const XrBatchDev& b, const int
     }
         for (int i = tid; i < mw; i += nthr) { s_open[i] = 0; s_defer[i] = 0; s_claim[i] = 0; s_wmin[i] = XR_DIAL_INF; }
     };
-    XR_MARK(1);
     build_field();
-    XR_MARK(2);
     if (tid <= X + 1) s_xc[tid] = my_xc;
     if (tid <= Y + 1) s_yc[tid] = my_yc;
     for (int i = tid + nthr; i <= X + 1; i += nthr)
         s_xc[i] = (uint32_t)(b.coords[R.xs_off + min(i - 1, X - 1)] - b.coords[R.xs_off]) << 2;
     for (int i = tid + nthr; i <= Y + 1; i += nthr)
         s_yc[i] = (uint32_t)(b.coords[R.ys_off + min(i - 1, Y - 1)] - b.coords[R.ys_off]) << 2;
-    auto el4x = [&](int i) { return s_xc[i + 1] - s_xc[i]; };
-    auto el4y = [&](int i) { return s_yc[i + 1] - s_yc[i]; };
-    (void)el4x; (void)el4y;
     if (tid == 0) {
         s_first_pin = 0x7FFFFFFF; s_npins = 0; s_niso = 0; s_src_iso = 0; s_abort = 0;
         s_gb[0] = 0x7FFFFFFF; s_gb[1] = -1; s_gb[2] = 0x7FFFFFFF; s_gb[3] = -1;
     }
     __syncthreads();
-    XR_MARK(3);
     for (int i = tid; i < nap; i += nthr) {
         const int pin = i < nthr ? my_ap_pin : (int)b.ap_pin[R.ap_off + ap_lo + i];
         const int apf = i < nthr ? my_ap_f : b.ap_node[R.ap_off + ap_lo + i];
@@ -459,9 +421,7 @@ __device__ __forceinline__ void xr_dial_route_env(const XrBatchDev& b, const int
         s_ap_conn[i] = cflag;
     }
     __syncthreads();
-    XR_MARK(4);
     // pins in closed pockets are never searched for (see xr_mark_isolated_pins)
-#if XR_POCKET_MASK
     // LDS form: the flood keeps its visited set in a node bitmask that is still all-zero at this point (wave 0: defer, wave 1:
     // claim) — test-and-set by one LDS atomic per candidate, all candidates of a pass at once — instead of comparing every
     // candidate with every node visited so far; the bits are cleared again afterwards.  Same pockets, same verdicts.
@@ -542,25 +502,19 @@ __device__ __forceinline__ void xr_dial_route_env(const XrBatchDev& b, const int
             }
         }
     }
-#else
-    xr_mark_isolated_pins(nap, s_ap_f, s_ap_pin, s_ap_conn, X, Y, Z, ldir, R.magic_yz, R.magic_z,
-                          [&](int f) { return field[f] == XR_W_BLOCK; }, s_pocket, &s_niso, &s_src_iso, s_first_pin, XR_POCKET_BUDGET_LDS);
-#endif
     __syncthreads();
-    XR_MARK(5);
     for (int i = tid; i < nap; i += nthr) s_ap_conn[i] &= 0x7F;
     const int n_isolated = s_src_iso ? s_npins - 1 : s_niso;       // unreachable pins known up front
     if (tid == 0) s_remaining = s_npins - 1 - n_isolated;
     XR_LAP(0);
 
     const uint32_t via4 = (uint32_t)b.via_cost << 2;
-    uint32_t pen4 = (uint32_t)b.pen_cost << 2;              // (XR-Maze v2: doubled by every rip-up-and-reroute attempt)
+    uint32_t pen4 = (uint32_t)b.pen_cost << 2;              // (XR-Maze v2: shifted to the last attempt's penalty below)
     const uint32_t delta = R.w_min * (uint32_t)b.dial_mult;
     const uint32_t uYZ = (uint32_t)YZ, uZ = (uint32_t)Z;
-    int d_vio = 0, d_wl = 0, d_via = 0, plen = 0, status = XR_ENV_OK, d_held = 0;   // thread 0 only
+    int d_vio = 0, d_wl = 0, d_via = 0, plen = 0, status = XR_ENV_OK;   // thread 0 only
     int nrounds = 0;
-    const uint64_t h0 = (tid == 0) ? b.hash[e] : 0;
-    uint64_t h = h0;
+    uint64_t h = (tid == 0) ? b.hash[e] : 0;
     int32_t* __restrict__ path = b.path + (int64_t)e * b.path_cap;
     // XR-Maze v2, neutral by default.  Guide: entering a node outside the net's guide box costs guide_cost.
     const uint32_t guide4 = V2 ? (uint32_t)b.guide_cost << 2 : 0u;
@@ -578,16 +532,9 @@ __device__ __forceinline__ void xr_dial_route_env(const XrBatchDev& b, const int
         if (!V2) return 0u;
         return (guide4 != 0u && !xr_guide_has(s_gbx, ngb, gb0, x, y, z)) ? guide4 : 0u;
     };
-    // Rip-up and reroute: claims of an attempt are tentative (owner = -a) until the attempt stands
-    const int16_t claim_val = (int16_t)(XR3_ALL_ATTEMPTS && V2 && b.maze_end_iter > 1 ? -a : a);      // (one attempt: its claims are final)
-#ifdef XR3_V2_ALL_ATTEMPTS
-    int attempt = 0;
-#else           // the rip-up-and-reroute loop has one possible outcome: the last attempt's route (xr_dial3.h)
-    int attempt = V2 ? max(b.maze_end_iter, 1) - 1 : 0;
-    if (V2) pen4 <<= attempt;
-#endif
+    // the rip-up-and-reroute loop has one possible outcome: the last attempt's route (xr_dial3.h)
+    if (V2) pen4 <<= max(b.maze_end_iter, 1) - 1;
 
-    for (;;) {                                              // attempts (exactly one unless maze_end_iter > 1)
     for (;;) {
         // ---- new search: sources are open with distance 0; deferred nodes are looked at again ------------
         if (tid == 0) {
@@ -616,13 +563,10 @@ __device__ __forceinline__ void xr_dial_route_env(const XrBatchDev& b, const int
         const int hb0 = s_hb[0], hb1 = s_hb[1], hb2 = s_hb[2], hb3 = s_hb[3], hb4 = s_hb[4], hb5 = s_hb[5];
         // h(v): distance to that box — coordinate differences + one via cost per layer (a consistent lower bound)
         auto heur_c = [&](int xc, int yc, int z) -> uint32_t {                 // (from coordinates x4)
-            if (!XR_DIAL_ASTAR) return 0u;
             const int hx = max(0, max(hb0 - xc, xc - hb1)), hy = max(0, max(hb2 - yc, yc - hb3));
             const int hz = max(0, max(hb4 - z, z - hb5));
             return ((uint32_t)(hx + hy) >> 2) + (uint32_t)hz * (uint32_t)b.via_cost;
         };
-        auto heur = [&](int x, int y, int z) -> uint32_t { return heur_c((int)s_xc[x + 1], (int)s_yc[y + 1], z); };
-        (void)heur;
         int cur = 0;
         // Bounded: a search takes a few tens of rounds (BASELINE configs: <= 43); round_cap = 1024 + N is far beyond any legal
         // region (a maze whose only path visits every node needs ~N/4).  Past it the router gives up on this net
@@ -640,9 +584,6 @@ __device__ __forceinline__ void xr_dial_route_env(const XrBatchDev& b, const int
             // (by the threads at the END of the workgroup: the first wave carries the words beyond one per thread)
             for (int i = nthr - 1 - tid; i < nap; i += nthr)
                 if (!s_ap_conn[i]) { const uint32_t w = field[s_ap_f[i]]; if (w < XR_W_UNREACHED) atomicMin(&s_bst[nx1], w >> 2); }
-            // A lane scans word wi and — where the mask has more words than the workgroup has threads — word wi + nthr in
-            // the SAME pass (one 64-bit bit set), so that no wave runs the body twice per round.
-#if XR_DIAL_QUAD
             // A lane scans word wi and — where the mask has more words than the workgroup has threads — word wi + nthr in
             // the SAME pass (one 64-bit bit set).  The nodes of this bucket are then expanded by QUADS of lanes, one lane per
             // direction: a hop of the run-ahead chain is one neighbour's worth of instructions instead of four (a route is
@@ -748,9 +689,6 @@ __device__ __forceinline__ void xr_dial_route_env(const XrBatchDev& b, const int
                         }
                         qh += __popcll(idle_g);
                         if (__ballot(gf >= 0) == 0ULL) break;                                            // uniform
-#ifdef XR_COUNT_HOPS
-                        if (tid == XR_TIMING_TID) _ph[7] += 1;          // (probe: hop iterations of this wave instead of rounds)
-#endif
                         // ---- one hop of every active quad.  All LDS reads are issued together (addresses made safe instead of
                         // guarded), then pure ALU, then the one atomic: two LDS round trips per hop
                         const bool act = gf >= 0;
@@ -779,7 +717,7 @@ __device__ __forceinline__ void xr_dial_route_env(const XrBatchDev& b, const int
                         if (go && !refused) {
                             const uint32_t old = atomicMin(&field[nf], cw);
                             lowered = cw < old;
-                            chain_cand = lowered && XR_DIAL_CHAIN && key < hi;
+                            chain_cand = lowered && key < hi;
                         }
                         const uint32_t c4 = (uint32_t)(__ballot(chain_cand) >> qbase) & 15u;
                         const uint32_t r4 = (uint32_t)(__ballot(refused) >> qbase) & 15u;
@@ -804,132 +742,11 @@ __device__ __forceinline__ void xr_dial_route_env(const XrBatchDev& b, const int
                 }
                 XR_LAP(2);
             }
-#else
-            for (int wi = tid; wi < mw; wi += 2 * nthr) {
-                const int wi2 = wi + nthr;
-                const bool has2 = wi2 < mw;
-                uint32_t wmA = s_wmin[wi], wmB = has2 ? s_wmin[wi2] : XR_DIAL_INF;
-                const bool actA = wmA < hi, actB = wmB < hi;
-                if (actA || actB) {
-                    // the word (probably) holds a node of this bucket: take it.  Order matters: reset the cached minimum,
-                    // THEN take the bits, THEN read distances — a concurrent insertion is either seen here or survives
-                    uint32_t bA = 0, bB = 0;
-                    if (actA) { s_wmin[wi] = XR_DIAL_INF; bA = atomicExch(&s_open[wi], 0u); }
-                    if (actB) { s_wmin[wi2] = XR_DIAL_INF; bB = atomicExch(&s_open[wi2], 0u); }
-                    unsigned long long bits = (unsigned long long)bA | ((unsigned long long)bB << 32);
-                    unsigned long long keep = 0, expd = 0;
-                    uint32_t kminA = XR_DIAL_INF, kminB = XR_DIAL_INF;
-                    while (bits) {                                    // four distance loads in flight at a time
-                        int q[4];
-                        uint32_t w[4];
-#pragma unroll
-                        for (int j = 0; j < 4; j++) {
-                            q[j] = bits ? __ffsll((long long)bits) - 1 : -1;
-                            bits &= bits - 1;                        // (0 stays 0)
-                        }
-                        int fq[4];
-#pragma unroll
-                        for (int j = 0; j < 4; j++) fq[j] = (q[j] & 31) * mw + (q[j] < 32 ? wi : wi2);
-#pragma unroll
-                        for (int j = 0; j < 4; j++) w[j] = q[j] >= 0 ? field[fq[j]] : XR_DIAL_INF;
-#pragma unroll
-                        for (int j = 0; j < 4; j++) {
-                            if (q[j] < 0) continue;
-                            uint32_t cx = 0, cr, cy = 0, cz = 0;
-                            if (XR_DIAL_ASTAR) {
-                                xr_divmod((uint32_t)fq[j], uYZ, R.magic_yz, cx, cr);
-                                xr_divmod(cr, uZ, R.magic_z, cy, cz);
-                            }
-                            const uint32_t key = (w[j] >> 2) + heur((int)cx, (int)cy, (int)cz);
-                            if (key >= hi) {
-                                keep |= 1ULL << q[j];
-                                if (q[j] < 32) kminA = key < kminA ? key : kminA; else kminB = key < kminB ? key : kminB;
-                            } else expd |= 1ULL << q[j];
-                        }
-                    }
-                    if ((uint32_t)keep) { atomicOr(&s_open[wi], (uint32_t)keep); atomicMin(&s_wmin[wi], kminA); }
-                    if ((uint32_t)(keep >> 32)) { atomicOr(&s_open[wi2], (uint32_t)(keep >> 32)); atomicMin(&s_wmin[wi2], kminB); }
-                    if (actA) wmA = kminA;
-                    if (actB) wmB = kminB;
-                    XR_LAP(1);
-                    while (expd) {
-                        const int qb = __ffsll((long long)expd) - 1;
-                        expd &= expd - 1;
-                        const int wsel = qb < 32 ? wi : wi2;
-                        uint32_t f = (uint32_t)((qb & 31) * mw + wsel);
-                        // Run-ahead: a neighbour lowered INTO the current bucket is expanded at once by the same lane (one
-                        // successor per node, the others take the open mask), so a distance travels a straight run of
-                        // in-bucket nodes within ONE round instead of one round per hop.
-                        for (;;) {
-                        const uint32_t d4 = field[f] & ~3u;
-                        // ---- expand f: planar neighbours along the layer's preferred direction + the two vias
-                        uint32_t x, r, y, z;
-                        xr_divmod(f, uYZ, R.magic_yz, x, r);
-                        xr_divmod(r, uZ, R.magic_z, y, z);
-                        const bool vert = (ldir >> z) & 1u;
-                        int nf[4];
-                        uint32_t len4[4], wn[4], cw[4], old[4];
-                        nf[0] = vert ? ((int)y + 1 < Y ? (int)f + Z : -1) : ((int)x + 1 < X ? (int)f + YZ : -1);
-                        len4[0] = vert ? el4y(y + 1) : el4x(x + 1);
-                        nf[1] = vert ? (y > 0 ? (int)f - Z : -1) : (x > 0 ? (int)f - YZ : -1);
-                        len4[1] = vert ? el4y(y) : el4x(x);
-                        nf[2] = ((int)z + 1 < Z) ? (int)f + 1 : -1; len4[2] = via4;
-                        nf[3] = (z > 0) ? (int)f - 1 : -1;          len4[3] = via4;
-#pragma unroll
-                        for (int k = 0; k < 4; k++) wn[k] = nf[k] >= 0 ? field[nf[k]] : XR_W_BLOCK;
-                        bool refused = false;
-                        uint32_t key[4], gcost[4];
-                        {   // h of the four neighbours (coordinates differ from f's in one component)
-                            const int ix = (int)x, iy = (int)y, iz = (int)z;
-                            gcost[0] = vert ? guide_of(ix, iy + 1, iz) : guide_of(ix + 1, iy, iz);
-                            gcost[1] = vert ? guide_of(ix, iy - 1, iz) : guide_of(ix - 1, iy, iz);
-                            gcost[2] = guide_of(ix, iy, iz + 1); gcost[3] = guide_of(ix, iy, iz - 1);
-                            key[0] = vert ? heur(ix, min(iy + 1, Y - 1), iz) : heur(min(ix + 1, X - 1), iy, iz);
-                            key[1] = vert ? heur(ix, max(iy - 1, 0), iz) : heur(max(ix - 1, 0), iy, iz);
-                            key[2] = heur(ix, iy, min(iz + 1, Z - 1));
-                            key[3] = heur(ix, iy, max(iz - 1, 0));
-                        }
-#pragma unroll
-                        for (int k = 0; k < 4; k++) {
-                            const uint32_t cand4 = d4 + len4[k] + ((wn[k] & 2u) ? pen4 : 0u) + gcost[k];
-                            cw[k] = cand4 | (wn[k] & 3u);
-                            key[k] += cand4 >> 2;                                 // f = d + h
-                            // blockage, a distance that does not exist (>= XR_DIST_CAP, spec), or no improvement: nothing to do
-                            bool go = wn[k] != XR_W_BLOCK && cand4 < XR_W_USABLE_END && cw[k] < wn[k];
-                            if (go && key[k] > best) { refused = true; go = false; }             // bound pruning (on f)
-                            if (!go) cw[k] = XR_DIAL_INF;
-                        }
-                        // the four atomics are issued back to back; their results are looked at afterwards
-#pragma unroll
-                        for (int k = 0; k < 4; k++) old[k] = cw[k] != XR_DIAL_INF ? atomicMin(&field[nf[k]], cw[k]) : 0u;
-                        int next_f = -1;
-#pragma unroll
-                        for (int k = 0; k < 4; k++) {
-                            if (cw[k] < old[k]) {                      // lowered
-                                if (XR_DIAL_CHAIN && next_f < 0 && key[k] < hi) { next_f = nf[k]; continue; }
-                                uint32_t oq, orr;                      // the neighbour becomes open
-                                xr_divmod((uint32_t)nf[k], umw, magic_mw, oq, orr);
-                                atomicOr(&s_open[orr], 1u << oq);
-                                atomicMin(&s_wmin[orr], key[k]);
-                                lmin = key[k] < lmin ? key[k] : lmin;
-                            }
-                        }
-                        if (refused) xr_mask_or(s_defer, f, umw, magic_mw);
-                        if (next_f < 0) break;
-                        f = (uint32_t)next_f;
-                        }
-                    }
-                    XR_LAP(2);
-                }
-                lmin = wmA < lmin ? wmA : lmin;
-                lmin = wmB < lmin ? wmB : lmin;
-            }
-#endif
             XR_LAP(1);
             lmin = xr_wave_min_u32(lmin);
             if ((tid & 63) == 0 && lmin != XR_DIAL_INF) atomicMin(&s_min[nx1], lmin);
             nrounds++;
-#if defined(XR_PHASE_TIMING) && !defined(XR_COUNT_HOPS) && !defined(XR_PROBE_SETUP)
+#ifdef XR_PHASE_TIMING
             if (tid == XR_TIMING_TID) _ph[7] += 1;
 #endif
             __syncthreads();
@@ -1002,7 +819,7 @@ __device__ __forceinline__ void xr_dial_route_env(const XrBatchDev& b, const int
                 auto claim_node = [&](int node, uint32_t w, int src, uint32_t pl4) {     // thread 0: node joins the path, left through `src`
                     uint32_t cq, cr;
                     xr_divmod((uint32_t)node, umw, magic_mw, cq, cr);
-                    if (w & 2u) { d_vio += 1; d_held += 1; }
+                    if (w & 2u) d_vio += 1;
                     atomicOr(&s_claim[cr], 1u << cq);
                     if (plen < b.path_cap) path[plen] = node;
                     plen++;
@@ -1054,7 +871,7 @@ __device__ __forceinline__ void xr_dial_route_env(const XrBatchDev& b, const int
                 } else if (tid == 0) {
                     // terminal node of the component: claimed (and recorded) only if nobody holds it yet
                     if (owner[v] == 0) {
-                        owner[v] = claim_val;
+                        owner[v] = (int16_t)a;
                         if (plen < b.path_cap) path[plen] = v;
                         plen++;
                         fnv_mix(h, (uint32_t)v);
@@ -1084,7 +901,7 @@ __device__ __forceinline__ void xr_dial_route_env(const XrBatchDev& b, const int
                             field[f] &= 3u;
                             // claim the path node if nobody holds it (by many threads at once, instead of one dependent
                             // HBM load per node inside the serial back-trace)
-                            if (owner[f] == 0) owner[f] = claim_val;
+                            if (owner[f] == 0) owner[f] = (int16_t)a;
                         }
                     }
                 }
@@ -1092,29 +909,6 @@ __device__ __forceinline__ void xr_dial_route_env(const XrBatchDev& b, const int
         }
         XR_LAP(4);
         // (the barrier at the top of the loop orders these writes before the next search / the exit test)
-    }
-    if (!XR3_ALL_ATTEMPTS || !V2 || b.maze_end_iter <= 1) break;
-    // ---- XR-Maze v2: does the attempt stand?  Its path uses a node held by another net and attempts are left: rip it up ----
-    if (tid == 0) s_retry = (d_held > 0 && attempt + 1 < b.maze_end_iter) ? 1 : 0;
-    __syncthreads();
-    const bool retry = s_retry != 0;
-    for (int f = tid; f < N; f += nthr)                       // tentative claims: accepted (-a -> a) or undone (-a -> 0)
-        if (owner[f] == (int16_t)-a) owner[f] = retry ? (int16_t)0 : (int16_t)a;
-    if (!retry) break;
-    attempt++;
-    pen4 = ((uint32_t)b.pen_cost << 2) << attempt;
-    if (tid == 0) { d_vio = 0; d_wl = 0; d_via = 0; plen = 0; d_held = 0; status = XR_ENV_OK; h = h0; }
-    __syncthreads();                                          // the owner grid is clean again before the field is rebuilt
-    build_field();
-    __syncthreads();
-    for (int i = tid; i < nap; i += nthr) {
-        const bool iso = s_ap_conn[i] == 2;
-        const bool first = s_ap_pin[i] == (short)s_first_pin;
-        s_ap_conn[i] = iso ? 2 : (first ? 1 : 0);
-        if (first && !iso) make_source(s_ap_f[i]);
-    }
-    if (tid == 0) s_remaining = s_npins - 1 - n_isolated;
-    // (the barrier at the top of the search loop orders all of this)
     }
 
     if (tid == 0) {
@@ -1170,7 +964,7 @@ __device__ __forceinline__ void xr_dial_route_env_big(const XrBatchDev& b, const
     __shared__ int s_remaining, s_target_i, s_first_pin, s_npins, s_niso, s_src_iso;
     __shared__ int s_pocket[4][XR_POCKET_CAP + 8];
     __shared__ int s_nG, s_nN, s_nE[3], s_ntouched, s_plen, s_ndefer;       // s_nE: three counters taking turns over the two E lists (one barrier per run-ahead pass)
-    __shared__ int s_gb[4], s_retry, s_ngb;                   // XR-Maze v2: bounding box of the net's access points (track indices), rip-up decision
+    __shared__ int s_gb[4], s_ngb;                            // XR-Maze v2: bounding box of the net's access points (track indices)
     __shared__ int4 s_gbx[XR_GUIDE_MAX_BOXES];                // ... and its guide (xr_guide_load)
 
     const int tid = threadIdx.x;
@@ -1235,7 +1029,7 @@ __device__ __forceinline__ void xr_dial_route_env_big(const XrBatchDev& b, const
     auto node_flags = [&](int f) -> uint32_t {
         const int nn = node_net[f], ow = owner[f];
         if (nn == -1) return 0u;
-        return 1u | (((ow != 0 && ow != a && !(V2 && ow == -a)) || (nn > 0 && nn != a)) ? 2u : 0u);     // (-a: a tentative claim of this very route)
+        return 1u | (((ow != 0 && ow != a && !(V2 && ow == -a)) || (nn > 0 && nn != a)) ? 2u : 0u);     // (-a: a tentative claim of this very route; none is written any more, the test is part of the shipped code: LAB_NOTES.md §8)
     };
     // first touch of a node in this route: remember it for the final reset
     auto touch = [&](uint32_t f) { const int k = atomicAdd(&s_ntouched, 1); touchg[k] = f; };
@@ -1268,13 +1062,13 @@ __device__ __forceinline__ void xr_dial_route_env_big(const XrBatchDev& b, const
     XR_LAP(0);
 
     const uint32_t via4 = (uint32_t)b.via_cost << 2;
-    uint32_t pen4 = (uint32_t)b.pen_cost << 2;              // (XR-Maze v2: doubled by every rip-up-and-reroute attempt)
+    uint32_t pen4 = (uint32_t)b.pen_cost << 2;              // (XR-Maze v2: shifted to the last attempt's penalty below)
     const uint32_t delta = R.w_min * (uint32_t)b.dial_mult_big;
     const uint32_t uYZ = (uint32_t)YZ, uZ = (uint32_t)Z;
-    int d_vio = 0, d_wl = 0, d_via = 0, plen = 0, status = XR_ENV_OK, d_held = 0;   // thread 0 only
+    int d_vio = 0, d_wl = 0, d_via = 0, plen = 0, status = XR_ENV_OK;   // thread 0 only
+    [[maybe_unused]] int d_held = 0;                        // (counted, never read; without it five kernels allocate registers differently: LAB_NOTES.md §8)
     int nrounds = 0;
-    const uint64_t h0 = (tid == 0) ? b.hash[e] : 0;
-    uint64_t h = h0;
+    uint64_t h = (tid == 0) ? b.hash[e] : 0;
     int32_t* __restrict__ path = b.path + (int64_t)e * b.path_cap;
 
     // put a node (back) into the open structure with distance d
@@ -1284,8 +1078,7 @@ __device__ __forceinline__ void xr_dial_route_env_big(const XrBatchDev& b, const
         atomicMin(&s_gmin[f >> 10], d);
     };
 
-    // XR-Maze v2, neutral by default: guide cost outside the net's guide box; tentative claims (owner = -a) until
-    // the attempt stands
+    // XR-Maze v2, neutral by default: guide cost outside the net's guide box
     const uint32_t guide4 = V2 ? (uint32_t)b.guide_cost << 2 : 0u;
     if (V2 && b.guide_cost) {
         xr_guide_load(b, R, a, s_gb, Z, s_gbx, &s_ngb, tid);
@@ -1301,15 +1094,9 @@ __device__ __forceinline__ void xr_dial_route_env_big(const XrBatchDev& b, const
         if (!V2) return 0u;
         return (guide4 != 0u && !xr_guide_has(s_gbx, ngb, gb0, x, y, z)) ? guide4 : 0u;
     };
-    const int16_t claim_val = (int16_t)(XR3_ALL_ATTEMPTS && V2 && b.maze_end_iter > 1 ? -a : a);      // (one attempt: its claims are final)
-#ifdef XR3_V2_ALL_ATTEMPTS
-    int attempt = 0;
-#else           // the rip-up-and-reroute loop has one possible outcome: the last attempt's route (xr_dial3.h)
-    int attempt = V2 ? max(b.maze_end_iter, 1) - 1 : 0;
-    if (V2) pen4 <<= attempt;
-#endif
+    // the rip-up-and-reroute loop has one possible outcome: the last attempt's route (xr_dial3.h)
+    if (V2) pen4 <<= max(b.maze_end_iter, 1) - 1;
 
-    for (;;) {                                              // attempts (exactly one unless maze_end_iter > 1)
     for (;;) {
         // ---- new search ---------------------------------------------------------------------------------
         if (tid == 0) {
@@ -1500,7 +1287,7 @@ __device__ __forceinline__ void xr_dial_route_env_big(const XrBatchDev& b, const
                     // (Round 5, measured and NOT adopted — both bit-exact: look-ahead loads of the next pass's words by the idle half of the
                     //  workgroup, +12 % (profiles/r05_g_*); "flags forward": the pass that lowers a node fetches the flags of ITS neighbours beside
                     //  its atomic and hands them on in the E entry, so the next pass goes straight to its atomics — one L2 round trip per pass
-                    //  instead of two, yet +17 % (profiles/r05_j_*, tools/archive/xr_big_flags_forward.patch): the pass-split probe shows why —
+                    //  instead of two, yet +17 % (profiles/r05_j_*): the pass-split probe shows why —
                     //  ~1.1 k of a pass's ~3.5 k cycles are the index / heuristic arithmetic in front of the atomic, the word load hides
                     //  behind it, and six more loads per lane queue up behind the atomic whose result the pass waits for.)
                     for (int it = tid; it < 4 * nE; it += nthr) {
@@ -1520,9 +1307,7 @@ __device__ __forceinline__ void xr_dial_route_env_big(const XrBatchDev& b, const
                         const bool inb = (unsigned)nx < (unsigned)X && (unsigned)ny < (unsigned)Y && (unsigned)nz < (unsigned)Z;
                         const int nf = inb ? (int)f + ddx * YZ + ddy * Z + ddz : (int)f;
                         const uint32_t wn = xr_ld(&fieldg[nf]);
-#if XR_BIG_SPEC_FLAGS
                         const int nn0 = node_net[nf], ow0 = owner[nf];        // flags of a first touch, loaded with the word, not after it
-#endif
                         const uint32_t xq = s_xc[x + 1], yq = s_yc[y + 1];
                         const uint32_t cb = (vert ? s_yc : s_xc)[(vert ? (int)y : (int)x) + 1 + (planar ? sgn : 0)];
                         const uint32_t ca = vert ? yq : xq;
@@ -1538,11 +1323,7 @@ __device__ __forceinline__ void xr_dial_route_env_big(const XrBatchDev& b, const
                         if (!inb) continue;
                         uint32_t fl;
                         if (wn == XR_BIG_CLEAN) {                                 // first touch: derive the flags
-#if XR_BIG_SPEC_FLAGS
                             fl = nn0 == -1 ? 0u : (1u | (((ow0 != 0 && ow0 != a && !(V2 && ow0 == -a)) || (nn0 > 0 && nn0 != a)) ? 2u : 0u));
-#else
-                            fl = node_flags(nf);
-#endif
                             if (fl == 0u) continue;
                         } else fl = wn & 3u;
                         const uint32_t cand4 = d4 + len4 + ((fl & 2u) ? pen4 : 0u) + gq;
@@ -1580,9 +1361,6 @@ __device__ __forceinline__ void xr_dial_route_env_big(const XrBatchDev& b, const
                     //  L2 round trip per pass on the critical chain.  A later pass that reads a word an unacknowledged atomic is about to
                     //  lower sees the older, HIGHER value: it may issue an atomicMin that loses, never skip one that would win.)
                     xr_lds_barrier();
-#ifdef XR_BIG_TWO_BARRIERS          // A/B: round 4's second barrier per pass (the counters need none)
-                    xr_lds_barrier();
-#endif
 #ifdef XR_BIG_PASS_PROBE
                     if (tid == 0) {
                         const long long pp4 = clock64();
@@ -1712,7 +1490,7 @@ __device__ __forceinline__ void xr_dial_route_env_big(const XrBatchDev& b, const
                     s_remaining = 0;
                 } else if (tid == 0) {
                     if (owner[v] == 0) {
-                        owner[v] = claim_val;
+                        owner[v] = (int16_t)a;
                         if (plen < b.path_cap) path[plen] = v;
                         plen++;
                         fnv_mix(h, (uint32_t)v);
@@ -1734,13 +1512,13 @@ __device__ __forceinline__ void xr_dial_route_env_big(const XrBatchDev& b, const
                 for (int i = tid; i < np; i += nthr) {
                     const int f = (int)pathg[i];
                     make_source(f);
-                    if (owner[f] == 0) owner[f] = claim_val;
+                    if (owner[f] == 0) owner[f] = (int16_t)a;
                 }
             }
         }
         XR_LAP(4);
     }
-    // ---- leave the scratch CLEAN: reset exactly what this route (attempt) touched ----------------------------
+    // ---- leave the scratch CLEAN: reset exactly what this route touched ----------------------------
     {
         const int nt = s_ntouched;
         for (int i = tid; i < nt; i += nthr) {
@@ -1749,28 +1527,6 @@ __device__ __forceinline__ void xr_dial_route_env_big(const XrBatchDev& b, const
             xr_st(&openg[f >> 5], 0u);
             xr_st(&wming[f >> 5], XR_DIAL_INF);
         }
-    }
-    if (!XR3_ALL_ATTEMPTS || !V2 || b.maze_end_iter <= 1) break;
-    // ---- XR-Maze v2: does the attempt stand?  Its path uses a node held by another net and attempts are left: rip it up ----
-    if (tid == 0) s_retry = (d_held > 0 && attempt + 1 < b.maze_end_iter) ? 1 : 0;
-    __syncthreads();
-    const bool retry = s_retry != 0;
-    for (int f = tid; f < N; f += nthr)                       // tentative claims: accepted (-a -> a) or undone (-a -> 0)
-        if (owner[f] == (int16_t)-a) owner[f] = retry ? (int16_t)0 : (int16_t)a;
-    if (!retry) break;
-    attempt++;
-    pen4 = ((uint32_t)b.pen_cost << 2) << attempt;
-    if (tid == 0) { d_vio = 0; d_wl = 0; d_via = 0; plen = 0; d_held = 0; status = XR_ENV_OK; h = h0; s_ntouched = 0; s_ndefer = 0; }
-    for (int i = tid; i < ng; i += nthr) s_gmin[i] = XR_DIAL_INF;
-    __syncthreads();                                          // scratch CLEAN, owner grid restored: start over from the first pin
-    for (int i = tid; i < nap; i += nthr) {
-        const bool iso = s_ap_conn[i] == 2;
-        const bool first = s_ap_pin[i] == (short)s_first_pin;
-        s_ap_conn[i] = iso ? 2 : (first ? 1 : 0);
-        if (first && !iso) make_source(s_ap_f[i]);
-    }
-    if (tid == 0) s_remaining = s_npins - 1 - n_isolated;
-    // (the barriers at the top of the search loop order all of this)
     }
     if (tid == 0) {
         if (n_isolated > 0) { d_vio += n_isolated; status |= XR_ENV_UNREACHABLE; }

@@ -25,6 +25,8 @@
 //    node can be claimed is in its word (not held <=> owner 0 or this net), a ripped-up attempt is undone by an LDS-only pass that
 //    returns every word to "unreached" (the static bits stay), and the attempt that stands is accepted by one scan of the words
 //    (source + owner bit + not held -> owner = net).  No owner reads, no N-wide global passes, no field rebuild per attempt.
+//    Since round 5 the route is computed ONCE, at the last attempt's penalty: no attempt is ripped up any more, and
+//    the undo pass is compiled but never reached (see the attempt loop).
 //
 // Two other search organisations were built on this word format and measured this round (git history of this file): ONE searching
 // wave with explicit bucket queues and wave-uniform counters (mean route -30 %, but a route with a wide frontier — 60 rounds — took
@@ -41,19 +43,6 @@
 #define XR3_WSYNC() do { __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); __builtin_amdgcn_wave_barrier(); \
                          __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront"); } while (0)
 
-// Solo rounds (round 5): a round whose predecessor took at most XR3_SOLO_ENTER nodes from the mask is run by ONE wave (the tracing wave) on its
-// own — scan, quads, next minimum — and so are the rounds after it, with wave-level synchronisation only, until a round takes more than
-// XR3_SOLO_EXIT nodes or the search ends; the other waves of the workgroup are parked at one barrier meanwhile.  A narrow frontier has work for
-// a few quads: four waves then mostly pay for each other's barrier skew (26 % of a route).  Same results (rounds are rounds, whoever runs them).
-// XR3_SOLO_ENTER < 0: off.
-#ifndef XR3_SOLO_ENTER
-#define XR3_SOLO_ENTER (-1)
-#endif
-#ifndef XR3_SOLO_EXIT
-#define XR3_SOLO_EXIT 24
-#endif
-
-#ifndef XR3_WAVE_MIN_SHFL
 // wave-wide min by DPP (row_shr 1,2,4,8 -> lane 15 of every row; row_bcast:15, row_bcast:31 -> lane 63), ~12 VALU ops, no LDS
 __device__ __forceinline__ uint32_t xr3_wave_min(uint32_t v) {
     const int id = -1;        // identity of min on u32
@@ -66,9 +55,6 @@ __device__ __forceinline__ uint32_t xr3_wave_min(uint32_t v) {
     t = (uint32_t)__builtin_amdgcn_update_dpp(id, (int)v, 0x143, 0xC, 0xF, false); v = t < v ? t : v;
     return (uint32_t)__builtin_amdgcn_readlane((int)v, 63);
 }
-#else
-__device__ __forceinline__ uint32_t xr3_wave_min(uint32_t v) { return xr_wave_min_u32(v); }
-#endif
 
 // n / d and n % d by the region's exact 24-bit magic (XrRegionDev::m24_*: verified at load for every n asked here): two full-rate
 // 24-bit multiplies instead of a 32-bit mul_hi / mul_lo pair plus fix-up
@@ -103,10 +89,9 @@ __device__ __forceinline__ bool xr_dial3_route_env(const XrBatchDev& b, const in
     __shared__ unsigned char s_ap_own[XR_MAX_AP_PER_NET];       // the access point's node had an owner when the route began (a used access point of this net)
     __shared__ unsigned char s_ap_slot[XR_MAX_AP_PER_NET];      // which heuristic box the access point's pin is dealt to (static, from the load)
     __shared__ uint32_t s_min[3], s_bst[3];                     // rotating per round: smallest open key, smallest target distance
-    __shared__ int s_cnt[3];                                    // ... and the nodes the round took from the mask (XR3_ADAPT: sparse rounds widen the bucket)
+    __shared__ int s_cnt[3];                                    // (written, never read since the bucket-width builds went; its stores are part of the shipped code: LAB_NOTES.md §8)
     __shared__ int s_hb[3][6];                                  // heuristic: three boxes over the unconnected pins (x, y: coordinates x32; z), see the search start
     __shared__ int s_qcnt[16];                                  // per wave: nodes of the bucket queued for its quads
-    __shared__ int s_hand[2];                                   // solo rounds: where the solo wave left the search (cur | rounds so far << 2), two slots taking turns
     __shared__ unsigned short s_qn[XR_QUAD_POOL];
     __shared__ int s_remaining, s_abort;
     __shared__ int s_gb[4], s_retry, s_ngb;                     // XR-Maze v2: bounding box of the net's access points (track indices), rip-up decision
@@ -274,14 +259,12 @@ __device__ __forceinline__ bool xr_dial3_route_env(const XrBatchDev& b, const in
     // the wave that selects targets and traces paths (everything else is done by the whole workgroup): rotates with the env
 #if defined(XR_PHASE_TIMING)
     const int sw = XR_TIMING_TID >> 6;
-#elif defined(XR3_SW0)
-    const int sw = 0;
 #else
     const int sw = (int)(((uint32_t)e * 0x9E3779B1u) >> 16) % (nthr >> 6);
 #endif
 
     const uint32_t via5 = (uint32_t)b.via_cost << 5;
-    uint32_t pen5 = (uint32_t)b.pen_cost << 5;              // (XR-Maze v2: doubled by every rip-up-and-reroute attempt)
+    uint32_t pen5 = (uint32_t)b.pen_cost << 5;              // (XR-Maze v2: shifted to the last attempt's penalty below)
     const uint32_t delta = R.w_min * (uint32_t)b.dial_mult * (uint32_t)(meas_cls >= b.heavy_class && b.heavy_class > 0 ? b.heavy_mult : 1);  // bucket width (keys f = d + h, DBU)
     const uint32_t guide5 = V2 ? (uint32_t)b.guide_cost << 5 : 0u;
     const uint32_t sh_yz = s24w & 31u, sh_z = (s24w >> 8) & 31u, sh_mw = (s24w >> 16) & 31u;       // (window form: its own magics)
@@ -332,14 +315,9 @@ __device__ __forceinline__ bool xr_dial3_route_env(const XrBatchDev& b, const in
     // held node cost what they cost, every alternative through one only got dearer — same distances along them, same first tight
     // predecessors, same targets (the argument behind round 4's "resume at the failed search", applied to a whole attempt) — and so would
     // every later one, up to the last.  If no attempt stands, the last one is the result by definition.  So the route is computed once, at
-    // the penalty of the last attempt (pen << (maze_end_iter - 1)); the loop below never iterates.  -DXR3_V2_ALL_ATTEMPTS keeps the
-    // attempt-by-attempt form of round 4 (same results: the A/B and the proof by test).
-#ifdef XR3_V2_ALL_ATTEMPTS
-    int attempt = 0;
-#else
+    // the penalty of the last attempt (pen << (maze_end_iter - 1)).
     int attempt = V2 ? max(b.maze_end_iter, 1) - 1 : 0;
     if (V2) pen5 <<= attempt;
-#endif
 
     // per-lane constants of a quad: lane 4g + d relaxes direction d of quad g's node: 0 +planar, 1 -planar, 2 +z, 3 -z
     const int dir = lane & 3, qbase = lane & ~3;
@@ -374,7 +352,9 @@ __device__ __forceinline__ bool xr_dial3_route_env(const XrBatchDev& b, const in
     uint64_t sv_h = h0;
     bool resume = false;
     bool win_fail = false;                                  // window form, tracing wave: a certificate failed
-    for (;;) {                                              // attempts (exactly one unless maze_end_iter > 1)
+    for (;;) {                                              // attempts: always exactly ONE pass.  `attempt` starts at the last one, so `doomable` and `retry` below
+                                                            // are never true and the rip-up pass at the end never runs; the compiler does not see that, so
+                                                            // taking them out changes the shipped code and is a change of its own (LAB_NOTES.md §8)
     // component = all access points of the lowest pin id (a resumed attempt: of every pin connected so far; its path nodes are sources still)
     for (int i = tid; i < nap; i += nthr)
         if (s_ap_conn[i] == 1) make_source((uint32_t)s_ap_f[i], s_ap_own[i] != 0);
@@ -407,11 +387,7 @@ __device__ __forceinline__ bool xr_dial3_route_env(const XrBatchDev& b, const in
                 int ax, ay, az;
                 node_xyz((uint32_t)s_ap_f[i], ax, ay, az);
                 const int cx = (int)s_tab[ax + 1], cy = (int)s_tab[XO + ay + 1];
-#ifdef XR3_HB_ONE       // A/B: one box around all unconnected pins (rounds 2-3)
-                int* hb = s_hb[0];
-#else
                 int* hb = s_hb[s_ap_slot[i] < 3 ? s_ap_slot[i] : 0];
-#endif
                 atomicMin(&hb[0], cx); atomicMax(&hb[1], cx); atomicMin(&hb[2], cy); atomicMax(&hb[3], cy);
                 atomicMin(&hb[4], az); atomicMax(&hb[5], az);
             }
@@ -436,59 +412,26 @@ __device__ __forceinline__ bool xr_dial3_route_env(const XrBatchDev& b, const in
         };
         XR_LAP(4);
         int cur = 0;
-        [[maybe_unused]] int bscale = 1;      // (XR3_ADAPT_LO builds: bucket width of the round, in units of delta)
         bool aborted = false;                 // (round cap: xr_dial.h)
-        bool soloing = false;                 // this wave runs the rounds on its own (the tracing wave only; the others wait at a barrier)
-        int hpar = 0;                         // which hand-off slot the next solo episode uses (every wave counts the episodes)
         for (int nsr = 0;; nsr++) {
             int nx1 = cur == 2 ? 0 : cur + 1, nx2 = nx1 == 2 ? 0 : nx1 + 1;
             const uint32_t m = s_min[cur], best = s_bst[cur];
             const bool sdone = m == XR_DIAL_INF || m > best;
             const bool scap = nsr >= round_cap || s_abort;
-            if (XR3_SOLO_ENTER >= 0) {
-                const int pc = s_cnt[cur];                        // nodes the round before this one took from the mask (search start: 1 << 20)
-                if (soloing && (sdone || scap || pc > XR3_SOLO_EXIT)) {      // leave the episode: publish where the search stands, release the others
-                    if (lane == 0) s_hand[hpar] = cur | (nsr << 2);
-                    hpar ^= 1;
-                    xr_lds_barrier();
-                    soloing = false;
-                }
-                if (!soloing && !sdone && !scap && pc <= XR3_SOLO_ENTER) {   // (uniform over the workgroup: everybody read the same pc)
-                    if (wv != sw) {                               // parked until the solo wave leaves its episode
-                        xr_lds_barrier();
-                        const int hv = s_hand[hpar];
-                        hpar ^= 1;
-                        cur = hv & 3; nsr = (hv >> 2) - 1;
-                        continue;
-                    }
-                    soloing = true;
-                }
-            }
             if (sdone) break;                                                // uniform
             if (scap) { aborted = true; break; }                             // uniform (s_abort: written before the last barrier)
-            // the team of this round: the whole workgroup, or the solo wave
-            const int tE = soloing ? lane : tid, nE = soloing ? 64 : nthr;
-#ifdef XR3_GROW_AFTER        // A/B only (profiles/r03_q_ab_growing_bucket_width.txt: wider late buckets cost 3-18 % --
-                             // the extra re-expansions outweigh the rounds saved); off in the shipped build
-            const uint32_t hi = m + (nsr >= XR3_GROW_AFTER ? delta * XR3_GROW_BY : delta);
-#elif defined(XR3_ADAPT_LO)  // A/B (round 4): a round that took fewer than XR3_ADAPT_LO nodes from the mask doubles the next bucket (up to
-                             // XR3_ADAPT_MAX x), one that took more than XR3_ADAPT_HI goes back to one width.  Bucket widths never change results.
-            { const int pc = s_cnt[cur]; if (pc < XR3_ADAPT_LO) bscale = min(bscale << 1, XR3_ADAPT_MAX); else if (pc > XR3_ADAPT_HI) bscale = 1; }
-            const uint32_t hi = m + delta * (uint32_t)bscale;
-#else
             const uint32_t hi = m + delta;
-#endif
             uint32_t lmin = XR_DIAL_INF;
-            if (tE == 0) { s_min[nx2] = XR_DIAL_INF; s_bst[nx2] = XR_DIAL_INF; s_cnt[nx2] = 0; }
+            if (tid == 0) { s_min[nx2] = XR_DIAL_INF; s_bst[nx2] = XR_DIAL_INF; s_cnt[nx2] = 0; }
             // bound for the next round: smallest tentative distance of an unconnected target
             // (by the threads at the END of the workgroup: the first wave carries the words beyond one per thread)
-            for (int i = nE - 1 - tE; i < nap; i += nE)
+            for (int i = nthr - 1 - tid; i < nap; i += nthr)
                 if (!s_ap_conn[i]) { const uint32_t d = field[s_ap_f[i]] >> 5; if (d != XR3_DMAX) atomicMin(&s_bst[nx1], d); }
             // A lane scans word wi and — where the mask has more words than the workgroup has threads — word wi + nthr in the
             // SAME pass (one 64-bit bit set).  The nodes of this bucket are then expanded by QUADS of lanes, one lane per direction.
-            for (int wbase = 0; wbase < mw; wbase += 2 * nE) {            // (uniform trip count: the expansion is wave-cooperative)
-                const int wi = wbase + tE;
-                const int wi2 = wi + nE;
+            for (int wbase = 0; wbase < mw; wbase += 2 * nthr) {            // (uniform trip count: the expansion is wave-cooperative)
+                const int wi = wbase + tid;
+                const int wi2 = wi + nthr;
                 unsigned long long expd = 0;
                 if (wi < mw) {
                     const bool has2 = wi2 < mw;
@@ -543,9 +486,9 @@ __device__ __forceinline__ bool xr_dial3_route_env(const XrBatchDev& b, const in
                 XR_LAP(1);
                 // ---- the wave's nodes of this bucket go into its slice of a small LDS queue (no room: back into the mask)
                 {
-                    const int qcap = soloing ? XR_QUAD_POOL : XR_QUAD_POOL / ((nthr + 63) >> 6);      // (alone: the whole pool)
+                    const int qcap = XR_QUAD_POOL / ((nthr + 63) >> 6);
                     int* qcnt = &s_qcnt[wv];
-                    unsigned short* qn = soloing ? s_qn : s_qn + wv * qcap;
+                    unsigned short* qn = s_qn + wv * qcap;
                     if (lane == 0) *qcnt = 0;
                     __builtin_amdgcn_wave_barrier();
                     while (expd) {
@@ -559,11 +502,6 @@ __device__ __forceinline__ bool xr_dial3_route_env(const XrBatchDev& b, const in
                     }
                     __builtin_amdgcn_wave_barrier();
                     const int nq = min(__builtin_amdgcn_readfirstlane(*qcnt), qcap);
-#if defined(XR3_ADAPT_LO)
-                    if (lane == 0 && nq) atomicAdd(&s_cnt[nx1], nq);
-#else
-                    if (XR3_SOLO_ENTER >= 0 && lane == 0 && nq) atomicAdd(&s_cnt[nx1], nq);
-#endif
                     // ---- quads: lanes 4g .. 4g+3 follow ONE chain, lane 4g+d relaxes direction d of the chain's current node
                     int gf = -1, gx = 0, gy = 0, gz = 0, qh = 0;
                     for (int nhop = 0;; nhop++) {
@@ -632,7 +570,7 @@ __device__ __forceinline__ bool xr_dial3_route_env(const XrBatchDev& b, const in
             lmin = xr3_wave_min(lmin);
             if (lane == 0 && lmin != XR_DIAL_INF) atomicMin(&s_min[nx1], lmin);
             if (wv == sw) nrounds++;
-            if (soloing) XR3_WSYNC(); else xr_lds_barrier();
+            xr_lds_barrier();
             XR_LAP(6);
             cur = nx1;
         }

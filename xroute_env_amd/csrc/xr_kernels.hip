@@ -342,35 +342,15 @@ __device__ __forceinline__ void xr_or_run(uint32_t* mask, int id0, uint32_t bits
     if (m1) atomicOr(&mask[wdx + 1], m1);
 }
 
-// Field layouts.
-//  PACKED_XYZ (used by both kernel variants): l = x*SX + y*SY + z with SY = Z|1, SX = (Y*SY)|1 (odd strides):
-//    lanes of a wave hold consecutive lines, so wave accesses have odd word strides: LDS bank-conflict free.
-//  LAYER_MAJOR (HBM-scratch variant only, compile with -DXR_SCRATCH_LAYER_MAJOR=1):
-//    l = z*X*Y + (layer z vertical ? x*Y + y : y*X + x): every track unit-stride, via columns gather one word per
-//    layer plane.  Measured SLOWER on BASELINE config 5 (256x256x12: 85 vs 67 ms per 64-env launch): the via
-//    columns are more than half of the line visits and become 12 cache lines each.  Kept for A/B runs.
-#ifndef XR_SCRATCH_LAYER_MAJOR
-#define XR_SCRATCH_LAYER_MAJOR 0
-#endif
-template <bool LDS_DIST_>
+// Field layout (both kernel variants): l = x*SX + y*SY + z with SY = Z|1, SX = (Y*SY)|1 (odd strides):
+// lanes of a wave hold consecutive lines, so wave accesses have odd word strides: LDS bank-conflict free.
 struct XrLayout {
-    static constexpr bool LDS_DIST = LDS_DIST_ || !XR_SCRATCH_LAYER_MAJOR;   // true: packed-xyz index math
-    int X, Y, Z, SX, SY, XY;
-    uint32_t ldir;
-    __device__ __forceinline__ XrLayout(int x, int y, int z, uint32_t ld) : X(x), Y(y), Z(z), ldir(ld) {
-        SY = Z | 1; SX = (Y * SY) | 1; XY = X * Y;
-    }
-    __device__ __forceinline__ int size() const { return LDS_DIST ? X * SX : Z * XY; }
-    __device__ __forceinline__ int idx(int x, int y, int z) const {
-        if (LDS_DIST) return x * SX + y * SY + z;
-        return z * XY + (((ldir >> z) & 1u) ? x * Y + y : y * X + x);
-    }
+    int X, SX, SY;
+    __device__ __forceinline__ XrLayout(int x, int y, int z) : X(x) { SY = z | 1; SX = (y * SY) | 1; }
+    __device__ __forceinline__ int size() const { return X * SX; }
+    __device__ __forceinline__ int idx(int x, int y, int z) const { return x * SX + y * SY + z; }
     __device__ __forceinline__ void decode(int l, int& x, int& y, int& z) const {
-        if (LDS_DIST) { x = l / SX; const int r = l - x * SX; y = r / SY; z = r - y * SY; }
-        else {
-            z = l / XY; const int r = l - z * XY;
-            if ((ldir >> z) & 1u) { x = r / Y; y = r - x * Y; } else { y = r / X; x = r - y * X; }
-        }
+        x = l / SX; const int r = l - x * SX; y = r / SY; z = r - y * SY;
     }
 };
 
@@ -420,7 +400,7 @@ __device__ __forceinline__ void xr_route_env(const XrBatchDev& b, const int e, c
 
     XR_T0();
     const int X = R.X, Y = R.Y, Z = R.Z, N = R.N;
-    const XrLayout<LDS_DIST> lay(X, Y, Z, R.ldir_mask);
+    const XrLayout lay(X, Y, Z);
     const int NL = lay.size();                    // field size in words (padded in the LDS layout)
     const int ncol = X * Y;
     const uint32_t ldir = R.ldir_mask;
@@ -634,7 +614,7 @@ __device__ __forceinline__ void xr_route_env(const XrBatchDev& b, const int e, c
                         const int it = (int)s_listH[k];
                         const int t = it / chH, c0 = it - t * chH;
                         const int zi = t / Y, y = t - zi * Y;
-                        const int base = lay.idx(0, y, s_hl[zi]), stride = lay.LDS_DIST ? lay.SX : 1;
+                        const int base = lay.idx(0, y, s_hl[zi]), stride = lay.SX;
                         auto ix = [=](int i) { return base + i * stride; };
                         // lowered node x: column (x, y) must be looked at (the chunk of the column holding this layer)
                         const int zc = (ZCH > 0) ? 0 : (int)s_hl[zi] / XR_CH;
@@ -653,7 +633,7 @@ __device__ __forceinline__ void xr_route_env(const XrBatchDev& b, const int e, c
                         const int it = (int)s_listV[k - offV];
                         const int t = it / chV, c0 = it - t * chV;
                         const int zi = t / X, x = t - zi * X;
-                        const int base = lay.idx(x, 0, s_vl[zi]), stride = lay.LDS_DIST ? lay.SY : 1;
+                        const int base = lay.idx(x, 0, s_vl[zi]), stride = lay.SY;
                         auto ix = [=](int i) { return base + i * stride; };
                         const int zc = (ZCH > 0) ? 0 : (int)s_vl[zi] / XR_CH;
                         auto mk = [&](int start, uint32_t bits) {
@@ -682,10 +662,9 @@ __device__ __forceinline__ void xr_route_env(const XrBatchDev& b, const int e, c
                         }
                     };
                     auto df = [&](int cc) { const int id = itC0 + c * chC + cc; atomicOr(&s_defer[id >> 5], 1u << (id & 31)); };
-                    // via chain: unit stride in the packed layout; one word per layer plane in the layer-major layout
-                    const bool packed = lay.LDS_DIST;
-                    const int cbase = packed ? lay.idx(x, y, 0) : 0, offh = y * X + x, offv = x * Y + y, xy = lay.XY;
-                    auto ix = [=](int z) { return packed ? cbase + z : z * xy + (((ldir >> z) & 1u) ? offv : offh); };
+                    // via chain: unit stride
+                    const int cbase = lay.idx(x, y, 0);
+                    auto ix = [=](int z) { return cbase + z; };
                     if (ZCH > 0) {
                         xr_seg_pass<true, false, (ZCH > 0 ? ZCH : 1), true, !LDS_DIST>(field, nullptr, ix, ZCH, via4, pen4, bound4, 0, mk, df);
                         xr_seg_pass<false, false, (ZCH > 0 ? ZCH : 1), true, !LDS_DIST>(field, nullptr, ix, ZCH, via4, pen4, bound4, 0, mk, df);
@@ -978,12 +957,9 @@ __device__ __forceinline__ void xr_node_features(const Src& s, int f, int X, int
 }
 
 // VEC = 4: float4 stores (needs N % 4 == 0 and 16-byte aligned planes); VEC = 1: any N.
-#ifndef XR_OBS_PLAIN_STORES      // non-temporal: the observation is written once and read by somebody else
+// non-temporal: the observation is written once and read by somebody else
 typedef float xr_f4 __attribute__((ext_vector_type(4)));
 #define XR_ST4(ptr, val) __builtin_nontemporal_store(xr_f4{(val).x, (val).y, (val).z, (val).w}, reinterpret_cast<xr_f4*>(ptr))
-#else
-#define XR_ST4(ptr, val) (*reinterpret_cast<float4*>(ptr) = (val))
-#endif
 template <class Src, int VEC>
 __device__ __forceinline__ void xr_obs_write(const Src& s, int X, int Y, int Z, int N, const int* s_ids, int K,
                                              float* __restrict__ out, int chunk_base, int knets = -1) {
@@ -1465,11 +1441,6 @@ __global__ void __launch_bounds__(BT) xr_plan_kernel(XrBatchDev b, const int32_t
     }
 }
 
-#ifdef XR_NP_PLAIN
-#define XR_NP_ST4(ptr, val) (*reinterpret_cast<float4*>(ptr) = (val))
-#else
-#define XR_NP_ST4(ptr, val) XR_ST4(ptr, val)
-#endif
 #define XR_NP_J 9            // float4 groups per thread per tile: 256 threads * 4 nodes * 9 = 9216 nodes
 // one unit = the 7 planes of one remaining net of one env (aligned planes: every region's N % 4 == 0)
 __device__ __forceinline__ void xr_unit_aligned(const XrBatchDev& b, int u) {
@@ -1500,27 +1471,7 @@ __device__ __forceinline__ void xr_unit_aligned(const XrBatchDev& b, int u) {
             for (int j = 0; j < XR_NP_J; j++) bits[j] |= (g == j * 256) ? m : 0u;
         }
         // plane 0 of the net: AP mask; planes 1..6: the six aliased "has a same-net axis neighbour" planes
-#ifndef XR_NP_ORDER
-#define XR_NP_ORDER 1
-#endif
-#if XR_NP_ORDER == 0       // plane-major: the workgroup writes the unit as one sequential run
-#pragma unroll 1
-        for (int pl = 0; pl < 7; pl++) {
-            float* __restrict__ pp = out + (int64_t)pl * N;
-            const int sh = pl ? 4 : 0;
-#pragma unroll
-            for (int j = 0; j < XR_NP_J; j++) {
-                const int g = g0 + j * 256 + tid;
-                if (g < ngrp) {
-                    const unsigned m = bits[j] >> sh;
-                    float4 v;
-                    v.x = (m & 1u) ? 1.f : 0.f; v.y = (m & 2u) ? 1.f : 0.f;
-                    v.z = (m & 4u) ? 1.f : 0.f; v.w = (m & 8u) ? 1.f : 0.f;
-                    XR_NP_ST4(pp + ((int64_t)g << 2), v);
-                }
-            }
-        }
-#else                      // rotation: 4 KB of each of the 7 planes in turn (the step kernel's own order)
+        // rotation: 4 KB of each of the 7 planes in turn (the step kernel's own order)
 #pragma unroll
         for (int j = 0; j < XR_NP_J; j++) {
             const int g = g0 + j * 256 + tid;
@@ -1530,12 +1481,11 @@ __device__ __forceinline__ void xr_unit_aligned(const XrBatchDev& b, int u) {
                 float4 v0, v1;
                 v0.x = (m0 & 1u) ? 1.f : 0.f; v0.y = (m0 & 2u) ? 1.f : 0.f; v0.z = (m0 & 4u) ? 1.f : 0.f; v0.w = (m0 & 8u) ? 1.f : 0.f;
                 v1.x = (m1 & 1u) ? 1.f : 0.f; v1.y = (m1 & 2u) ? 1.f : 0.f; v1.z = (m1 & 4u) ? 1.f : 0.f; v1.w = (m1 & 8u) ? 1.f : 0.f;
-                XR_NP_ST4(pp, v0);
+                XR_ST4(pp, v0);
 #pragma unroll
-                for (int pl = 1; pl < 7; pl++) XR_NP_ST4(pp + (int64_t)pl * N, v1);
+                for (int pl = 1; pl < 7; pl++) XR_ST4(pp + (int64_t)pl * N, v1);
             }
         }
-#endif
     }
 }
 
@@ -1633,11 +1583,7 @@ __device__ __forceinline__ void xr_unit_stream(const XrBatchDev& b, int u, uint3
 // XrBatchDev::obs_out_u8 selects it; obs_stride is then in bytes, a multiple of 16, and the row base 16-byte aligned.
 // ------------------------------------------------------------------------------------------------
 typedef unsigned xr_u4 __attribute__((ext_vector_type(4)));
-#ifndef XR_OBS_PLAIN_STORES
 #define XR_STU8(ptr, v) __builtin_nontemporal_store((v), reinterpret_cast<xr_u4*>(ptr))
-#else
-#define XR_STU8(ptr, v) (*reinterpret_cast<xr_u4*>(ptr) = (v))
-#endif
 // 4 mask bits (bit j = node j) -> 4 bytes 0 / 1
 __device__ __forceinline__ uint32_t xr_nib_bytes(uint32_t m) {
     return (m & 1u) | ((m & 2u) << 7) | ((m & 4u) << 14) | ((m & 8u) << 21);
@@ -1832,12 +1778,7 @@ __global__ void __launch_bounds__(256) xr_obs_u8_kernel(XrBatchDev b, uint8_t* _
     }
 }
 
-#ifndef XR_QUEUE_SKIP
-#define XR_QUEUE_SKIP 1
-#endif
-#ifndef XR_QUEUE_BATCH
-#define XR_QUEUE_BATCH 1
-#endif
+constexpr int XR_QUEUE_BATCH = 1;      // units a workgroup claims per atomic
 // Static first tasks of the queue form (see xr_step_queue_kernel): of G workgroups, those with bit `sh` of their index clear start with
 // a route (first_r of them), the others with a unit (first_u); sh < 0: every workgroup starts with a route.
 __device__ __forceinline__ void xr_queue_first(int G, int sh, int& first_r, int& first_u) {
@@ -1854,7 +1795,7 @@ __global__ void __launch_bounds__(256) xr_unit_helper_kernel(XrBatchDev b) {
     __shared__ int s_u;
     const int total = (int)b.queue[2];
     int first_r, first_u;
-    xr_queue_first(b.queue_grid, XR_QUEUE_SKIP == 1 ? b.queue_skip_shift : -1, first_r, first_u);     // (units 0 .. first_u - 1 belong to the step kernel)
+    xr_queue_first(b.queue_grid, b.queue_skip_shift, first_r, first_u);     // (units 0 .. first_u - 1 belong to the step kernel)
     for (;;) {
         if (threadIdx.x == 0) s_u = first_u + (int)atomicAdd(&b.queue[1], 1u);
         __syncthreads();
@@ -1880,9 +1821,8 @@ __global__ void __launch_bounds__(256) xr_netplane_stream_kernel(XrBatchDev b) {
 // half of the workgroups (bit 5 of the workgroup index: spread over every XCD and CU) start with units so that the launch writes
 // from its first microseconds.  No workgroup ever waits for another one.
 // ------------------------------------------------------------------------------------------------
-#ifndef XR_QUEUE_WAVES_PER_SIMD
-#define XR_QUEUE_WAVES_PER_SIMD 4      // register budget of the persistent step kernel: 4 waves per SIMD = its own 4 workgroups per CU.
-#endif                                 // (6 = <= 80 VGPRs, room for helper-writer waves beside them: measured no faster)
+constexpr int XR_QUEUE_WAVES_PER_SIMD = 4;     // register budget of the persistent step kernel: 4 waves per SIMD = its own 4 workgroups per CU.
+                                               // (6 = <= 80 VGPRs, room for helper-writer waves beside them: measured no faster)
 // (U8: the uint8 observation, XrBatchDev::obs_out_u8 — same tasks, same queues, byte writers; the fp32 kernel is the U8 = false body)
 template <bool LDS_DIST, int ZCH, bool U8>
 __device__ __forceinline__ void xr_step_queue_body(XrBatchDev& b, const int32_t* __restrict__ actions, char* smem) {
@@ -1892,15 +1832,14 @@ __device__ __forceinline__ void xr_step_queue_body(XrBatchDev& b, const int32_t*
     const int total = (int)b.queue[2];
     const int quota = max(1, (int)(((int64_t)total * b.queue_quota_pm) / (1000 * (int64_t)B)));
     bool routes_left = true, units_left = total > 0;
-    bool skip_route = XR_QUEUE_SKIP == 1 ? (b.queue_skip_shift >= 0 && ((blockIdx.x >> b.queue_skip_shift) & 1) != 0) : XR_QUEUE_SKIP == 2 ? (blockIdx.x & 3) == 3
-                    : XR_QUEUE_SKIP == 3 ? (blockIdx.x & 3) != 0 : false;
+    bool skip_route = b.queue_skip_shift >= 0 && ((blockIdx.x >> b.queue_skip_shift) & 1) != 0;
     // The FIRST task of every workgroup is static — the route-first workgroups take route tasks 0, 1, 2, ... by their rank among
     // themselves, the unit-first ones units 0, 1, 2, ... — and the two counters hand out what follows: a thousand workgroups opening
     // the launch with an atomic on the same word serialise in L2 (tools/queue_timeline_probe.py: the first routes started 6-12 us into
     // the launch).
     int first_r = 0, first_u = 0, my_first = -1;          // tasks handed out statically; this workgroup's own one (-1: taken)
     const bool unit_first = skip_route;
-    if (XR_QUEUE_SKIP == 1) {
+    {
         const int sh = b.queue_skip_shift, G = (int)gridDim.x, i = (int)blockIdx.x;
         xr_queue_first(G, sh, first_r, first_u);
         my_first = sh < 0 ? i : ((i >> (sh + 1)) << sh) + (i & ((1 << sh) - 1));          // rank among the workgroups of its kind
@@ -1925,13 +1864,7 @@ __device__ __forceinline__ void xr_step_queue_body(XrBatchDev& b, const int32_t*
 #ifdef XR_TIMELINE
                 const long long t0 = XR_TL_NOW();
 #endif
-#ifdef XR_ROUTE_PRIO      // A/B: routing waves ahead of the unit writers they share a CU with (instruction arbitration)
-                __builtin_amdgcn_s_setprio(XR_ROUTE_PRIO);
-#endif
                 xr_route_dispatch<LDS_DIST, ZCH>(b, e, actions[e], smem);
-#ifdef XR_ROUTE_PRIO
-                __builtin_amdgcn_s_setprio(0);
-#endif
                 if constexpr (U8) xr_obs_head_u8(b, e, smem);
                 else xr_obs_epilogue(b, e, smem, true);
                 xr_lds_barrier();
