@@ -4,8 +4,9 @@
 // (argument checks, region / guide / state-blob validators, size arithmetic, staging buffers, error paths) can be built with
 // g++ -fsanitize=address,undefined and driven without a GPU (tests/test_host_sanitizers.py).  "Device" memory is plain malloc (so
 // the sanitizer's red zones sit around every device buffer and catch a mis-sized host-to-device copy), streams and events are dummies,
-// kernels do not exist: the launchers of stub_launch.cpp return success without computing anything.  No result of this build is ever
-// compared with anything — the parity tests run on the real library on a real GPU.
+// kernels do not exist: the launchers of stub_launch.cpp return success without computing anything.  Nothing this build computes is ever
+// compared with anything — the parity tests run on the real library on a real GPU; load_trace.cpp compares what the HOST side decides
+// and uploads at load with a recorded trace.
 #pragma once
 #define HIP_INCLUDE_HIP_HIP_RUNTIME_H        // (the real header's guard: xr_device.h declares the launchers only after it)
 #include <cstdint>
@@ -23,12 +24,14 @@ struct hipDeviceProp_t { int multiProcessorCount; size_t sharedMemPerBlock; size
 // allocations above this many bytes fail (tests shrink it to walk the out-of-memory paths); -1 = no limit
 extern "C" int64_t xr_stub_alloc_limit;
 extern "C" int64_t xr_stub_alloc_live;     // bytes currently allocated (leak check of the error paths)
+extern "C" void (*xr_stub_malloc_hook)(size_t bytes);     // optional (null: off): sees the byte count of every hipMalloc, refused ones included
 
 static inline const char* hipGetErrorString(hipError_t e) { return e == hipSuccess ? "success" : e == hipErrorOutOfMemory ? "out of memory (stub)" : "invalid value (stub)"; }
 static inline hipError_t hipGetDeviceCount(int* n) { *n = 1; return hipSuccess; }
 static inline hipError_t hipSetDevice(int d) { return d == 0 ? hipSuccess : hipErrorInvalidValue; }
 static inline hipError_t hipGetDeviceProperties(hipDeviceProp_t* p, int) { p->multiProcessorCount = 256; p->sharedMemPerBlock = 160 * 1024; p->totalGlobalMem = (size_t)1 << 30; return hipSuccess; }
 static inline hipError_t hipMalloc(void** p, size_t n) {
+    if (xr_stub_malloc_hook) xr_stub_malloc_hook(n);
     if (xr_stub_alloc_limit >= 0 && (int64_t)n > xr_stub_alloc_limit) { *p = nullptr; return hipErrorOutOfMemory; }
     // the size rides in a 16-byte header so that hipFree can keep the live-bytes count
     uint8_t* q = static_cast<uint8_t*>(malloc(n + 16));

@@ -12,10 +12,14 @@ pytestmark = pytest.mark.gpu
 
 
 def _episode_vs_oracle(regions, steps=400, **kw):
-    from oracle import xr_oracle as orc
     from xroute_env_amd.batch import RegionBatch
-    batch = RegionBatch(regions, device="cuda:0", **kw)
-    envs = [orc.OracleEnv(r) for r in regions]
+    return _play_vs_oracle(RegionBatch(regions, device="cuda:0", **kw), steps)
+
+
+def _play_vs_oracle(batch, steps=400):
+    """Every slot of a loaded batch (slot e plays region e % n_regions, as after a load) from reset to its episode end."""
+    from oracle import xr_oracle as orc
+    envs = [orc.OracleEnv(batch.regions[e % len(batch.regions)]) for e in range(batch.n_envs)]
     batch.reset()
     obs = batch.alloc_observation()
     rng = np.random.default_rng(3)
@@ -69,6 +73,27 @@ def test_path_truncation_flag_and_exact_metrics():
     reg = generate_region(9730, dims=(24, 40, 9), k_range=(6, 6))
     b = _episode_vs_oracle([reg], path_cap=3)          # recorded path truncated, metrics and hash still exact
     assert b.path_cap == 3
+
+
+def test_reload_changes_router_form():
+    """One handle, reloaded from regions whose distance field fits LDS to one that takes the HBM-scratch form of the frontier router
+    (64x48x12 = 36 864 nodes: 4 bytes a node plus the masks exceed the 160 KB of LDS) and back: every load replaces what the one before
+    decided, and each plays bit-exact."""
+    from xroute_env_amd.batch import RegionBatch
+    small = [generate_region(9750 + i, dims=(6, 6, 2), k_range=(2, 3), net_span=4) for i in range(2)]
+    large = [generate_region(9752, dims=(64, 48, 12), k_range=(4, 6), net_span=8)]
+    assert large[0].n_nets <= 6
+    batch = _play_vs_oracle(RegionBatch(small, n_envs=4, device="cuda:0"))
+    lds = [batch.route_occupancy()[1]]
+    for regions in (large, small):
+        batch.regions = list(regions)
+        with torch.cuda.device(batch.device):
+            batch._load()
+        lds.append(batch.route_occupancy()[1])
+        assert batch.n_max == (max(r.n_nodes for r in regions) + 7) // 8 * 8
+        _play_vs_oracle(batch)
+    assert lds[0] != lds[1] and lds[1] != lds[2] and lds[2] == lds[0], lds
+    assert lds[1] > 60 * 1024 > lds[0]       # the group table and work lists of the HBM-scratch form against a 72-node field
 
 
 def _desc(L, reg):

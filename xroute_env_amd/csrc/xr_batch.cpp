@@ -78,6 +78,9 @@ struct ObsValid {
     bool holds(const void* p, int64_t s, bool u) const { return ptr == p && stride == s && u8 == u; }
 };
 
+// window form of the LDS router (xr_dial3.h, WIN); x = 0: off
+struct Window { int x = 0, y = 0, nmax = 0, margin = 0, ystep = 1; uint32_t m24_yz = 0, m24_z = 0, m24_mw = 0, s24 = 0; };
+
 }  // namespace
 
 struct xr_batch {
@@ -87,9 +90,7 @@ struct xr_batch {
     int n_max = 0;          // padded max nodes per region (multiple of 8)
     int n_max_nodes = 0;    // true max N
     int n_lds = 0;          // padded distance-field words (odd strides), max over regions
-    int tracks_max = 0;
-    int lines_max = 0;
-    int bits_max = 0;       // tracks + 2 x columns
+    int lines_max = 0;      // worklist items (line, chunk of 8 nodes) of the sweep router, max over regions
     int zch = 0;            // 9 / 12 when all regions have that many layers
     int kzch = 0;           // template selector of the step kernels: zch, or -1 = bucketed-frontier router (xr_dial.h)
     int k_max = 0;
@@ -130,7 +131,7 @@ struct xr_batch {
     DevBuf<unsigned long long> total_steps;
     DevBuf<uint32_t> dist_scratch, dg_field, dg_masks, dg_touch, dg_path;
     bool dial_big = false;
-    struct { int x = 0, y = 0, nmax = 0, margin = 0, ystep = 1; uint32_t m24_yz = 0, m24_z = 0, m24_mw = 0, s24 = 0; } win;   // window form (xr_dial3.h, WIN); x = 0: off
+    Window win;
     DevBuf<unsigned short> list_scratch;
     // split observation
     DevBuf<int32_t> plan_region, plan_unit_net;
@@ -217,6 +218,643 @@ void mark_obs_valid(xr_batch* b, const void* out, int64_t stride, bool u8, int e
     for (int g = 0; g < b->n_groups; g++)
         if (env_lo <= b->group_bounds[g] && b->group_bounds[g + 1] <= env_hi)
             b->group_valid[g].set(static_cast<const char*>(out) + (b->group_bounds[g] - env_lo) * row_bytes, stride, u8);
+}
+
+
+// ---- xr_batch_load_regions, step by step: stage_regions (descriptors -> host tables + Extents), place_route (Extents -> RoutePlacement),
+// commit_load (both -> xr_batch), alloc_batch, upload_batch, fill_dev -------------------------------------------------------------------
+
+using MagicCache = std::map<uint64_t, uint64_t>;   // (divisor, limit) -> multiplier << 8 | shift (0xFF: none)
+
+// exact 24-bit magics (largest shift whose multiplier and products fit, then checked for every n below `lim`)
+bool magic24(MagicCache& cache, uint32_t dv, uint32_t lim, uint32_t& M, uint32_t& S) {
+    const uint64_t key = ((uint64_t)dv << 32) | lim;
+    auto it = cache.find(key);
+    if (it != cache.end()) { M = (uint32_t)(it->second >> 8); S = (uint32_t)(it->second & 0xFF); return S != 0xFF; }
+    bool found = false;
+    if (lim <= (1u << 24))
+        for (int sh = 31; sh >= 0 && !found; sh--) {
+            const uint64_t m = (((uint64_t)1 << sh) + dv - 1) / dv;
+            if (m >= (1u << 24) || (uint64_t)(lim > 0 ? lim - 1 : 0) * m >= ((uint64_t)1 << 32)) continue;
+            bool ok = true;
+            for (uint32_t nn = 0; nn < lim && ok; nn++) ok = (uint32_t)(((uint64_t)nn * m) >> sh) == nn / dv;
+            if (ok) { M = (uint32_t)m; S = (uint32_t)sh; found = true; }
+        }
+    cache[key] = found ? (((uint64_t)M << 8) | S) : 0xFF;
+    return found;
+}
+
+// What the router placement needs to know of the regions: maxima over them, and what holds for all of them
+struct Extents {
+    int n_max_nodes = 0, k_max = 0, x_max = 0, y_max = 0;
+    int n_lds = 0;                 // padded distance-field words (odd strides), max over regions, a multiple of 8
+    int z_min = 1 << 30, z_max = 0;
+    int64_t edge_max = 0;          // longest edge of any region graph, the via included (range checks of xr_dial3.h)
+    int64_t ext_max = 0;           // widest span of a region's tracks in x or y, DBU
+    int items_max = 0;             // worklist items (line, chunk of 8 nodes) of the sweep router, max over regions
+    bool mult4 = true, mult16 = true;   // every N % 4 / % 16 == 0
+    bool div24_all = true;         // every region has its exact 24-bit division constants
+    size_t gmask_bytes = 0;        // XR-Maze v2: bytes of the static guide masks of every (region, net) (XrRegionDev::gmask_off)
+    int n_max() const { return (n_max_nodes + 7) & ~7; }
+    int zch() const { return (z_min == z_max && (z_max == 9 || z_max == 12)) ? z_max : 0; }
+    int legal_words() const { return std::max(1, (k_max + 63) / 64); }
+};
+
+// The static tables of the regions as the device will hold them, staged on the host
+struct RegionStaging {
+    std::vector<XrRegionDev> reg;
+    std::vector<uint32_t> rec;
+    std::vector<int32_t> coords, csr, ap_node, ap_feat;
+    std::vector<int16_t> ap_pin;
+    std::vector<uint8_t> net_work;       // per (region, net): predicted route work class (launch order of route-only launches)
+    std::vector<int32_t> info;           // per (region, net): static facts for xr_dial3.h (XrBatchDev::net_info)
+    std::vector<uint8_t> ap_flags;       // per access point: bit 0 = its pin sits in a closed pocket; bits 1..2 = heuristic slot
+    std::vector<uint64_t> legal0;
+    MagicCache magics;
+    Extents ext;
+};
+
+int32_t check_desc(const xr_region_desc& d, int r) {
+    if (d.dim_x < 1 || d.dim_y < 1 || d.dim_z < 1 || d.dim_z > XR_MAX_LAYERS)
+        return fail(XR_ERR_RANGE, "region %d: dims %dx%dx%d out of range (z <= %d)", r, d.dim_x, d.dim_y, d.dim_z,
+                    XR_MAX_LAYERS);
+    if ((int64_t)d.dim_x * d.dim_y * d.dim_z > (int64_t)1 << 30) return fail(XR_ERR_RANGE, "region %d: too many nodes", r);
+    if (!d.xs_host || !d.ys_host || !d.layer_dir_host || !d.nodes_host)
+        return fail(XR_ERR_INVALID, "region %d: null array", r);
+    if (d.n_nets < 0 || d.n_nets > XR_MAX_NETS) return fail(XR_ERR_RANGE, "region %d: n_nets %d", r, d.n_nets);
+    // track coordinates within +-2^30 DBU: every difference of two of them (edge lengths, extents) then fits the kernels' int32 arithmetic
+    for (int i = 0; i < d.dim_x; i++)
+        if (d.xs_host[i] < -(1 << 30) || d.xs_host[i] > (1 << 30)) return fail(XR_ERR_RANGE, "region %d: xs[%d] = %d outside +-2^30", r, i, d.xs_host[i]);
+    for (int i = 0; i < d.dim_y; i++)
+        if (d.ys_host[i] < -(1 << 30) || d.ys_host[i] > (1 << 30)) return fail(XR_ERR_RANGE, "region %d: ys[%d] = %d outside +-2^30", r, i, d.ys_host[i]);
+    for (int i = 1; i < d.dim_x; i++)
+        if (d.xs_host[i] <= d.xs_host[i - 1]) return fail(XR_ERR_INVALID, "region %d: xs not strictly increasing", r);
+    for (int i = 1; i < d.dim_y; i++)
+        if (d.ys_host[i] <= d.ys_host[i - 1]) return fail(XR_ERR_INVALID, "region %d: ys not strictly increasing", r);
+    return XR_OK;
+}
+
+// Shape, initial metrics, layer directions, and what the frontier routers divide by: smallest edge length, flat-index decode constants.
+// One pass over the track pitches serves w_min and the longest edge / widest span of the batch
+void decode_constants(const xr_config& cfg, const xr_region_desc& d, XrRegionDev& R, MagicCache& magics, Extents& ext) {
+    const int64_t n64 = (int64_t)d.dim_x * d.dim_y * d.dim_z;
+    R.X = d.dim_x; R.Y = d.dim_y; R.Z = d.dim_z; R.N = (int)n64;
+    R.n_nets = d.n_nets;
+    R.m0[0] = d.metrics0[0]; R.m0[1] = d.metrics0[1]; R.m0[2] = d.metrics0[2];
+    R.ldir_mask = 0;
+    for (int z = 0; z < d.dim_z; z++)
+        if (d.layer_dir_host[z]) R.ldir_mask |= (1u << z);
+    int64_t e_min = cfg.via_cost, e_max = cfg.via_cost;
+    for (int i = 1; i < d.dim_x; i++) { const int64_t e = (int64_t)d.xs_host[i] - d.xs_host[i - 1]; e_min = std::min(e_min, e); e_max = std::max(e_max, e); }
+    for (int i = 1; i < d.dim_y; i++) { const int64_t e = (int64_t)d.ys_host[i] - d.ys_host[i - 1]; e_min = std::min(e_min, e); e_max = std::max(e_max, e); }
+    R.w_min = std::max(1u, (uint32_t)e_min);
+    ext.edge_max = std::max(ext.edge_max, e_max);
+    ext.ext_max = std::max<int64_t>(ext.ext_max, std::max<int64_t>((int64_t)d.xs_host[d.dim_x - 1] - d.xs_host[0], (int64_t)d.ys_host[d.dim_y - 1] - d.ys_host[0]));
+    const uint32_t yz = (uint32_t)d.dim_y * (uint32_t)d.dim_z, zz = (uint32_t)d.dim_z;
+    R.magic_yz = yz >= 2 ? (uint32_t)((1ULL << 32) / yz) : 0xFFFFFFFFu;
+    R.magic_z = zz >= 2 ? (uint32_t)((1ULL << 32) / zz) : 0xFFFFFFFFu;
+    const uint32_t mwv = (uint32_t)((n64 + 31) / 32);
+    R.magic_mw = mwv >= 2 ? (uint32_t)((1ULL << 32) / mwv) : 0xFFFFFFFFu;
+    uint32_t s_yz = 0, s_z = 0, s_mw = 0;
+    const bool okd = n64 < 65536 && magic24(magics, yz, (uint32_t)n64, R.m24_yz, s_yz) && magic24(magics, zz, yz, R.m24_z, s_z) &&
+                     magic24(magics, std::max(1u, mwv), (uint32_t)n64, R.m24_mw, s_mw);
+    R.s24 = s_yz | (s_z << 8) | (s_mw << 16) | ((okd ? 1u : 0u) << 24);
+    if (!okd) ext.div24_all = false;
+}
+
+// Per-net access-point lists (counting sort by 1-based net id; flat order inside a net) with ap_pin and ap_feat.  cnt: the region's
+// slice of net_csr (access points of net n: [cnt[n], cnt[n + 1]) from R.ap_off)
+int32_t stage_access_points(const xr_region_desc& d, int r, XrRegionDev& R, RegionStaging& s, std::vector<int32_t>& cnt) {
+    R.net_off = (int32_t)s.csr.size();
+    R.ap_off = (int32_t)s.ap_node.size();
+    cnt.assign(d.n_nets + 2, 0);
+    for (int f = 0; f < R.N; f++) {
+        const uint32_t rec = d.nodes_host[f];
+        if (XR_REC_TYPE(rec) == XR_TYPE_ACCESS) {
+            const int net1 = (int)XR_REC_NET1(rec);
+            if (net1 < 1 || net1 > d.n_nets)
+                return fail(XR_ERR_RANGE, "region %d node %d: ACCESS node with net id %d outside 1..%d", r, f, net1,
+                            d.n_nets);
+            cnt[net1 + 1]++;
+        }
+    }
+    for (int n = 1; n <= d.n_nets + 1; n++) cnt[n] += cnt[n - 1];
+    R.nlegal0 = 0;
+    for (int n = 1; n <= d.n_nets; n++) {
+        const int c = cnt[n + 1] - cnt[n];
+        if (c > XR_MAX_AP_PER_NET)
+            return fail(XR_ERR_RANGE, "region %d net %d: %d access points (max %d)", r, n, c, XR_MAX_AP_PER_NET);
+        R.nlegal0 += (c > 0);
+    }
+    s.csr.insert(s.csr.end(), cnt.begin(), cnt.end());
+    const size_t base = s.ap_node.size();
+    s.ap_node.resize(base + cnt[d.n_nets + 1]);
+    s.ap_pin.resize(base + cnt[d.n_nets + 1]);
+    std::vector<int32_t> cur(cnt.begin(), cnt.end());
+    for (int f = 0; f < R.N; f++) {
+        const uint32_t rec = d.nodes_host[f];
+        if (XR_REC_TYPE(rec) == XR_TYPE_ACCESS) {
+            const int net1 = (int)XR_REC_NET1(rec);
+            s.ap_node[base + cur[net1]] = f;
+            s.ap_pin[base + cur[net1]] = (int16_t)XR_REC_PIN1(rec);
+            cur[net1]++;
+        }
+    }
+    // per access point: does it have an in-bounds axis neighbour that is an access point of the same net, any pin
+    // (the reference's aliased direction planes, baseline/build_3Dgrid.py:125-138); static, so decided once here
+    s.ap_feat.resize(s.ap_node.size());
+    const int Yd = d.dim_y, Zd = d.dim_z, YZd = Yd * Zd;
+    auto net_of = [&](int f) -> int {
+        const uint32_t rr = d.nodes_host[f];
+        return XR_REC_TYPE(rr) == XR_TYPE_ACCESS ? (int)XR_REC_NET1(rr) : 0;
+    };
+    for (size_t i = base; i < s.ap_node.size(); i++) {
+        const int f = s.ap_node[i], n = net_of(f);
+        const int z = f % Zd, y = (f / Zd) % Yd, x = f / YZd;
+        const bool adj = (x + 1 < d.dim_x && net_of(f + YZd) == n) || (y > 0 && net_of(f - Zd) == n) || (x > 0 && net_of(f - YZd) == n) ||
+                         (y + 1 < Yd && net_of(f + Zd) == n) || (z + 1 < Zd && net_of(f + 1) == n) || (z > 0 && net_of(f - 1) == n);
+        s.ap_feat[i] = f | (adj ? (int32_t)0x80000000 : 0);
+    }
+    return XR_OK;
+}
+
+// Static facts of every net for the round-3 router: lowest pin, number of distinct pins, and which pins are ISOLATED — all
+// access points of the pin sit in a pocket closed by BLOCKAGE nodes that holds no access point of another pin of the net.
+// Such a pin can never be reached (nor reach anything): XR-Maze v1 charges one violation for it, and a router that has to
+// find that out by searching explores the whole component first.  The pocket's boundary is static, so the flood (budget 64
+// nodes; a larger pocket just counts as open, the result is the same) runs here, once, not in every route.
+void stage_net_facts(const xr_region_desc& d, const XrRegionDev& R, RegionStaging& s, const std::vector<int32_t>& cnt) {
+    s.info.resize(s.csr.size(), 0);
+    s.ap_flags.resize(s.ap_node.size(), 0);
+    const int Xd = d.dim_x, Yd = d.dim_y, Zd = d.dim_z, YZd = Yd * Zd;
+    const int32_t* ap_node = s.ap_node.data() + R.ap_off;
+    const int16_t* ap_pin = s.ap_pin.data() + R.ap_off;
+    uint8_t* ap_flags = s.ap_flags.data() + R.ap_off;
+    auto blocked = [&](int f) { return XR_REC_TYPE(d.nodes_host[f]) == XR_TYPE_BLOCKAGE; };
+    std::vector<int> seen_pins, pocket;
+    for (int n = 1; n <= d.n_nets; n++) {
+        const int lo = cnt[n], hi = cnt[n + 1];
+        if (hi <= lo) continue;
+        seen_pins.clear();
+        for (int i = lo; i < hi; i++)
+            if (std::find(seen_pins.begin(), seen_pins.end(), (int)ap_pin[i]) == seen_pins.end()) seen_pins.push_back(ap_pin[i]);
+        const int first = *std::min_element(seen_pins.begin(), seen_pins.end());
+        int n_iso = 0, src_iso = 0;
+        for (int pn : seen_pins) {
+            pocket.clear();
+            for (int i = lo; i < hi; i++) if (ap_pin[i] == pn) pocket.push_back(ap_node[i]);
+            bool open_pocket = false;
+            for (size_t k = 0; k < pocket.size() && !open_pocket; k++) {
+                const int f = pocket[k], z = f % Zd, y = (f / Zd) % Yd, x = f / YZd;
+                const bool vert = d.layer_dir_host[z] != 0;
+                const int nb[4] = {vert ? (y + 1 < Yd ? f + Zd : -1) : (x + 1 < Xd ? f + YZd : -1),
+                                   vert ? (y > 0 ? f - Zd : -1) : (x > 0 ? f - YZd : -1),
+                                   z + 1 < Zd ? f + 1 : -1, z > 0 ? f - 1 : -1};
+                for (int q = 0; q < 4; q++) {
+                    if (nb[q] < 0 || blocked(nb[q])) continue;
+                    if (std::find(pocket.begin(), pocket.end(), nb[q]) != pocket.end()) continue;
+                    if (pocket.size() >= 64) { open_pocket = true; break; }
+                    pocket.push_back(nb[q]);
+                }
+            }
+            if (open_pocket) continue;
+            bool other = false;                    // an access point of another pin of the net inside the pocket: reachable
+            for (int i = lo; i < hi && !other; i++)
+                if (ap_pin[i] != pn && std::find(pocket.begin(), pocket.end(), ap_node[i]) != pocket.end()) other = true;
+            if (other) continue;
+            for (int i = lo; i < hi; i++) if (ap_pin[i] == pn) ap_flags[i] = 1;
+            if (pn == first) src_iso = 1; else n_iso++;
+        }
+        s.info[R.net_off + n] = (first & 0x3FFF) | ((int)seen_pins.size() << 14) | (n_iso << 22) | (src_iso << 30);
+        // heuristic slot of every access point (bits 1..2 of ap_flags): pins in ascending id order, the lowest one (the first
+        // component: never a target) aside, are dealt round-robin over the three pin boxes of xr_dial3.h's heuristic
+        std::sort(seen_pins.begin(), seen_pins.end());
+        for (int i = lo; i < hi; i++) {
+            const int rank = (int)(std::find(seen_pins.begin(), seen_pins.end(), (int)ap_pin[i]) - seen_pins.begin());
+            ap_flags[i] |= (uint8_t)(((rank + 2) % 3) << 1);         // rank 1 -> slot 0, 2 -> 1, 3 -> 2, 4 -> 0 ...
+        }
+    }
+}
+
+// predicted work of routing net n: extent of its access points (DBU; a layer of span counted as half a via) times
+// (6 + pins) — the shape tools/lpt_probe.py fitted; only the ORDER of these numbers matters
+void stage_work_guess(const xr_config& cfg, const xr_region_desc& d, const XrRegionDev& R, const RegionStaging& s, const std::vector<int32_t>& cnt,
+                      std::vector<float>& work) {
+    work.resize(s.csr.size(), 0.0f);
+    const int Yd = d.dim_y, Zd = d.dim_z, YZd = Yd * Zd;
+    for (int n = 1; n <= d.n_nets; n++) {
+        const int lo = cnt[n], hi = cnt[n + 1];
+        if (hi <= lo) continue;
+        int x0 = 1 << 30, x1 = -1, y0 = 1 << 30, y1 = -1, z0 = 1 << 30, z1 = -1;
+        uint64_t pins[4] = {0, 0, 0, 0};
+        int npins = 0;
+        for (int i = lo; i < hi; i++) {
+            const int f = s.ap_node[R.ap_off + i], z = f % Zd, y = (f / Zd) % Yd, x = f / YZd;
+            x0 = std::min(x0, x); x1 = std::max(x1, x); y0 = std::min(y0, y); y1 = std::max(y1, y);
+            z0 = std::min(z0, z); z1 = std::max(z1, z);
+            const int pn = s.ap_pin[R.ap_off + i] & 255;
+            if (!((pins[pn >> 6] >> (pn & 63)) & 1)) { pins[pn >> 6] |= 1ull << (pn & 63); npins++; }
+        }
+        const double ext = (double)(d.xs_host[x1] - d.xs_host[x0]) + (double)(d.ys_host[y1] - d.ys_host[y0]) +
+                           0.5 * cfg.via_cost * (z1 - z0) + R.w_min;
+        work[R.net_off + n] = (float)(ext * (6 + npins));
+    }
+}
+
+// Worklist items of the sweep router are (line, chunk of 8 nodes) pairs: x-tracks * ceil(X/8) + y-tracks * ceil(Y/8) + columns * (1 when
+// every region has 9 / 12 layers, else ceil(Z/8)); each kind is addressed with 16 bits
+int32_t count_worklist_items(const std::vector<XrRegionDev>& reg, Extents& ext) {
+    for (size_t r = 0; r < reg.size(); r++) {
+        const XrRegionDev& R = reg[r];
+        int nv = 0;
+        for (int z = 0; z < R.Z; z++) nv += (R.ldir_mask >> z) & 1u;
+        const int chH = (R.X + 7) / 8, chV = (R.Y + 7) / 8, chC = ext.zch() ? 1 : (R.Z + 7) / 8;
+        const int64_t itH = (int64_t)(R.Z - nv) * R.Y * chH, itV = (int64_t)nv * R.X * chV, itC = (int64_t)R.X * R.Y * chC;
+        if (itH > 65536 || itV > 65536 || itC > 65536)
+            return fail(XR_ERR_RANGE, "region %d: more than 65536 worklist items of one kind (%lld / %lld / %lld)", (int)r,
+                        (long long)itH, (long long)itV, (long long)itC);
+        ext.items_max = std::max(ext.items_max, (int)(itH + itV + itC));
+    }
+    return XR_OK;
+}
+
+// Validates the descriptors and stages every static table; touches no xr_batch
+int32_t stage_regions(const xr_config& cfg, const xr_region_desc* regs, int n_regions, RegionStaging& s) {
+    Extents& ext = s.ext;
+    ext.edge_max = cfg.via_cost;
+    s.reg.resize(n_regions);
+    std::vector<int32_t> cnt;
+    std::vector<float> work;             // per (region, net): predicted route work
+    for (int r = 0; r < n_regions; r++) {
+        const xr_region_desc& d = regs[r];
+        if (const int32_t rc = check_desc(d, r)) return rc;
+        XrRegionDev& R = s.reg[r];
+        decode_constants(cfg, d, R, s.magics, ext);
+        R.xs_off = (int32_t)s.coords.size();
+        s.coords.insert(s.coords.end(), d.xs_host, d.xs_host + d.dim_x);
+        R.ys_off = (int32_t)s.coords.size();
+        s.coords.insert(s.coords.end(), d.ys_host, d.ys_host + d.dim_y);
+        R.gmask_off = (int64_t)ext.gmask_bytes;
+        R.gmask_stride = (int32_t)((((size_t)R.N + 7) / 8 + 15) & ~(size_t)15);
+        R.pad0 = 0;
+        ext.gmask_bytes += (size_t)R.gmask_stride * (size_t)std::max(d.n_nets, 0);
+        // node records, padded to a multiple of 8 elements so that int16 planes stay 16-byte aligned
+        R.node_off = (int64_t)s.rec.size();
+        s.rec.insert(s.rec.end(), d.nodes_host, d.nodes_host + R.N);
+        while (s.rec.size() % 8) s.rec.push_back(XR_TYPE_NORMAL);
+        if (const int32_t rc = stage_access_points(d, r, R, s, cnt)) return rc;
+        stage_net_facts(d, R, s, cnt);
+        stage_work_guess(cfg, d, R, s, cnt, work);
+        ext.n_max_nodes = std::max(ext.n_max_nodes, R.N);
+        ext.k_max = std::max(ext.k_max, d.n_nets);
+        ext.x_max = std::max(ext.x_max, d.dim_x);
+        ext.y_max = std::max(ext.y_max, d.dim_y);
+        if (R.N % 4) ext.mult4 = false;
+        if (R.N % 16) ext.mult16 = false;
+        // padded field: l = x*SX + y*SY + z, SY = Z|1, SX = (Y*SY)|1 (xr_route_kernel)
+        const int64_t sy = d.dim_z | 1, sx = ((int64_t)d.dim_y * sy) | 1;
+        const int64_t words = (int64_t)d.dim_x * sx;
+        if (words > ((int64_t)1 << 30)) return fail(XR_ERR_RANGE, "region %d: too many nodes", r);
+        ext.n_lds = std::max(ext.n_lds, (int)((words + 7) & ~(int64_t)7));
+        ext.z_min = std::min(ext.z_min, d.dim_z); ext.z_max = std::max(ext.z_max, d.dim_z);
+    }
+    const int legal_words = ext.legal_words();
+    // the observation kernels stage the ascending legal-id list in LDS (4 bytes per possible net)
+    if ((size_t)legal_words * 64 * 4 + (size_t)(legal_words + 1) * 4 > 60 * 1024)
+        return fail(XR_ERR_RANGE, "k_max %d too large for the observation kernel's LDS id list (max ~15000 nets)", ext.k_max);
+    s.legal0.assign((size_t)n_regions * legal_words, 0);
+    for (int r = 0; r < n_regions; r++) {
+        s.reg[r].legal0_off = (int64_t)r * legal_words;
+        const int32_t* csr = s.csr.data() + s.reg[r].net_off;
+        for (int n = 1; n <= s.reg[r].n_nets; n++)
+            if (csr[n + 1] > csr[n]) s.legal0[(size_t)r * legal_words + ((n - 1) >> 6)] |= 1ULL << ((n - 1) & 63);
+    }
+    // work classes 1..255 relative to the batch's largest prediction
+    s.net_work.assign(s.csr.size(), 0);
+    float wmax = 1.0f;
+    for (float w : work) wmax = std::max(wmax, w);
+    for (size_t i = 0; i < work.size(); i++)
+        if (work[i] > 0.0f) s.net_work[i] = (uint8_t)(1 + std::min(254, (int)(254.0f * work[i] / wmax)));
+    return count_worklist_items(s.reg, ext);
+}
+
+// Where and how the route tasks of every later launch run: one of the 12 <LDS_DIST, ZCH> instantiations and its launch shape
+struct RoutePlacement {
+    int zch = 0;              // 9 / 12 when all regions have that many layers
+    int kzch = 0;             // template selector of the step kernels: zch (sweep router), or < 0 = a frontier router (XR_ZCH_*)
+    bool lds_dist = true;     // distance field in LDS, else in HBM scratch
+    bool dial_big = false;    // the frontier router's HBM-scratch form (xr_dial.h)
+    size_t route_lds = 0;
+    int route_threads = 256;
+    bool sweep_full = false;  // auto router: the full-rewrite queue launch of a large batch takes the line-segment sweeps
+    size_t sweep_lds = 0;
+    bool stream_ok = false;   // ids + 2 bytes/node of the largest region fit the LDS of the observation stream form
+    Window win;
+    size_t lw_max = 0;        // words per item bitmask of the sweep router
+    int items_max = 0;
+    int path_cap = 0;
+};
+
+// The LDS router inside a window of the region first (xr_dial3.h, WIN; xr_config.window: > 0 = that many tracks at most — the
+// largest square window <= it that fits LDS; 0 (default) and < 0 = off: measured no faster on BASELINE config 5):
+// every region must have the same layer count and hold the window, rows of the state arrays must start on 16-byte boundaries
+// wherever a window row may start, the arithmetic limits are those of the form.  win_lds: the window's LDS when one is found
+Window choose_window(const xr_config& cfg, RegionStaging& s, size_t big_lds, size_t& win_lds) {
+    const Extents& ext = s.ext;
+    Window win;
+    const bool v2cfg = cfg.guide_cost > 0 || cfg.maze_end_iter > 1;
+    const int64_t pen_w = (int64_t)cfg.drc_cost * cfg.drc_unit;
+    if (cfg.window <= 0 || v2cfg || ext.z_min != ext.z_max || ext.edge_max + pen_w >= XR3_STEP_LIMIT) return win;
+    const int Zw = ext.z_max;
+    int ystep = 1;
+    while ((ystep * Zw) % 8) ystep *= 2;                 // rows start at y0 * Z elements: a multiple of 8 of them (16 bytes of int16)
+    bool rows_ok = true;
+    int xmin = 1 << 30, ymin = 1 << 30;
+    for (const XrRegionDev& R : s.reg) {
+        rows_ok = rows_ok && ((int64_t)R.Y * Zw) % 8 == 0;
+        xmin = std::min(xmin, R.X); ymin = std::min(ymin, R.Y);
+    }
+    for (int w = std::min(cfg.window, std::min(xmin, ymin)); w >= 8 && rows_ok; w--) {
+        if ((w * Zw) % 8) continue;                          // a chunk of 8 nodes never straddles two window rows
+        const int64_t nw = (int64_t)w * w * Zw;
+        const size_t wl = XR3_LDS_BYTES((nw + 7) & ~7, w, w);
+        if (nw >= 65536 || std::max(wl, big_lds) + 2 * kLdsStatic > kLdsLimit || (int64_t)w * ext.edge_max >= XR3_EXTENT_LIMIT) continue;
+        uint32_t myz, syz, mz, sz, mmw, smw;
+        const uint32_t mwv = (uint32_t)((nw + 31) / 32);
+        if (!magic24(s.magics, (uint32_t)(w * Zw), (uint32_t)nw, myz, syz) || !magic24(s.magics, (uint32_t)Zw, (uint32_t)std::max(w, 1) * Zw * 2, mz, sz) ||
+            !magic24(s.magics, mwv, (uint32_t)nw, mmw, smw)) continue;
+        win.x = w; win.y = w; win.nmax = (int)((nw + 7) & ~7); win.ystep = ystep;
+        // tracks kept free around the net's box (the row alignment is checked per net).  A net whose box nearly fills the window
+        // floods past its faces, fails its certificate and has paid for the attempt on top of the fallback: margins of 4 / 8 /
+        // 13 / 18 tracks of a 52-track window send 27 / 33 / 48 / 68 % of BASELINE config 5's routes to the fallback
+        // (profiles/r04_l_config5_window_form.txt)
+        win.margin = std::max(1, std::min(4, w / 8));
+        if (const char* em = getenv("XR_WINDOW_MARGIN")) win.margin = std::max(1, atoi(em));      // (A/B runs)
+        win.m24_yz = myz; win.m24_z = mz; win.m24_mw = mmw; win.s24 = syz | (sz << 8) | (smw << 16);
+        win_lds = wl;
+        break;
+    }
+    return win;
+}
+
+// The router choice, whole: which form routes, with the field where, in how much LDS, with how many threads.  Writes no xr_batch.
+//   sweep router (kzch = zch >= 0): field in LDS when field + edge-length tables + 3 item bitmasks + worklists (u16 item ids; the claim
+//     bitmask aliases them) fit, else in HBM scratch
+//   frontier router, LDS (kzch -1; -3 = round 3's form, xr_dial3.h): field + node bitmasks + edge tables in LDS — the default
+//   frontier router, HBM scratch (kzch -1, dial_big): regions too large for LDS, or force_scratch_field; may try an LDS window first
+//   -2 / -4: the instantiations of -1 / -3 with the XR-Maze v2 knobs compiled in
+int32_t place_route(const xr_config& cfg, RegionStaging& s, RoutePlacement& p) {
+    const Extents& ext = s.ext;
+    const int n_max = ext.n_max(), legal_words = ext.legal_words();
+    p.zch = ext.zch();
+    p.items_max = ext.items_max;
+    p.path_cap = cfg.path_cap > 0 ? cfg.path_cap : std::min(ext.n_max_nodes, 4096);
+    p.lw_max = ((size_t)ext.items_max + 31) / 32 + 1;
+    const size_t el_bytes = (size_t)(ext.x_max + 2 + ext.y_max + 2) * 4;
+    const size_t list_bytes = std::max(((size_t)ext.items_max * 2 + 3) & ~(size_t)3, ((size_t)ext.n_lds / 32 + 1) * 4);
+    const size_t sweep_need = (size_t)ext.n_lds * 4 + el_bytes + 3 * p.lw_max * 4 + list_bytes + 16;
+    const bool sweep_fits = sweep_need + kLdsStatic <= kLdsLimit && !cfg.force_scratch_field;
+    const size_t dial_lds = (size_t)n_max * 4 + 4 * ((size_t)n_max / 32 + 1) * 4 + el_bytes + 16;
+    // HBM-scratch form: groups of 1024 nodes must fit the LDS group table
+    const size_t big_lds = (size_t)XR_BIG_MAXG * 6 + (size_t)XR_BIG_CA * 4 + (size_t)XR_BIG_CN * 4 + 2 * (size_t)XR_BIG_CE * 8 + el_bytes + 16;
+    const bool frontier = cfg.router != XR_ROUTER_SWEEP, big_ok = ((size_t)n_max / 1024 + 2) <= 1024;
+    // workgroup size unless the caller asks: 256 with the field in LDS (4 waves; 4 workgroups per CU resident at 24x40x9), 1024 with the
+    // sweep router's field in HBM scratch (latency-bound on memory: more items in flight per env)
+    int threads = 256;
+    if (frontier && !cfg.force_scratch_field && dial_lds + kLdsStatic <= kLdsLimit) {
+        p.kzch = -1; p.lds_dist = true; p.route_lds = dial_lds;
+    } else if (frontier && big_ok) {
+        p.kzch = -1; p.lds_dist = false; p.dial_big = true; p.route_lds = big_lds;
+        // (round 2, config 5: 256 threads 4.2-4.7 ms, 512: 3.7-3.9 ms.  Round 3, same box, ms per launch at 256 / 1024 / 4096 envs: 512 threads
+        //  1.9 / 2.7 / 4.0, 1024 threads 1.8 / 2.4 / 6.5 — a wider workgroup shortens each route's rounds (wide frontiers) but only one
+        //  fits a CU: it pays while the batch is at most ~4 routes per CU, i.e. while the launch is bound by its longest routes)
+        hipDeviceProp_t prop;
+        threads = hipGetDeviceProperties(&prop, cfg.device) == hipSuccess && cfg.n_envs <= 4 * prop.multiProcessorCount ? 1024 : 512;
+        size_t win_lds = 0;
+        p.win = choose_window(cfg, s, big_lds, win_lds);
+        p.route_lds = std::max(p.route_lds, win_lds);
+    } else {
+        p.kzch = p.zch; p.lds_dist = sweep_fits; p.route_lds = sweep_fits ? sweep_need : el_bytes + 3 * p.lw_max * 4;
+        threads = sweep_fits ? 256 : 1024;
+    }
+    p.route_threads = cfg.block_threads ? cfg.block_threads : threads;
+    // round 3's LDS form (xr_dial3.h) where it applies: the field fits with its queues, node ids fit 16 bits, and its 27-bit distance
+    // arithmetic cannot wrap: every distance that exists is below XR_DIST_CAP = 0x07F00000 (spec; a candidate at or above the cap is
+    // never written), so a reached word + one edge with every penalty stays inside 32 bits while that step is < 2^20 (the x32
+    // fixed point of the word); the x32 coordinate tables and the heuristic need a region that spans < 2^25 DBU
+    const size_t d3_lds = XR3_LDS_BYTES(n_max, ext.x_max, ext.y_max);
+    const int64_t pen_max = ((int64_t)cfg.drc_cost * cfg.drc_unit) << (cfg.maze_end_iter - 1);
+    const bool range_ok = ext.edge_max + pen_max + cfg.guide_cost < XR3_STEP_LIMIT && ext.ext_max < XR3_EXTENT_LIMIT &&
+                          (int64_t)cfg.via_cost * 32 < XR3_EXTENT_LIMIT;
+    if (p.kzch == -1 && p.lds_dist && cfg.router != XR_ROUTER_DIAL_R2 && range_ok && n_max < 65536 && ext.div24_all &&
+        d3_lds + kLdsStatic <= kLdsLimit) {
+        p.kzch = -3;
+        p.route_lds = d3_lds;
+    }
+    if (cfg.guide_cost > 0 || cfg.maze_end_iter > 1) {
+        if (p.kzch >= 0)
+            return fail(XR_ERR_RANGE, "xr_batch_load_regions: XR-Maze v2 (guide_cost / maze_end_iter) needs the frontier router "
+                                      "(router != XR_ROUTER_SWEEP, regions within its limits)");
+        p.kzch = p.kzch == -3 ? -4 : -2;
+    }
+    if (p.kzch >= 0 && (cfg.router == XR_ROUTER_DIAL || cfg.router == XR_ROUTER_DIAL_R2))
+        return fail(XR_ERR_RANGE, "xr_batch_load_regions: XR_ROUTER_DIAL: the largest region (%d nodes) exceeds the frontier router's limits", n_max);
+    // the fused observation epilogue stages the ascending legal-id list in the same LDS; the flat-stream observation (any N): ids + a
+    // 16-bit feature per node
+    const size_t ids_bytes = (size_t)(legal_words * 64 + ((legal_words + 1 + 3) & ~3)) * 4;
+    const size_t stream_bytes = ids_bytes + (size_t)n_max * 2;
+    p.stream_ok = stream_bytes <= 60 * 1024;
+    const size_t obs_lds = p.stream_ok && !ext.mult4 ? stream_bytes : ids_bytes;
+    p.route_lds = std::max(p.route_lds, obs_lds);
+    // router = 0 (auto) picks per entry point the scheme measured faster for it: the frontier router everywhere, except the
+    // FULL-rewrite queue launch of a very large batch, where the line-segment sweeps are ahead (same box, DESIGN.md §5.1:
+    // 1.727-1.730 ms against 1.773-1.775 ms per 4096-env step; at 2048 envs the frontier router wins, 0.921 against 0.945-0.954 ms)
+    // (round 3, same box: synthetic 24x40x9 regions 1.681 ms with the sweeps against 1.700 ms with the frontier router; the regions
+    //  extracted from ispd18_test1 — unaligned planes, 3.5 pins per net, K up to 77: their step is bound by routing, not by the write
+    //  stream — 2.40 ms against 2.05 ms: the sweeps are only chosen for aligned planes)
+    p.sweep_lds = std::max(sweep_need, obs_lds);
+    p.sweep_full = cfg.router == 0 && (p.kzch == -1 || p.kzch == -3) && p.lds_dist && sweep_fits && cfg.block_threads == 0 &&
+                   cfg.n_envs >= 4096 && ext.mult4 && p.sweep_lds + kLdsStatic <= kLdsLimit;
+    if (p.route_lds + kLdsStatic > kLdsLimit)
+        return fail(XR_ERR_RANGE, "route kernel needs %zu bytes of LDS (line bitmasks of the largest region)", p.route_lds);
+    return XR_OK;
+}
+
+// Every range check has passed: what the regions are and where they route becomes the batch's
+void commit_load(xr_batch* b, int n_regions, const RegionStaging& s, const RoutePlacement& p) {
+    const Extents& ext = s.ext;
+    b->n_regions = n_regions;
+    b->n_max_nodes = ext.n_max_nodes;
+    b->n_max = ext.n_max();
+    b->n_lds = ext.n_lds;
+    b->lines_max = p.items_max;
+    b->k_max = ext.k_max;
+    b->legal_words = ext.legal_words();
+    b->x_max = ext.x_max;
+    b->y_max = ext.y_max;
+    b->all_n_mult4 = ext.mult4;
+    b->all_n_mult16 = ext.mult16;
+    b->zch = p.zch; b->kzch = p.kzch; b->lds_dist = p.lds_dist; b->dial_big = p.dial_big;
+    b->route_lds = p.route_lds; b->route_threads = p.route_threads;
+    b->sweep_full = p.sweep_full; b->sweep_lds = p.sweep_lds; b->stream_ok = p.stream_ok;
+    b->win = p.win;
+    b->path_cap = p.path_cap;
+    b->h_net_off.resize(n_regions); b->h_n_nets.resize(n_regions); b->h_dims.resize(3 * (size_t)n_regions);
+    for (int r = 0; r < n_regions; r++) {
+        b->h_net_off[r] = s.reg[r].net_off; b->h_n_nets[r] = s.reg[r].n_nets;
+        b->h_dims[3 * r] = s.reg[r].X; b->h_dims[3 * r + 1] = s.reg[r].Y; b->h_dims[3 * r + 2] = s.reg[r].Z;
+    }
+    b->h_csr_size = s.csr.size();
+    b->guide_mask_bytes = ext.gmask_bytes;
+}
+
+int32_t alloc_batch(xr_batch* b, const RegionStaging& s) {
+    const size_t B = (size_t)b->cfg.n_envs, n_rec = s.rec.size(), n_csr = s.csr.size(), n_ap = std::max<size_t>(1, s.ap_node.size());
+#define XR_ALLOC(buf, count)                                                                        \
+    do {                                                                                            \
+        hipError_t _e = (buf).alloc(count);                                                         \
+        if (_e != hipSuccess)                                                                       \
+            return fail(XR_ERR_NOMEM, "hipMalloc of %zu bytes failed: %s", (size_t)(count) * sizeof(*(buf).p), \
+                        hipGetErrorString(_e));                                                     \
+    } while (0)
+    XR_ALLOC(b->regions, s.reg.size());
+    XR_ALLOC(b->rg_rec, n_rec);
+    XR_ALLOC(b->rg_node_net, n_rec);
+    XR_ALLOC(b->rg_owner0, n_rec);
+    XR_ALLOC(b->coords, s.coords.size());
+    XR_ALLOC(b->net_csr, n_csr);
+    XR_ALLOC(b->ap_node, n_ap);
+    XR_ALLOC(b->ap_pin, n_ap);
+    XR_ALLOC(b->ap_feat, n_ap);
+    XR_ALLOC(b->legal0, s.legal0.size());
+    XR_ALLOC(b->env_region, B);
+    XR_ALLOC(b->env_replay, B);
+    XR_ALLOC(b->nlegal, B);
+    XR_ALLOC(b->cum, B * 3);
+    XR_ALLOC(b->delta, B * 3);
+    XR_ALLOC(b->status, B);
+    XR_ALLOC(b->path, B * b->path_cap);
+    XR_ALLOC(b->path_len, B);
+    XR_ALLOC(b->sweeps, B);
+    XR_ALLOC(b->touched, B);
+    XR_ALLOC(b->route_order, B);
+    XR_ALLOC(b->net_work, n_csr);
+    XR_ALLOC(b->net_meas, n_csr);
+    XR_ALLOC(b->net_info, n_csr);
+    XR_ALLOC(b->ap_flags, n_ap);
+    XR_ALLOC(b->owner, B * b->n_max);
+    XR_ALLOC(b->legal, B * b->legal_words);
+    XR_ALLOC(b->hash, B);
+    XR_ALLOC(b->reward, B);
+    XR_ALLOC(b->records, B);
+    XR_ALLOC(b->done, B);
+    XR_ALLOC(b->env_steps, B);
+    XR_ALLOC(b->total_steps, 1);
+    XR_ALLOC(b->phase_cycles, B * 8);
+    XR_ALLOC(b->plan_region, B);
+    XR_ALLOC(b->queue, 8);
+    XR_ALLOC(b->group_queue, (size_t)XR_MAX_GROUPS * 8);
+    XR_ALLOC(b->plan_units, B * std::max(1, b->k_max));
+    XR_ALLOC(b->plan_unit_net, B * std::max(1, b->k_max));
+    if (b->dial_big) {
+        const size_t mwg = (size_t)b->n_max / 32 + 1;
+        XR_ALLOC(b->dg_field, B * b->n_max);
+        XR_ALLOC(b->dg_masks, B * 2 * mwg);
+        XR_ALLOC(b->dg_touch, B * b->n_max);
+        XR_ALLOC(b->dg_path, B * b->n_max * 2);
+    } else if (!b->lds_dist) {
+        XR_ALLOC(b->dist_scratch, B * b->n_lds);
+        XR_ALLOC(b->cls_scratch, B * b->n_lds);
+        XR_ALLOC(b->list_scratch, B * b->lines_max);
+    }
+#undef XR_ALLOC
+    return XR_OK;
+}
+
+// Static tables up, env state to its start, node records ingested.  Returns after the stream has drained: the staging may die
+int32_t upload_batch(xr_batch* b, const RegionStaging& s, hipStream_t st) {
+    const size_t B = (size_t)b->cfg.n_envs;
+    XR_HIP(hipMemcpyAsync(b->regions.p, s.reg.data(), s.reg.size() * sizeof(XrRegionDev), hipMemcpyHostToDevice, st));
+    XR_HIP(hipMemcpyAsync(b->rg_rec.p, s.rec.data(), s.rec.size() * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+    XR_HIP(hipMemcpyAsync(b->coords.p, s.coords.data(), s.coords.size() * sizeof(int32_t), hipMemcpyHostToDevice, st));
+    XR_HIP(hipMemcpyAsync(b->net_csr.p, s.csr.data(), s.csr.size() * sizeof(int32_t), hipMemcpyHostToDevice, st));
+    XR_HIP(hipMemcpyAsync(b->net_work.p, s.net_work.data(), s.net_work.size(), hipMemcpyHostToDevice, st));
+    XR_HIP(hipMemsetAsync(b->net_meas.p, 0, s.csr.size(), st));                  // nothing measured yet: the launch orders use the geometric guess
+    XR_HIP(hipMemcpyAsync(b->net_info.p, s.info.data(), s.info.size() * sizeof(int32_t), hipMemcpyHostToDevice, st));
+    if (!s.ap_flags.empty()) XR_HIP(hipMemcpyAsync(b->ap_flags.p, s.ap_flags.data(), s.ap_flags.size(), hipMemcpyHostToDevice, st));
+    if (!s.ap_node.empty()) {
+        XR_HIP(hipMemcpyAsync(b->ap_node.p, s.ap_node.data(), s.ap_node.size() * sizeof(int32_t), hipMemcpyHostToDevice, st));
+        XR_HIP(hipMemcpyAsync(b->ap_pin.p, s.ap_pin.data(), s.ap_pin.size() * sizeof(int16_t), hipMemcpyHostToDevice, st));
+        XR_HIP(hipMemcpyAsync(b->ap_feat.p, s.ap_feat.data(), s.ap_feat.size() * sizeof(int32_t), hipMemcpyHostToDevice, st));
+    }
+    XR_HIP(hipMemcpyAsync(b->legal0.p, s.legal0.data(), s.legal0.size() * sizeof(uint64_t), hipMemcpyHostToDevice, st));
+    std::vector<int32_t> henv(B);
+    for (size_t e = 0; e < B; e++) henv[e] = (int32_t)(e % s.reg.size());
+    XR_HIP(hipMemcpyAsync(b->env_region.p, henv.data(), B * sizeof(int32_t), hipMemcpyHostToDevice, st));
+    XR_HIP(hipMemsetAsync(b->env_replay.p, 0, B * sizeof(int32_t), st));
+    XR_HIP(hipMemsetAsync(b->env_steps.p, 0, B * sizeof(int64_t), st));
+    XR_HIP(hipMemsetAsync(b->total_steps.p, 0, sizeof(unsigned long long), st));
+    XR_HIP(hipMemsetAsync(b->phase_cycles.p, 0, B * 8 * sizeof(long long), st));
+    XR_HIP(hipMemsetAsync(b->nlegal.p, 0, B * sizeof(int32_t), st));
+    XR_HIP(hipMemsetAsync(b->touched.p, 0, B * sizeof(int32_t), st));
+    XR_HIP(hipMemsetAsync(b->route_order.p, 0, B * sizeof(int32_t), st));
+    XR_HIP(hipMemsetAsync(b->records.p, 0, B * sizeof(XrStepRecord), st));
+    XR_HIP(hipMemsetAsync(b->owner.p, 0, B * b->n_max * sizeof(int16_t), st));
+    XR_HIP(hipMemsetAsync(b->path.p, 0, B * b->path_cap * sizeof(int32_t), st));
+    if (b->dial_big) {      // the persistent CLEAN state of the scratch: field CLEAN, no open bits, word minima = infinity
+        const size_t mwg = (size_t)b->n_max / 32 + 1;
+        XR_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(b->dg_field.p), (int)0xFFFFFFFEu, B * b->n_max, st));
+        for (size_t e = 0; e < B; e++) {
+            XR_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(b->dg_masks.p + e * 2 * mwg), 0, mwg, st));
+            XR_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(b->dg_masks.p + e * 2 * mwg + mwg), (int)0xFFFFFFFFu, mwg, st));
+        }
+    }
+    std::vector<uint64_t> hhash(B, 0xcbf29ce484222325ULL);
+    XR_HIP(hipMemcpyAsync(b->hash.p, hhash.data(), B * sizeof(uint64_t), hipMemcpyHostToDevice, st));
+    XR_HIP(hipMemsetAsync(b->queue.p, 0, 8 * sizeof(uint32_t), st));       // both banks start clean; from then on every plan zeroes the other bank
+    b->queue_bank = 0; b->queue_last = b->queue.p;
+    XR_HIP(hipMemsetAsync(b->group_queue.p, 0, (size_t)XR_MAX_GROUPS * 8 * sizeof(uint32_t), st));     // (the partition itself survives a reload)
+    for (int g = 0; g < XR_MAX_GROUPS; g++) b->group_bank[g] = 0;
+    XR_HIP(xr_launch_ingest(b->rg_rec.p, b->rg_node_net.p, b->rg_owner0.p, (int64_t)s.rec.size(), st));
+    XR_HIP(hipStreamSynchronize(st));   // host staging vectors die here
+    return XR_OK;
+}
+
+// The kernels' view of the batch (zeroed by the caller): every buffer, size and knob
+void fill_dev(xr_batch* b, const RoutePlacement& p) {
+    XrBatchDev& d = b->dev;
+    d.regions = b->regions.p; d.rg_rec = b->rg_rec.p; d.rg_node_net = b->rg_node_net.p; d.rg_owner0 = b->rg_owner0.p;
+    d.coords = b->coords.p; d.net_csr = b->net_csr.p; d.ap_node = b->ap_node.p; d.ap_pin = b->ap_pin.p; d.ap_feat = b->ap_feat.p; d.net_work = b->net_work.p; d.net_info = b->net_info.p;
+    d.ap_flags = b->ap_flags.p; d.legal0 = b->legal0.p; d.guide_csr = nullptr; d.guide_box = nullptr;
+    {   // measured launch order (round 5): on unless XR_NO_MEASURED_ORDER=1 (A/B switch; results never depend on the order)
+        const char* off = getenv("XR_NO_MEASURED_ORDER");
+        d.net_meas = (off && off[0] == '1') ? nullptr : b->net_meas.p;
+        const char* ht = getenv("XR_HEAVY_CLASS"); const char* hm = getenv("XR_HEAVY_MULT");       // (experiment switches)
+        d.heavy_class = std::min(255, std::max(0, ht ? atoi(ht) : 0)); d.heavy_mult = std::min(16, std::max(1, hm ? atoi(hm) : 2));   // (a width of 0 would spin a route to its round cap)
+        d.meas_shift = b->lds_dist ? 13 : 15;       // class unit: 8 k cycles (LDS form: a route is 0.1-1.5 M cycles), 32 k (HBM-scratch form: up to 6 M)
+    }
+    d.n_regions = b->n_regions; d.n_envs = b->cfg.n_envs; d.n_max = b->n_max; d.n_lds = b->n_lds; d.lw_max = (int)p.lw_max; d.lines_max = p.items_max;
+    d.x_max = b->x_max; d.y_max = b->y_max; d.legal_words = b->legal_words; d.path_cap = b->path_cap;
+    d.env_region = b->env_region.p; d.env_replay = b->env_replay.p; d.owner = b->owner.p; d.legal = b->legal.p;
+    d.nlegal = b->nlegal.p; d.cum = b->cum.p; d.delta = b->delta.p; d.reward = b->reward.p; d.done = b->done.p;
+    d.status = b->status.p; d.path = b->path.p; d.path_len = b->path_len.p; d.hash = b->hash.p;
+    d.env_steps = b->env_steps.p; d.total_steps = b->total_steps.p; d.sweeps = b->sweeps.p; d.touched = b->touched.p; d.records = b->records.p;
+    // (round 3's LDS form, same-box A/B profiles/r03_l_ab_bucket_width.txt: 12 against 8 — route-only 512 / 4096 envs 0.211 / 0.381 ->
+    //  0.203 / 0.372 ms, 512-env step 0.315 -> 0.306 ms; 16 the same, 24 slower; round 2's form and the HBM-scratch form keep 8)
+    d.dial_mult = b->cfg.dial_mult > 0 ? b->cfg.dial_mult : ((b->kzch == -3 || b->kzch == -4) ? 12 : 8);
+    d.dial_mult_big = b->cfg.dial_mult > 0 ? b->cfg.dial_mult : 8;
+    d.round_cap = b->cfg.debug_round_cap;
+    d.win_x = b->win.x; d.win_y = b->win.y; d.win_nmax = b->win.nmax; d.win_margin = b->win.margin; d.win_ystep = b->win.ystep;
+    d.win_m24_yz = b->win.m24_yz; d.win_m24_z = b->win.m24_z; d.win_m24_mw = b->win.m24_mw; d.win_s24 = b->win.s24;
+    d.guide_cost = b->cfg.guide_cost; d.guide_margin = b->cfg.guide_margin; d.maze_end_iter = b->cfg.maze_end_iter;
+    d.dg_field = b->dg_field.p; d.dg_masks = b->dg_masks.p; d.dg_touch = b->dg_touch.p; d.dg_path = b->dg_path.p;
+    d.dist_scratch = b->dist_scratch.p; d.cls_scratch = b->cls_scratch.p; d.list_scratch = b->list_scratch.p; d.phase_cycles = b->phase_cycles.p;
+    d.obs_split_pm = 1000;
+    d.obs_lds_bytes = (int32_t)std::min<size_t>(b->route_lds, 1u << 30);      // (every launch of the default router carries route_lds)
+    d.plan_region = b->plan_region.p; d.plan_units = b->plan_units.p; d.plan_unit_net = b->plan_unit_net.p; d.queue = b->queue.p; d.queue_quota_pm = 750;
+    d.via_cost = b->cfg.via_cost; d.pen_cost = b->cfg.drc_cost * b->cfg.drc_unit;
+    d.max_route_count = b->cfg.max_route_count; d.auto_reset = b->cfg.auto_reset;
+    d.w_violation = b->cfg.w_violation; d.w_via = b->cfg.w_via; d.w_wirelength = b->cfg.w_wirelength;
 }
 
 }  // namespace
@@ -318,7 +956,6 @@ int32_t xr_batch_load_regions(xr_batch* b, const xr_region_desc* regs, int32_t n
     if (!b || !regs || n_regions < 1) return fail(XR_ERR_INVALID, "xr_batch_load_regions: bad argument");
     XR_HIP(hipSetDevice(b->cfg.device));
     hipStream_t st = static_cast<hipStream_t>(stream);
-    const int B = b->cfg.n_envs;
     // a reload invalidates the batch until it has completed: a failure midway must not leave `loaded` set over
     // freed or partly reallocated device buffers
     b->loaded = false;
@@ -330,561 +967,15 @@ int32_t xr_batch_load_regions(xr_batch* b, const xr_region_desc* regs, int32_t n
     b->guide_csr.release(); b->guide_box.release(); b->guide_mask.release(); b->guide_mask_bytes = 0;        // guides belong to the regions they were loaded for
     memset(&b->dev, 0, sizeof(b->dev));
 
-    std::vector<XrRegionDev> hreg(n_regions);
-    std::vector<uint32_t> hrec;
-    std::vector<int32_t> hcoords, hcsr, hap_node, hap_feat;
-    std::vector<int16_t> hap_pin;
-    std::vector<float> hwork;            // per (region, net): predicted route work (launch order of route-only launches)
-    std::vector<int32_t> hinfo;          // per (region, net): static facts for xr_dial3.h (XrBatchDev::net_info)
-    std::vector<uint8_t> hap_flags;      // per access point: bit 0 = its pin sits in a closed pocket
-    int64_t edge_max = b->cfg.via_cost;  // longest edge of any region graph (range checks of xr_dial3.h)
-    int64_t ext_max = 0;                 // widest span of a region's tracks in x or y, DBU
-    std::map<uint64_t, uint64_t> magic_cache;   // (divisor, limit) -> multiplier << 8 | shift (0xFF: none)
-    bool div24_all = true;               // every region has its exact 24-bit division constants
-    // exact 24-bit magics (largest shift whose multiplier and products fit, then checked for every n below `lim`)
-    auto magic24 = [&](uint32_t dv, uint32_t lim, uint32_t& M, uint32_t& S) -> bool {
-        const uint64_t key = ((uint64_t)dv << 32) | lim;
-        auto it = magic_cache.find(key);
-        if (it != magic_cache.end()) { M = (uint32_t)(it->second >> 8); S = (uint32_t)(it->second & 0xFF); return S != 0xFF; }
-        bool found = false;
-        if (lim <= (1u << 24))
-            for (int sh = 31; sh >= 0 && !found; sh--) {
-                const uint64_t m = (((uint64_t)1 << sh) + dv - 1) / dv;
-                if (m >= (1u << 24) || (uint64_t)(lim > 0 ? lim - 1 : 0) * m >= ((uint64_t)1 << 32)) continue;
-                bool ok = true;
-                for (uint32_t nn = 0; nn < lim && ok; nn++) ok = (uint32_t)(((uint64_t)nn * m) >> sh) == nn / dv;
-                if (ok) { M = (uint32_t)m; S = (uint32_t)sh; found = true; }
-            }
-        magic_cache[key] = found ? (((uint64_t)M << 8) | S) : 0xFF;
-        return found;
-    };
-    int n_max_nodes = 0, k_max = 0, x_max = 0, y_max = 0, n_lds = 0, tracks_max = 0, lines_max = 0, bits_max = 0, z_min = 1 << 30, z_max = 0, ncol_max = 0;
-    size_t gmask_bytes = 0;        // XR-Maze v2: bytes of the static guide masks of every (region, net) (XrRegionDev::gmask_off)
-    bool mult4 = true, mult16 = true;
-    for (int r = 0; r < n_regions; r++) {
-        const xr_region_desc& d = regs[r];
-        if (d.dim_x < 1 || d.dim_y < 1 || d.dim_z < 1 || d.dim_z > XR_MAX_LAYERS)
-            return fail(XR_ERR_RANGE, "region %d: dims %dx%dx%d out of range (z <= %d)", r, d.dim_x, d.dim_y, d.dim_z,
-                        XR_MAX_LAYERS);
-        const int64_t n64 = (int64_t)d.dim_x * d.dim_y * d.dim_z;
-        if (n64 > (int64_t)1 << 30) return fail(XR_ERR_RANGE, "region %d: too many nodes", r);
-        if (!d.xs_host || !d.ys_host || !d.layer_dir_host || !d.nodes_host)
-            return fail(XR_ERR_INVALID, "region %d: null array", r);
-        if (d.n_nets < 0 || d.n_nets > XR_MAX_NETS) return fail(XR_ERR_RANGE, "region %d: n_nets %d", r, d.n_nets);
-        // track coordinates within +-2^30 DBU: every difference of two of them (edge lengths, extents) then fits the kernels' int32 arithmetic
-        for (int i = 0; i < d.dim_x; i++)
-            if (d.xs_host[i] < -(1 << 30) || d.xs_host[i] > (1 << 30)) return fail(XR_ERR_RANGE, "region %d: xs[%d] = %d outside +-2^30", r, i, d.xs_host[i]);
-        for (int i = 0; i < d.dim_y; i++)
-            if (d.ys_host[i] < -(1 << 30) || d.ys_host[i] > (1 << 30)) return fail(XR_ERR_RANGE, "region %d: ys[%d] = %d outside +-2^30", r, i, d.ys_host[i]);
-        for (int i = 1; i < d.dim_x; i++)
-            if (d.xs_host[i] <= d.xs_host[i - 1]) return fail(XR_ERR_INVALID, "region %d: xs not strictly increasing", r);
-        for (int i = 1; i < d.dim_y; i++)
-            if (d.ys_host[i] <= d.ys_host[i - 1]) return fail(XR_ERR_INVALID, "region %d: ys not strictly increasing", r);
-        const int N = (int)n64;
-        XrRegionDev& R = hreg[r];
-        R.X = d.dim_x; R.Y = d.dim_y; R.Z = d.dim_z; R.N = N;
-        R.n_nets = d.n_nets;
-        R.m0[0] = d.metrics0[0]; R.m0[1] = d.metrics0[1]; R.m0[2] = d.metrics0[2];
-        R.ldir_mask = 0;
-        for (int z = 0; z < d.dim_z; z++)
-            if (d.layer_dir_host[z]) R.ldir_mask |= (1u << z);
-        {   // bucketed-frontier router: smallest edge length, flat-index decode constants
-            uint32_t wmin = (uint32_t)b->cfg.via_cost;
-            for (int i = 1; i < d.dim_x; i++) wmin = std::min(wmin, (uint32_t)(d.xs_host[i] - d.xs_host[i - 1]));
-            for (int i = 1; i < d.dim_y; i++) wmin = std::min(wmin, (uint32_t)(d.ys_host[i] - d.ys_host[i - 1]));
-            R.w_min = std::max(1u, wmin);
-            const uint32_t yz = (uint32_t)d.dim_y * (uint32_t)d.dim_z, zz = (uint32_t)d.dim_z;
-            R.magic_yz = yz >= 2 ? (uint32_t)((1ULL << 32) / yz) : 0xFFFFFFFFu;
-            R.magic_z = zz >= 2 ? (uint32_t)((1ULL << 32) / zz) : 0xFFFFFFFFu;
-            const uint32_t mwv = (uint32_t)((n64 + 31) / 32);
-            R.magic_mw = mwv >= 2 ? (uint32_t)((1ULL << 32) / mwv) : 0xFFFFFFFFu;
-            uint32_t s_yz = 0, s_z = 0, s_mw = 0;
-            const bool okd = n64 < 65536 && magic24(yz, (uint32_t)n64, R.m24_yz, s_yz) && magic24(zz, yz, R.m24_z, s_z) &&
-                             magic24(std::max(1u, mwv), (uint32_t)n64, R.m24_mw, s_mw);
-            R.s24 = s_yz | (s_z << 8) | (s_mw << 16) | ((okd ? 1u : 0u) << 24);
-            if (!okd) div24_all = false;
-        }
-        R.xs_off = (int32_t)hcoords.size();
-        hcoords.insert(hcoords.end(), d.xs_host, d.xs_host + d.dim_x);
-        R.ys_off = (int32_t)hcoords.size();
-        hcoords.insert(hcoords.end(), d.ys_host, d.ys_host + d.dim_y);
-        // node records, padded to a multiple of 8 elements so that int16 planes stay 16-byte aligned
-        R.gmask_off = (int64_t)gmask_bytes;
-        R.gmask_stride = (int32_t)((((size_t)N + 7) / 8 + 15) & ~(size_t)15);
-        R.pad0 = 0;
-        gmask_bytes += (size_t)R.gmask_stride * (size_t)std::max(d.n_nets, 0);
-        R.node_off = (int64_t)hrec.size();
-        hrec.insert(hrec.end(), d.nodes_host, d.nodes_host + N);
-        while (hrec.size() % 8) hrec.push_back(XR_TYPE_NORMAL);
-        // per-net access-point lists (counting sort by 1-based net id; flat order inside a net)
-        R.net_off = (int32_t)hcsr.size();
-        R.ap_off = (int32_t)hap_node.size();
-        std::vector<int32_t> cnt(d.n_nets + 2, 0);
-        for (int f = 0; f < N; f++) {
-            const uint32_t rec = d.nodes_host[f];
-            if (XR_REC_TYPE(rec) == XR_TYPE_ACCESS) {
-                const int net1 = (int)XR_REC_NET1(rec);
-                if (net1 < 1 || net1 > d.n_nets)
-                    return fail(XR_ERR_RANGE, "region %d node %d: ACCESS node with net id %d outside 1..%d", r, f, net1,
-                                d.n_nets);
-                cnt[net1 + 1]++;
-            }
-        }
-        for (int n = 1; n <= d.n_nets + 1; n++) cnt[n] += cnt[n - 1];
-        R.nlegal0 = 0;
-        for (int n = 1; n <= d.n_nets; n++) {
-            const int c = cnt[n + 1] - cnt[n];
-            if (c > XR_MAX_AP_PER_NET)
-                return fail(XR_ERR_RANGE, "region %d net %d: %d access points (max %d)", r, n, c, XR_MAX_AP_PER_NET);
-            R.nlegal0 += (c > 0);
-        }
-        hcsr.insert(hcsr.end(), cnt.begin(), cnt.end());
-        const size_t base = hap_node.size();
-        hap_node.resize(base + cnt[d.n_nets + 1]);
-        hap_pin.resize(base + cnt[d.n_nets + 1]);
-        std::vector<int32_t> cur(cnt.begin(), cnt.end());
-        for (int f = 0; f < N; f++) {
-            const uint32_t rec = d.nodes_host[f];
-            if (XR_REC_TYPE(rec) == XR_TYPE_ACCESS) {
-                const int net1 = (int)XR_REC_NET1(rec);
-                hap_node[base + cur[net1]] = f;
-                hap_pin[base + cur[net1]] = (int16_t)XR_REC_PIN1(rec);
-                cur[net1]++;
-            }
-        }
-        // per access point: does it have an in-bounds axis neighbour that is an access point of the same net, any pin
-        // (the reference's aliased direction planes, baseline/build_3Dgrid.py:125-138); static, so decided once here
-        hap_feat.resize(hap_node.size());
-        {
-            const int Yd = d.dim_y, Zd = d.dim_z, YZd = Yd * Zd;
-            auto net_of = [&](int f) -> int {
-                const uint32_t rr = d.nodes_host[f];
-                return XR_REC_TYPE(rr) == XR_TYPE_ACCESS ? (int)XR_REC_NET1(rr) : 0;
-            };
-            for (size_t i = base; i < hap_node.size(); i++) {
-                const int f = hap_node[i], n = net_of(f);
-                const int z = f % Zd, y = (f / Zd) % Yd, x = f / YZd;
-                const bool adj = (x + 1 < d.dim_x && net_of(f + YZd) == n) || (y > 0 && net_of(f - Zd) == n) || (x > 0 && net_of(f - YZd) == n) ||
-                                 (y + 1 < Yd && net_of(f + Zd) == n) || (z + 1 < Zd && net_of(f + 1) == n) || (z > 0 && net_of(f - 1) == n);
-                hap_feat[i] = f | (adj ? (int32_t)0x80000000 : 0);
-            }
-        }
-        // Static facts of every net for the round-3 router: lowest pin, number of distinct pins, and which pins are ISOLATED — all
-        // access points of the pin sit in a pocket closed by BLOCKAGE nodes that holds no access point of another pin of the net.
-        // Such a pin can never be reached (nor reach anything): XR-Maze v1 charges one violation for it, and a router that has to
-        // find that out by searching explores the whole component first.  The pocket's boundary is static, so the flood (budget 64
-        // nodes; a larger pocket just counts as open, the result is the same) runs here, once, not in every route.
-        hinfo.resize(hcsr.size(), 0);
-        hap_flags.resize(hap_node.size(), 0);
-        {
-            const int Xd = d.dim_x, Yd = d.dim_y, Zd = d.dim_z, YZd = Yd * Zd;
-            for (int i = 1; i < Xd; i++) edge_max = std::max<int64_t>(edge_max, d.xs_host[i] - d.xs_host[i - 1]);
-            for (int i = 1; i < Yd; i++) edge_max = std::max<int64_t>(edge_max, d.ys_host[i] - d.ys_host[i - 1]);
-            ext_max = std::max<int64_t>(ext_max, std::max<int64_t>((int64_t)d.xs_host[Xd - 1] - d.xs_host[0], (int64_t)d.ys_host[Yd - 1] - d.ys_host[0]));
-            auto blocked = [&](int f) { return XR_REC_TYPE(d.nodes_host[f]) == XR_TYPE_BLOCKAGE; };
-            std::vector<int> seen_pins, pocket;
-            for (int n = 1; n <= d.n_nets; n++) {
-                const int lo = cnt[n], hi = cnt[n + 1];
-                if (hi <= lo) continue;
-                seen_pins.clear();
-                for (int i = lo; i < hi; i++) {
-                    const int pn = hap_pin[base + i];
-                    if (std::find(seen_pins.begin(), seen_pins.end(), pn) == seen_pins.end()) seen_pins.push_back(pn);
-                }
-                const int first = *std::min_element(seen_pins.begin(), seen_pins.end());
-                int n_iso = 0, src_iso = 0;
-                for (int pn : seen_pins) {
-                    pocket.clear();
-                    for (int i = lo; i < hi; i++) if (hap_pin[base + i] == pn) pocket.push_back(hap_node[base + i]);
-                    bool open_pocket = false;
-                    for (size_t k = 0; k < pocket.size() && !open_pocket; k++) {
-                        const int f = pocket[k], z = f % Zd, y = (f / Zd) % Yd, x = f / YZd;
-                        const bool vert = d.layer_dir_host[z] != 0;
-                        const int nb[4] = {vert ? (y + 1 < Yd ? f + Zd : -1) : (x + 1 < Xd ? f + YZd : -1),
-                                           vert ? (y > 0 ? f - Zd : -1) : (x > 0 ? f - YZd : -1),
-                                           z + 1 < Zd ? f + 1 : -1, z > 0 ? f - 1 : -1};
-                        for (int q = 0; q < 4; q++) {
-                            if (nb[q] < 0 || blocked(nb[q])) continue;
-                            if (std::find(pocket.begin(), pocket.end(), nb[q]) != pocket.end()) continue;
-                            if (pocket.size() >= 64) { open_pocket = true; break; }
-                            pocket.push_back(nb[q]);
-                        }
-                    }
-                    if (open_pocket) continue;
-                    bool other = false;                    // an access point of another pin of the net inside the pocket: reachable
-                    for (int i = lo; i < hi && !other; i++)
-                        if (hap_pin[base + i] != pn && std::find(pocket.begin(), pocket.end(), hap_node[base + i]) != pocket.end()) other = true;
-                    if (other) continue;
-                    for (int i = lo; i < hi; i++) if (hap_pin[base + i] == pn) hap_flags[base + i] = 1;
-                    if (pn == first) src_iso = 1; else n_iso++;
-                }
-                hinfo[R.net_off + n] = (first & 0x3FFF) | ((int)seen_pins.size() << 14) | (n_iso << 22) | (src_iso << 30);
-                // heuristic slot of every access point (bits 1..2 of ap_flags): pins in ascending id order, the lowest one (the first
-                // component: never a target) aside, are dealt round-robin over the three pin boxes of xr_dial3.h's heuristic
-                std::sort(seen_pins.begin(), seen_pins.end());
-                for (int i = lo; i < hi; i++) {
-                    const int rank = (int)(std::find(seen_pins.begin(), seen_pins.end(), (int)hap_pin[base + i]) - seen_pins.begin());
-                    hap_flags[base + i] |= (uint8_t)(((rank + 2) % 3) << 1);         // rank 1 -> slot 0, 2 -> 1, 3 -> 2, 4 -> 0 ...
-                }
-            }
-        }
-        // predicted work of routing net n: extent of its access points (DBU; a layer of span counted as half a via) times
-        // (6 + pins) — the shape tools/lpt_probe.py fitted; only the ORDER of these numbers matters
-        hwork.resize(hcsr.size(), 0.0f);
-        {
-            const int Yd = d.dim_y, Zd = d.dim_z, YZd = Yd * Zd;
-            for (int n = 1; n <= d.n_nets; n++) {
-                const int lo = cnt[n], hi = cnt[n + 1];
-                if (hi <= lo) continue;
-                int x0 = 1 << 30, x1 = -1, y0 = 1 << 30, y1 = -1, z0 = 1 << 30, z1 = -1;
-                uint64_t pins[4] = {0, 0, 0, 0};
-                int npins = 0;
-                for (int i = lo; i < hi; i++) {
-                    const int f = hap_node[base + i], z = f % Zd, y = (f / Zd) % Yd, x = f / YZd;
-                    x0 = std::min(x0, x); x1 = std::max(x1, x); y0 = std::min(y0, y); y1 = std::max(y1, y);
-                    z0 = std::min(z0, z); z1 = std::max(z1, z);
-                    const int pn = hap_pin[base + i] & 255;
-                    if (!((pins[pn >> 6] >> (pn & 63)) & 1)) { pins[pn >> 6] |= 1ull << (pn & 63); npins++; }
-                }
-                const double ext = (double)(d.xs_host[x1] - d.xs_host[x0]) + (double)(d.ys_host[y1] - d.ys_host[y0]) +
-                                   0.5 * b->cfg.via_cost * (z1 - z0) + R.w_min;
-                hwork[R.net_off + n] = (float)(ext * (6 + npins));
-            }
-        }
-        n_max_nodes = std::max(n_max_nodes, N);
-        k_max = std::max(k_max, d.n_nets);
-        x_max = std::max(x_max, d.dim_x);
-        y_max = std::max(y_max, d.dim_y);
-        if (N % 4) mult4 = false;
-        if (N % 16) mult16 = false;
-        {   // padded field: l = x*SX + y*SY + z, SY = Z|1, SX = (Y*SY)|1 (xr_route_kernel)
-            const int64_t sy = d.dim_z | 1, sx = ((int64_t)d.dim_y * sy) | 1;
-            const int64_t words = (int64_t)d.dim_x * sx;
-            if (words > ((int64_t)1 << 30)) return fail(XR_ERR_RANGE, "region %d: too many nodes", r);
-            n_lds = std::max(n_lds, (int)words);
-            int nv = 0;
-            for (int z = 0; z < d.dim_z; z++) nv += d.layer_dir_host[z] ? 1 : 0;
-            tracks_max = std::max(tracks_max, (d.dim_z - nv) * d.dim_y + nv * d.dim_x);
-            lines_max = std::max(lines_max, (d.dim_z - nv) * d.dim_y + nv * d.dim_x + d.dim_x * d.dim_y);
-            bits_max = std::max(bits_max, (d.dim_z - nv) * d.dim_y + nv * d.dim_x + 2 * d.dim_x * d.dim_y);
-            z_min = std::min(z_min, d.dim_z); z_max = std::max(z_max, d.dim_z);
-            ncol_max = std::max(ncol_max, d.dim_x * d.dim_y);
-        }
-    }
-    const int legal_words = std::max(1, (k_max + 63) / 64);
-    // the observation kernels stage the ascending legal-id list in LDS (4 bytes per possible net)
-    if ((size_t)legal_words * 64 * 4 + (size_t)(legal_words + 1) * 4 > 60 * 1024)
-        return fail(XR_ERR_RANGE, "k_max %d too large for the observation kernel's LDS id list (max ~15000 nets)", k_max);
-    std::vector<uint64_t> hlegal0((size_t)n_regions * legal_words, 0);
-    for (int r = 0; r < n_regions; r++) {
-        hreg[r].legal0_off = (int64_t)r * legal_words;
-        const int32_t* csr = hcsr.data() + hreg[r].net_off;
-        for (int n = 1; n <= hreg[r].n_nets; n++)
-            if (csr[n + 1] > csr[n]) hlegal0[(size_t)r * legal_words + ((n - 1) >> 6)] |= 1ULL << ((n - 1) & 63);
-    }
-
-    b->n_regions = n_regions;
-    b->n_max_nodes = n_max_nodes;
-    b->n_max = (n_max_nodes + 7) & ~7;
-    b->n_lds = (n_lds + 7) & ~7;
-    b->tracks_max = tracks_max;
-    b->lines_max = lines_max;
-    b->bits_max = bits_max;
-    b->zch = (z_min == z_max && (z_max == 9 || z_max == 12)) ? z_max : 0;
-    b->k_max = k_max;
-    b->legal_words = legal_words;
-    b->x_max = x_max;
-    b->y_max = y_max;
-    b->all_n_mult4 = mult4;
-    b->all_n_mult16 = mult16;
-    b->path_cap = b->cfg.path_cap > 0 ? b->cfg.path_cap : std::min(n_max_nodes, 4096);
-
-    // route kernel placement: distance field in LDS when it fits.  Worklist items are (line, chunk of 8 nodes) pairs:
-    // x-tracks * ceil(X/8) + y-tracks * ceil(Y/8) + columns * (1 when every region has 9 / 12 layers, else ceil(Z/8))
-    int items_max = 0, kind_max = 0;
-    for (int r = 0; r < n_regions; r++) {
-        const XrRegionDev& R = hreg[r];
-        int nv = 0;
-        for (int z = 0; z < R.Z; z++) nv += (R.ldir_mask >> z) & 1u;
-        const int chH = (R.X + 7) / 8, chV = (R.Y + 7) / 8, chC = b->zch ? 1 : (R.Z + 7) / 8;
-        const int64_t itH = (int64_t)(R.Z - nv) * R.Y * chH, itV = (int64_t)nv * R.X * chV, itC = (int64_t)R.X * R.Y * chC;
-        if (itH > 65536 || itV > 65536 || itC > 65536)
-            return fail(XR_ERR_RANGE, "region %d: more than 65536 worklist items of one kind (%lld / %lld / %lld)", r,
-                        (long long)itH, (long long)itV, (long long)itC);
-        items_max = std::max(items_max, (int)(itH + itV + itC));
-        kind_max = std::max(kind_max, (int)std::max(itH, std::max(itV, itC)));
-    }
-    lines_max = items_max;
-    b->lines_max = items_max;
-    // field + edge-length tables + 3 item bitmasks + worklists (u16 item ids; the claim bitmask aliases them)
-    const size_t lw_max = ((size_t)items_max + 31) / 32 + 1;
-    const size_t el_bytes = (size_t)(x_max + 2 + y_max + 2) * 4;
-    const size_t list_bytes = std::max(((size_t)items_max * 2 + 3) & ~(size_t)3, ((size_t)b->n_lds / 32 + 1) * 4);
-    const size_t lds_need = (size_t)b->n_lds * 4 + el_bytes + 3 * lw_max * 4 + list_bytes + 16;
-    b->lds_dist = lds_need + kLdsStatic <= kLdsLimit && !b->cfg.force_scratch_field;
-    b->route_lds = b->lds_dist ? lds_need : el_bytes + 3 * lw_max * 4;
-    const bool sweep_lds_ok = b->lds_dist;
-    // workgroup size of the step kernel unless the caller asks: 256 with the field in LDS (4 waves; 4 workgroups per CU
-    // resident at 24x40x9), 1024 with the field in HBM scratch (latency-bound on memory: more items in flight per env)
-    b->route_threads = b->cfg.block_threads ? b->cfg.block_threads : (b->lds_dist ? 256 : 1024);
-    // default router: bucketed frontier expansion with field + three node bitmasks + edge tables in LDS (xr_dial.h);
-    // regions that do not fit keep the sweep router's HBM-scratch form
-    b->kzch = b->zch;
-    {
-        const size_t mw_max = (size_t)b->n_max / 32 + 1;
-        const size_t dial_lds = (size_t)b->n_max * 4 + 4 * mw_max * 4 + el_bytes + 16;
-        // HBM-scratch form (regions too large for LDS, or force_scratch_field): groups of 1024 nodes must fit the LDS group table
-        const size_t big_lds = (size_t)XR_BIG_MAXG * 6 + (size_t)XR_BIG_CA * 4 + (size_t)XR_BIG_CN * 4 + 2 * (size_t)XR_BIG_CE * 8 + el_bytes + 16;
-        const bool big_ok = ((size_t)b->n_max / 1024 + 2) <= 1024;
-        b->dial_big = false;
-        if (b->cfg.router != XR_ROUTER_SWEEP && !b->cfg.force_scratch_field && dial_lds + kLdsStatic <= kLdsLimit) {
-            b->kzch = -1;
-            b->lds_dist = true;
-            b->route_lds = dial_lds;
-            b->route_threads = b->cfg.block_threads ? b->cfg.block_threads : 256;
-        } else if (b->cfg.router != XR_ROUTER_SWEEP && big_ok) {
-            b->kzch = -1;
-            b->lds_dist = false;
-            b->dial_big = true;
-            b->route_lds = big_lds;
-            // (round 2, config 5: 256 threads 4.2-4.7 ms, 512: 3.7-3.9 ms.  Round 3, same box, ms per launch at 256 / 1024 / 4096 envs: 512 threads
-            //  1.9 / 2.7 / 4.0, 1024 threads 1.8 / 2.4 / 6.5 — a wider workgroup shortens each route's rounds (wide frontiers) but only one
-            //  fits a CU: it pays while the batch is at most ~4 routes per CU, i.e. while the launch is bound by its longest routes)
-            int big_threads = 512;
-            {
-                hipDeviceProp_t prop;
-                if (hipGetDeviceProperties(&prop, b->cfg.device) == hipSuccess && B <= 4 * prop.multiProcessorCount) big_threads = 1024;
-            }
-            b->route_threads = b->cfg.block_threads ? b->cfg.block_threads : big_threads;
-            // the LDS router inside a window of the region first (xr_dial3.h, WIN; xr_config.window: > 0 = that many tracks at most — the
-            // largest square window <= it that fits LDS; 0 (default) and < 0 = off: measured no faster on BASELINE config 5):
-            // every region must have the same layer count and hold the window, rows of the state arrays must start on 16-byte boundaries
-            // wherever a window row may start, the arithmetic limits are those of the form
-            b->win = {};
-            const bool v2cfg = b->cfg.guide_cost > 0 || b->cfg.maze_end_iter > 1;
-            const int64_t pen_w = (int64_t)b->cfg.drc_cost * b->cfg.drc_unit;
-            if (b->cfg.window > 0 && !v2cfg && z_min == z_max && edge_max + pen_w < XR3_STEP_LIMIT) {
-                const int Zw = z_max;
-                int ystep = 1;
-                while ((ystep * Zw) % 8) ystep *= 2;                 // rows start at y0 * Z elements: a multiple of 8 of them (16 bytes of int16)
-                bool rows_ok = true;
-                int xmin = 1 << 30, ymin = 1 << 30;
-                for (int r = 0; r < n_regions; r++) {
-                    rows_ok = rows_ok && ((int64_t)regs[r].dim_y * Zw) % 8 == 0;
-                    xmin = std::min(xmin, (int)regs[r].dim_x); ymin = std::min(ymin, (int)regs[r].dim_y);
-                }
-                int w = std::min(b->cfg.window, std::min(xmin, ymin));
-                for (; w >= 8 && rows_ok; w--) {
-                    if ((w * Zw) % 8) continue;                          // a chunk of 8 nodes never straddles two window rows
-                    const int64_t nw = (int64_t)w * w * Zw;
-                    const size_t wl = XR3_LDS_BYTES((nw + 7) & ~7, w, w);
-                    if (nw >= 65536 || std::max(wl, big_lds) + 2 * kLdsStatic > kLdsLimit || (int64_t)w * edge_max >= XR3_EXTENT_LIMIT) continue;
-                    uint32_t myz, syz, mz, sz, mmw, smw;
-                    const uint32_t mwv = (uint32_t)((nw + 31) / 32);
-                    if (!magic24((uint32_t)(w * Zw), (uint32_t)nw, myz, syz) || !magic24((uint32_t)Zw, (uint32_t)std::max(w, 1) * Zw * 2, mz, sz) ||
-                        !magic24(mwv, (uint32_t)nw, mmw, smw)) continue;
-                    b->win.x = w; b->win.y = w; b->win.nmax = (int)((nw + 7) & ~7); b->win.ystep = ystep;
-                    // tracks kept free around the net's box (the row alignment is checked per net).  A net whose box nearly fills the window
-                    // floods past its faces, fails its certificate and has paid for the attempt on top of the fallback: margins of 4 / 8 /
-                    // 13 / 18 tracks of a 52-track window send 27 / 33 / 48 / 68 % of BASELINE config 5's routes to the fallback
-                    // (profiles/r04_l_config5_window_form.txt)
-                    b->win.margin = std::max(1, std::min(4, w / 8));
-                    if (const char* em = getenv("XR_WINDOW_MARGIN")) b->win.margin = std::max(1, atoi(em));      // (A/B runs)
-                    b->win.m24_yz = myz; b->win.m24_z = mz; b->win.m24_mw = mmw; b->win.s24 = syz | (sz << 8) | (smw << 16);
-                    b->route_lds = std::max(b->route_lds, wl);
-                    break;
-                }
-            }
-        }
-        // round 3's LDS form (xr_dial3.h) where it applies: the field fits with its queues, node ids fit 16 bits, and its 27-bit distance
-        // arithmetic cannot wrap: every distance that exists is below XR_DIST_CAP = 0x07F00000 (spec; a candidate at or above the cap is
-        // never written), so a reached word + one edge with every penalty stays inside 32 bits while that step is < 2^20 (the x32
-        // fixed point of the word); the x32 coordinate tables and the heuristic need a region that spans < 2^25 DBU
-        {
-            const size_t d3_lds = XR3_LDS_BYTES(b->n_max, x_max, y_max);
-            const int64_t pen_max = ((int64_t)b->cfg.drc_cost * b->cfg.drc_unit) << (b->cfg.maze_end_iter - 1);
-            const bool range_ok = edge_max + pen_max + b->cfg.guide_cost < XR3_STEP_LIMIT && ext_max < XR3_EXTENT_LIMIT &&
-                                  (int64_t)b->cfg.via_cost * 32 < XR3_EXTENT_LIMIT;
-            if (b->kzch == -1 && b->lds_dist && b->cfg.router != XR_ROUTER_DIAL_R2 && range_ok && b->n_max < 65536 && div24_all &&
-                d3_lds + kLdsStatic <= kLdsLimit) {
-                b->kzch = -3;
-                b->route_lds = d3_lds;
-            }
-        }
-        const bool v2 = b->cfg.guide_cost > 0 || b->cfg.maze_end_iter > 1;
-        if (v2 && b->kzch == -3) b->kzch = -4;
-        if (v2 && b->kzch == -1) b->kzch = -2;          // the instantiations with the XR-Maze v2 knobs compiled in (LDS and HBM-scratch form)
-        if (v2 && b->kzch != -2 && b->kzch != -4)
-            return fail(XR_ERR_RANGE, "xr_batch_load_regions: XR-Maze v2 (guide_cost / maze_end_iter) needs the frontier router "
-                                      "(router != XR_ROUTER_SWEEP, regions within its limits)");
-        if (b->kzch >= 0 && (b->cfg.router == XR_ROUTER_DIAL || b->cfg.router == XR_ROUTER_DIAL_R2)) {
-            return fail(XR_ERR_RANGE, "xr_batch_load_regions: XR_ROUTER_DIAL: the largest region (%d nodes) exceeds the frontier router's limits", b->n_max);
-        }
-    }
-    // the fused observation epilogue stages the ascending legal-id list in the same LDS
-    const size_t ids_bytes = (size_t)(legal_words * 64 + ((legal_words + 1 + 3) & ~3)) * 4;
-    // flat-stream observation (any N): ids + a 16-bit feature per node in LDS
-    const size_t stream_bytes = (size_t)(legal_words * 64 + ((legal_words + 1 + 3) & ~3)) * 4 + (size_t)b->n_max * 2;
-    b->stream_ok = stream_bytes <= 60 * 1024;
-    b->route_lds = std::max(b->route_lds, b->stream_ok && !mult4 ? stream_bytes : ids_bytes);
-    // router = 0 (auto) picks per entry point the scheme measured faster for it: the frontier router everywhere, except the
-    // FULL-rewrite queue launch of a very large batch, where the line-segment sweeps are ahead (same box, DESIGN.md §5.1:
-    // 1.727-1.730 ms against 1.773-1.775 ms per 4096-env step; at 2048 envs the frontier router wins, 0.921 against 0.945-0.954 ms)
-    b->sweep_lds = std::max(lds_need, b->stream_ok && !mult4 ? stream_bytes : ids_bytes);
-    // (round 3, same box: synthetic 24x40x9 regions 1.681 ms with the sweeps against 1.700 ms with the frontier router; the regions
-    //  extracted from ispd18_test1 — unaligned planes, 3.5 pins per net, K up to 77: their step is bound by routing, not by the write
-    //  stream — 2.40 ms against 2.05 ms: the sweeps are only chosen for aligned planes)
-    b->sweep_full = b->cfg.router == 0 && (b->kzch == -1 || b->kzch == -3) && b->lds_dist && sweep_lds_ok && b->cfg.block_threads == 0 &&
-                    b->cfg.n_envs >= 4096 && mult4 && b->sweep_lds + kLdsStatic <= kLdsLimit;
-    if (b->route_lds + kLdsStatic > kLdsLimit)
-        return fail(XR_ERR_RANGE, "route kernel needs %zu bytes of LDS (line bitmasks of the largest region)", b->route_lds);
-    if (std::max(b->route_lds, b->sweep_full ? b->sweep_lds : 0) > 64 * 1024)
-        XR_HIP(xr_route_set_max_lds(std::max(b->route_lds, b->sweep_full ? b->sweep_lds : 0)));
-
-    // ---- device allocations ------------------------------------------------------------------
-#define XR_ALLOC(buf, count)                                                                        \
-    do {                                                                                            \
-        hipError_t _e = (buf).alloc(count);                                                         \
-        if (_e != hipSuccess)                                                                       \
-            return fail(XR_ERR_NOMEM, "hipMalloc of %zu bytes failed: %s", (size_t)(count) * sizeof(*(buf).p), \
-                        hipGetErrorString(_e));                                                     \
-    } while (0)
-    XR_ALLOC(b->regions, n_regions);
-    XR_ALLOC(b->rg_rec, hrec.size());
-    XR_ALLOC(b->rg_node_net, hrec.size());
-    XR_ALLOC(b->rg_owner0, hrec.size());
-    XR_ALLOC(b->coords, hcoords.size());
-    XR_ALLOC(b->net_csr, hcsr.size());
-    XR_ALLOC(b->ap_node, std::max<size_t>(1, hap_node.size()));
-    XR_ALLOC(b->ap_pin, std::max<size_t>(1, hap_pin.size()));
-    XR_ALLOC(b->ap_feat, std::max<size_t>(1, hap_feat.size()));
-    XR_ALLOC(b->legal0, hlegal0.size());
-    XR_ALLOC(b->env_region, B);
-    XR_ALLOC(b->env_replay, B);
-    XR_ALLOC(b->nlegal, B);
-    XR_ALLOC(b->cum, (size_t)B * 3);
-    XR_ALLOC(b->delta, (size_t)B * 3);
-    XR_ALLOC(b->status, B);
-    XR_ALLOC(b->path, (size_t)B * b->path_cap);
-    XR_ALLOC(b->path_len, B);
-    XR_ALLOC(b->sweeps, B);
-    XR_ALLOC(b->touched, B);
-    XR_ALLOC(b->route_order, B);
-    XR_ALLOC(b->net_work, hcsr.size());
-    XR_ALLOC(b->net_meas, hcsr.size());
-    XR_ALLOC(b->net_info, hcsr.size());
-    XR_ALLOC(b->ap_flags, std::max<size_t>(1, hap_flags.size()));
-    XR_ALLOC(b->owner, (size_t)B * b->n_max);
-    XR_ALLOC(b->legal, (size_t)B * legal_words);
-    XR_ALLOC(b->hash, B);
-    XR_ALLOC(b->reward, B);
-    XR_ALLOC(b->records, B);
-    XR_ALLOC(b->done, B);
-    XR_ALLOC(b->env_steps, B);
-    XR_ALLOC(b->total_steps, 1);
-    XR_ALLOC(b->phase_cycles, (size_t)B * 8);
-    XR_ALLOC(b->plan_region, B);
-    XR_ALLOC(b->queue, 8);
-    XR_ALLOC(b->group_queue, (size_t)XR_MAX_GROUPS * 8);
-    XR_ALLOC(b->plan_units, (size_t)B * std::max(1, k_max));
-    XR_ALLOC(b->plan_unit_net, (size_t)B * std::max(1, k_max));
-    if (b->dial_big) {
-        const size_t mwg = (size_t)b->n_max / 32 + 1;
-        XR_ALLOC(b->dg_field, (size_t)B * b->n_max);
-        XR_ALLOC(b->dg_masks, (size_t)B * 2 * mwg);
-        XR_ALLOC(b->dg_touch, (size_t)B * b->n_max);
-        XR_ALLOC(b->dg_path, (size_t)B * b->n_max * 2);
-    } else if (!b->lds_dist) {
-        XR_ALLOC(b->dist_scratch, (size_t)B * b->n_lds);
-        XR_ALLOC(b->cls_scratch, (size_t)B * b->n_lds);
-        XR_ALLOC(b->list_scratch, (size_t)B * b->lines_max);
-    }
-#undef XR_ALLOC
-
-    XR_HIP(hipMemcpyAsync(b->regions.p, hreg.data(), hreg.size() * sizeof(XrRegionDev), hipMemcpyHostToDevice, st));
-    XR_HIP(hipMemcpyAsync(b->rg_rec.p, hrec.data(), hrec.size() * sizeof(uint32_t), hipMemcpyHostToDevice, st));
-    XR_HIP(hipMemcpyAsync(b->coords.p, hcoords.data(), hcoords.size() * sizeof(int32_t), hipMemcpyHostToDevice, st));
-    XR_HIP(hipMemcpyAsync(b->net_csr.p, hcsr.data(), hcsr.size() * sizeof(int32_t), hipMemcpyHostToDevice, st));
-    std::vector<uint8_t> hclass(hcsr.size(), 0);        // work classes 1..255 relative to the batch's largest prediction
-    {
-        float wmax = 1.0f;
-        for (float w : hwork) wmax = std::max(wmax, w);
-        for (size_t i = 0; i < hwork.size(); i++)
-            if (hwork[i] > 0.0f) hclass[i] = (uint8_t)(1 + std::min(254, (int)(254.0f * hwork[i] / wmax)));
-    }
-    XR_HIP(hipMemcpyAsync(b->net_work.p, hclass.data(), hclass.size(), hipMemcpyHostToDevice, st));
-    XR_HIP(hipMemsetAsync(b->net_meas.p, 0, hcsr.size(), st));                  // nothing measured yet: the launch orders use the geometric guess
-    hinfo.resize(hcsr.size(), 0);
-    XR_HIP(hipMemcpyAsync(b->net_info.p, hinfo.data(), hinfo.size() * sizeof(int32_t), hipMemcpyHostToDevice, st));
-    if (!hap_flags.empty()) XR_HIP(hipMemcpyAsync(b->ap_flags.p, hap_flags.data(), hap_flags.size(), hipMemcpyHostToDevice, st));
-    if (!hap_node.empty()) {
-        XR_HIP(hipMemcpyAsync(b->ap_node.p, hap_node.data(), hap_node.size() * sizeof(int32_t), hipMemcpyHostToDevice, st));
-        XR_HIP(hipMemcpyAsync(b->ap_pin.p, hap_pin.data(), hap_pin.size() * sizeof(int16_t), hipMemcpyHostToDevice, st));
-        XR_HIP(hipMemcpyAsync(b->ap_feat.p, hap_feat.data(), hap_feat.size() * sizeof(int32_t), hipMemcpyHostToDevice, st));
-    }
-    XR_HIP(hipMemcpyAsync(b->legal0.p, hlegal0.data(), hlegal0.size() * sizeof(uint64_t), hipMemcpyHostToDevice, st));
-    std::vector<int32_t> henv(B);
-    for (int e = 0; e < B; e++) henv[e] = e % n_regions;
-    XR_HIP(hipMemcpyAsync(b->env_region.p, henv.data(), (size_t)B * sizeof(int32_t), hipMemcpyHostToDevice, st));
-    XR_HIP(hipMemsetAsync(b->env_replay.p, 0, (size_t)B * sizeof(int32_t), st));
-    XR_HIP(hipMemsetAsync(b->env_steps.p, 0, (size_t)B * sizeof(int64_t), st));
-    XR_HIP(hipMemsetAsync(b->total_steps.p, 0, sizeof(unsigned long long), st));
-    XR_HIP(hipMemsetAsync(b->phase_cycles.p, 0, (size_t)B * 8 * sizeof(long long), st));
-    XR_HIP(hipMemsetAsync(b->nlegal.p, 0, (size_t)B * sizeof(int32_t), st));
-    XR_HIP(hipMemsetAsync(b->touched.p, 0, (size_t)B * sizeof(int32_t), st));
-    XR_HIP(hipMemsetAsync(b->route_order.p, 0, (size_t)B * sizeof(int32_t), st));
-    XR_HIP(hipMemsetAsync(b->records.p, 0, (size_t)B * sizeof(XrStepRecord), st));
-    XR_HIP(hipMemsetAsync(b->owner.p, 0, (size_t)B * b->n_max * sizeof(int16_t), st));
-    XR_HIP(hipMemsetAsync(b->path.p, 0, (size_t)B * b->path_cap * sizeof(int32_t), st));
-    if (b->dial_big) {      // the persistent CLEAN state of the scratch: field CLEAN, no open bits, word minima = infinity
-        const size_t mwg = (size_t)b->n_max / 32 + 1;
-        XR_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(b->dg_field.p), (int)0xFFFFFFFEu, (size_t)B * b->n_max, st));
-        for (int e = 0; e < B; e++) {
-            XR_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(b->dg_masks.p + (size_t)e * 2 * mwg), 0, mwg, st));
-            XR_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(b->dg_masks.p + (size_t)e * 2 * mwg + mwg), (int)0xFFFFFFFFu, mwg, st));
-        }
-    }
-    std::vector<uint64_t> hhash(B, 0xcbf29ce484222325ULL);
-    XR_HIP(hipMemcpyAsync(b->hash.p, hhash.data(), (size_t)B * sizeof(uint64_t), hipMemcpyHostToDevice, st));
-
-    XR_HIP(hipMemsetAsync(b->queue.p, 0, 8 * sizeof(uint32_t), st));       // both banks start clean; from then on every plan zeroes the other bank
-    b->queue_bank = 0; b->queue_last = b->queue.p;
-    XR_HIP(hipMemsetAsync(b->group_queue.p, 0, (size_t)XR_MAX_GROUPS * 8 * sizeof(uint32_t), st));     // (the partition itself survives a reload)
-    for (int g = 0; g < XR_MAX_GROUPS; g++) b->group_bank[g] = 0;
-    XR_HIP(xr_launch_ingest(b->rg_rec.p, b->rg_node_net.p, b->rg_owner0.p, (int64_t)hrec.size(), st));
-    XR_HIP(hipStreamSynchronize(st));   // host staging vectors die here
-
-    XrBatchDev& d = b->dev;
-    d.regions = b->regions.p; d.rg_rec = b->rg_rec.p; d.rg_node_net = b->rg_node_net.p; d.rg_owner0 = b->rg_owner0.p;
-    d.coords = b->coords.p; d.net_csr = b->net_csr.p; d.ap_node = b->ap_node.p; d.ap_pin = b->ap_pin.p; d.ap_feat = b->ap_feat.p; d.net_work = b->net_work.p; d.net_info = b->net_info.p;
-    {   // measured launch order (round 5): on unless XR_NO_MEASURED_ORDER=1 (A/B switch; results never depend on the order)
-        const char* off = getenv("XR_NO_MEASURED_ORDER");
-        d.net_meas = (off && off[0] == '1') ? nullptr : b->net_meas.p;
-        const char* ht = getenv("XR_HEAVY_CLASS"); const char* hm = getenv("XR_HEAVY_MULT");       // (experiment switches)
-        d.heavy_class = std::min(255, std::max(0, ht ? atoi(ht) : 0)); d.heavy_mult = std::min(16, std::max(1, hm ? atoi(hm) : 2));   // (a width of 0 would spin a route to its round cap)
-        d.meas_shift = b->lds_dist ? 13 : 15;       // class unit: 8 k cycles (LDS form: a route is 0.1-1.5 M cycles), 32 k (HBM-scratch form: up to 6 M)
-    } d.ap_flags = b->ap_flags.p;
-    d.legal0 = b->legal0.p; d.n_regions = n_regions;
-    d.n_envs = B; d.n_max = b->n_max; d.n_lds = b->n_lds; d.lw_max = (int)lw_max; d.lines_max = lines_max; d.x_max = x_max; d.y_max = y_max; d.legal_words = legal_words; d.path_cap = b->path_cap;
-    d.env_region = b->env_region.p; d.env_replay = b->env_replay.p; d.owner = b->owner.p; d.legal = b->legal.p;
-    d.nlegal = b->nlegal.p; d.cum = b->cum.p; d.delta = b->delta.p; d.reward = b->reward.p; d.done = b->done.p;
-    d.status = b->status.p; d.path = b->path.p; d.path_len = b->path_len.p; d.hash = b->hash.p;
-    d.env_steps = b->env_steps.p; d.total_steps = b->total_steps.p; d.sweeps = b->sweeps.p; d.touched = b->touched.p; d.records = b->records.p;
-    // (round 3's LDS form, same-box A/B profiles/r03_l_ab_bucket_width.txt: 12 against 8 — route-only 512 / 4096 envs 0.211 / 0.381 ->
-    //  0.203 / 0.372 ms, 512-env step 0.315 -> 0.306 ms; 16 the same, 24 slower; round 2's form and the HBM-scratch form keep 8)
-    d.dial_mult = b->cfg.dial_mult > 0 ? b->cfg.dial_mult : ((b->kzch == -3 || b->kzch == -4) ? 12 : 8);
-    d.dial_mult_big = b->cfg.dial_mult > 0 ? b->cfg.dial_mult : 8;
-    d.round_cap = b->cfg.debug_round_cap;
-    d.win_x = b->dial_big ? b->win.x : 0; d.win_y = b->win.y; d.win_nmax = b->win.nmax; d.win_margin = b->win.margin; d.win_ystep = b->win.ystep;
-    d.win_m24_yz = b->win.m24_yz; d.win_m24_z = b->win.m24_z; d.win_m24_mw = b->win.m24_mw; d.win_s24 = b->win.s24;
-    d.guide_cost = b->cfg.guide_cost; d.guide_margin = b->cfg.guide_margin; d.maze_end_iter = b->cfg.maze_end_iter;
-    d.dg_field = b->dg_field.p; d.dg_masks = b->dg_masks.p; d.dg_touch = b->dg_touch.p; d.dg_path = b->dg_path.p;
-    d.dist_scratch = b->dist_scratch.p; d.cls_scratch = b->cls_scratch.p; d.list_scratch = b->list_scratch.p; d.phase_cycles = b->phase_cycles.p;
-    d.obs_out = nullptr; d.obs_stride = 0; d.obs_vec4 = 0; d.obs_head_only = 0; d.obs_split_pm = 1000; d.obs_incremental = 0;
-    d.obs_out_u8 = nullptr;
-    d.obs_lds_bytes = (int32_t)std::min<size_t>(b->route_lds, 1u << 30);      // (every launch of the default router carries route_lds)
-    d.env_base = 0; d.env_count = 0;
-    d.plan_region = b->plan_region.p; d.plan_units = b->plan_units.p; d.plan_unit_net = b->plan_unit_net.p; d.queue = b->queue.p; d.queue_quota_pm = 750;
+    RegionStaging staging;
+    RoutePlacement place;
+    if (const int32_t rc = stage_regions(b->cfg, regs, n_regions, staging)) return rc;
+    if (const int32_t rc = place_route(b->cfg, staging, place)) return rc;
+    commit_load(b, n_regions, staging, place);
+    const size_t lds_top = std::max(place.route_lds, place.sweep_full ? place.sweep_lds : 0);
+    if (lds_top > 64 * 1024) XR_HIP(xr_route_set_max_lds(lds_top));
+    if (const int32_t rc = alloc_batch(b, staging)) return rc;
+    if (const int32_t rc = upload_batch(b, staging, st)) return rc;
     if (!b->aux_stream) {
         XR_HIP(hipStreamCreateWithFlags(&b->aux_stream, hipStreamNonBlocking));
         XR_HIP(hipEventCreateWithFlags(&b->ev_fork, hipEventDisableTiming));
@@ -892,18 +983,8 @@ int32_t xr_batch_load_regions(xr_batch* b, const xr_region_desc* regs, int32_t n
         XR_HIP(hipEventCreate(&b->ev_w0));
         XR_HIP(hipEventCreate(&b->ev_w1));
     }
-    d.via_cost = b->cfg.via_cost; d.pen_cost = b->cfg.drc_cost * b->cfg.drc_unit;
-    d.max_route_count = b->cfg.max_route_count; d.auto_reset = b->cfg.auto_reset;
-    d.w_violation = b->cfg.w_violation; d.w_via = b->cfg.w_via; d.w_wirelength = b->cfg.w_wirelength;
-    b->h_net_off.resize(n_regions); b->h_n_nets.resize(n_regions); b->h_dims.resize(3 * (size_t)n_regions);
-    for (int r = 0; r < n_regions; r++) {
-        b->h_net_off[r] = hreg[r].net_off; b->h_n_nets[r] = hreg[r].n_nets;
-        b->h_dims[3 * r] = hreg[r].X; b->h_dims[3 * r + 1] = hreg[r].Y; b->h_dims[3 * r + 2] = hreg[r].Z;
-    }
-    b->h_csr_size = hcsr.size();
+    fill_dev(b, place);
     b->loaded = true;
-    b->guide_mask_bytes = gmask_bytes;
-    d.guide_csr = nullptr; d.guide_box = nullptr;
     return build_guide_masks(b, st);          // (the default guides: bounding box of every net's access points)
 }
 
