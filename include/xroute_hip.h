@@ -452,6 +452,52 @@ int32_t xr_batch_observation_u8(xr_batch* b, uint8_t* out_dev, int64_t env_strid
 int32_t xr_batch_lookahead(xr_batch* b, int32_t group, const uint64_t* cand_mask_dev, int32_t* out_dev, int32_t k_cap, double* reward_out_dev,
                            void* stream);
 
+/* ---- rollouts: every env's episode played to its end, without stepping ---- */
+/* From the state every env is in now: what the whole rest of the episode costs under a given continuation, n_rollouts continuations per
+ * env — the many-ply expansion of the reference's MCTS trainer (baseline/xroute/trainer4/dispatcher.py:113-118), a Monte-Carlo value
+ * estimate, the "best of R random orderings" net-ordering baseline.  For every row (an env of the whole batch or of one env group, as in
+ * xr_batch_lookahead) and every r in [0, n_rollouts): copy the env's state into a throw-away shadow slot, route the prefix, continue under
+ * `policy` — every route by the same router the step takes (xr_config.router, dial_mult, the XR-Maze v2 knobs and loaded guides included).
+ *   group            -1: the whole batch, rows [0, n_envs).  >= 0: that env group; rows start at the group's first slot, and the work is
+ *                    enqueued on `stream` only.
+ *   n_rollouts       1 .. XR_ROLLOUT_MAX continuations per env.
+ *   policy           XR_ROLLOUT_STOP: play the prefix only.  XR_ROLLOUT_RANDOM: after the prefix, the built-in random policy until no net
+ *                    is left (or max_plies) with seed_r = seed + r * 0x9E3779B97F4A7C15 (mod 2^64): at every ply the net
+ *                    xr_batch_random_actions(seed_r) would choose for THIS env from the shadow state (keyed by the global env index and
+ *                    the shadow's env_steps, which a real route advances and a rejected action does not).  Rollout r of env e is bit for
+ *                    bit what a twin batch in the same state does when stepped to the end with xr_batch_random_actions(seed_r).
+ *   prefix_dev       NULL, or int32 [rows][n_rollouts][prefix_stride] of 1-based net ids, a value <= 0 ends a list.  An entry that is not
+ *                    legal at that point is skipped and flagged XR_ENV_BAD_ACTION in the rollout's status, as xr_batch_route_order treats
+ *                    it; a skipped entry costs no ply.  Once no net is left the rest of a list is ignored.
+ *   max_plies        0: until no legal net is left.  > 0: stop after that many real routes, the prefix's included.
+ *   out_dev          int32 [rows][n_rollouts][8]: {d_violation, d_wirelength, d_via (cumulative at the end minus cumulative now), status
+ *                    (OR of the XR_ENV_* bits of every route and every skipped entry), plies (real routes made), nlegal_end, path_len_sum,
+ *                    0}.
+ *   return_out_dev   NULL, or double [rows][n_rollouts]: the sum of the per-step rewards, added in step order in double from 0.0.
+ *   hash_out_dev     NULL, or uint64 [rows][n_rollouts]: the env's hash chain (XR_FETCH_HASH) continued over the rollout's routes.
+ *   order_out_dev    NULL, or int32 [rows][n_rollouts][k_cap]: the nets routed, in order; entries past `plies` are 0.  k_cap >= k_max is
+ *                    required only when order_out_dev is given.
+ * An env that is done (no legal net) gets the empty rollout — rollouts never look through an auto-reset: {0, 0, 0, 0, 0, 0, 0, 0}, return
+ * 0.0, hash = the env's current hash, order all 0.  (A rollout that makes no route from a live env — XR_ROLLOUT_STOP without a usable
+ * prefix — is the same except nlegal_end = the env's nlegal, and XR_ENV_BAD_ACTION if entries were skipped.)
+ * Errors (the batch is untouched after any of them): XR_ERR_INVALID null b / out_dev, a group outside -1 .. n_groups - 1, an unknown
+ * policy, prefix_dev with prefix_stride < 1, a negative max_plies; XR_ERR_STATE before xr_batch_load_regions; XR_ERR_RANGE n_rollouts
+ * outside 1 .. XR_ROLLOUT_MAX, k_cap < k_max with order_out_dev, rows x n_rollouts beyond 31 bits; XR_ERR_RANGE for the HBM-scratch router
+ * forms (force_scratch_field included) and for stream_per_region, for lookahead's reason.
+ * Contract, the same as lookahead's.  A rollout never synchronises: it only enqueues on `stream` (one persistent launch; tasks are claimed
+ * from a counter that the previous launch on the pool zeroed).  It may allocate its private memory on the first call, per batch and per
+ * group (it plays in lookahead's shadow slots, with claim counters of its own).  It leaves NO TRACE in the batch: every array
+ * xr_batch_fetch returns is only read, and the validity of the in-place observation buffers (fp32 and uint8, batch-wide and per group) is
+ * kept.  Rollouts of DIFFERENT groups may be in flight at once on different streams; within one group (or for the whole batch) rollouts,
+ * lookaheads and steps are ordered by the caller. */
+#define XR_ROLLOUT_STOP    0   /* play the prefix only */
+#define XR_ROLLOUT_RANDOM  1   /* after the prefix: the built-in random policy until no net is left (or max_plies) */
+#define XR_ROLLOUT_MAX     4096
+int32_t xr_batch_rollout(xr_batch* b, int32_t group, int32_t n_rollouts, int32_t policy, uint64_t seed,
+                         const int32_t* prefix_dev, int32_t prefix_stride, int32_t max_plies,
+                         int32_t* out_dev, double* return_out_dev, uint64_t* hash_out_dev,
+                         int32_t* order_out_dev, int32_t k_cap, void* stream);
+
 /* ---- XR-Maze v2: global-route guides (optional) ---------------------------------------------- */
 /* The reference's simulator runs with `-follow_guide 1` (ispd/ispd18_test1/run-net-ordering-training.tcl:3) on the guide file
  * it ships (ispd/ispd18_test1/ispd18_test1.input.guide: per net, rectangles per metal layer).  With xr_config.guide_cost > 0 a

@@ -33,6 +33,7 @@ SYMBOLS = [
     "xr_batch_set_groups", "xr_batch_step_group", "xr_batch_random_actions_group", "xr_batch_fetch_group",
     "xr_batch_step_observe_u8", "xr_batch_observation_u8",
     "xr_batch_lookahead",
+    "xr_batch_rollout",
     "xr_observation_from_records", "xr_proto_decode", "xr_proto_encode_response", "xr_proto_encode_request",
 ]
 
@@ -59,6 +60,12 @@ RECORD_BYTES = 48
 XR_MAX_GROUPS, XR_GROUP_INPLACE = 64, 1
 XR_OBS_U8_INPLACE = 1
 XR_ROUTER_SWEEP, XR_ROUTER_DIAL = 1, 2
+XR_ROLLOUT_STOP, XR_ROLLOUT_RANDOM, XR_ROLLOUT_MAX = 0, 1, 4096
+
+
+def rollout_seed(seed: int, r: int) -> int:
+    """seed_r of xr_batch_rollout: the seed whose xr_batch_random_actions rollout r follows (mod 2^64)."""
+    return (int(seed) + int(r) * 0x9E3779B97F4A7C15) & (2 ** 64 - 1)
 
 
 class XrRegionDesc(C.Structure):
@@ -123,6 +130,7 @@ def lib():
     L.xr_batch_step_observe_u8.argtypes = [vp, C.c_int32, vp, vp, C.c_int64, C.c_int32, vp]
     L.xr_batch_observation_u8.argtypes = [vp, vp, C.c_int64, C.c_int32, C.c_int32, vp]
     L.xr_batch_lookahead.argtypes = [vp, C.c_int32, vp, vp, C.c_int32, vp, vp]
+    L.xr_batch_rollout.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32, C.c_uint64, vp, C.c_int32, C.c_int32, vp, vp, vp, vp, C.c_int32, vp]
     L.xr_batch_random_actions_group.argtypes = [vp, C.c_int32, vp, C.c_uint64, vp]
     L.xr_batch_fetch_group.argtypes = [vp, C.c_int32, C.c_int32, vp, C.c_size_t, vp]
     L.xr_agent_obstacle_tower_weights.argtypes = []

@@ -317,6 +317,56 @@ class RegionBatch:
                                                  self._stream_arg(stream)))
         return out, reward_out
 
+    # ---- rollouts: every env's episode played to its end, without stepping (xr_batch_rollout) -----------------------------------
+    _ROLLOUT_POLICY = {"stop": _lib.XR_ROLLOUT_STOP, "random": _lib.XR_ROLLOUT_RANDOM}
+
+    def rollout(self, n_rollouts: int, seed: int = 0, policy="random", prefix: Optional[torch.Tensor] = None, max_plies: int = 0,
+                group: Optional[int] = None, stream=None, out: Optional[torch.Tensor] = None, return_out: Optional[torch.Tensor] = None,
+                hash_out: Optional[torch.Tensor] = None, order_out: Optional[torch.Tensor] = None):
+        """From the state every env is in now, play the rest of its episode n_rollouts times; the batch is left exactly as it was.
+        Rollout r routes its prefix (int32 [rows, n_rollouts, stride] of 1-based net ids, <= 0 ends a list; entries that are not legal
+        are skipped and flagged BAD_ACTION), then continues under `policy`: "stop" (the prefix only) or "random" (what random_actions(
+        _lib.rollout_seed(seed, r)) would pick at every ply, until no net is left or max_plies real routes were made).  Returns a dict
+        of device tensors: `out` int32 [rows, R, 8] = {d_violation, d_wirelength, d_via, status OR, plies, nlegal_end, path_len_sum, 0},
+        `ret` float64 [rows, R] (the sum of the per-step rewards), `hash` int64 [rows, R] (the env's hash chain continued) and `order`
+        int32 [rows, R, k_max] (the nets routed, 0 past `plies`).  A done env holds the empty rollout.  group: an env group (rows = its
+        slots, enqueued on `stream`, default the current stream); None: the whole batch."""
+        if group is None:
+            g, rows = -1, self.n_envs
+        else:
+            lo, hi = self.group_bounds(group)
+            g, rows = int(group), hi - lo
+        R = int(n_rollouts)
+        if not 1 <= R <= _lib.XR_ROLLOUT_MAX:
+            raise ValueError(f"n_rollouts must be in 1..{_lib.XR_ROLLOUT_MAX}, got {n_rollouts}")
+        if rows * R >= 2 ** 31:
+            raise ValueError("rows x n_rollouts does not fit 31 bits")
+        pol = self._ROLLOUT_POLICY.get(policy, policy) if isinstance(policy, str) else policy
+        if isinstance(pol, bool) or pol not in (_lib.XR_ROLLOUT_STOP, _lib.XR_ROLLOUT_RANDOM):
+            raise ValueError(f"policy must be 'stop' or 'random' (XR_ROLLOUT_STOP / XR_ROLLOUT_RANDOM), got {policy!r}")
+        if int(max_plies) < 0:
+            raise ValueError(f"max_plies must be >= 0, got {max_plies}")
+        k = max(int(self.k_max), 1)
+        bufs = {"out": (out, torch.int32, (rows, R, 8)), "return_out": (return_out, torch.float64, (rows, R)),
+                "hash_out": (hash_out, torch.int64, (rows, R)), "order_out": (order_out, torch.int32, (rows, R, k))}
+        if any(t is None for t, _, _ in bufs.values()):
+            with torch.cuda.stream(stream if stream is not None else torch.cuda.current_stream(self.device)):
+                bufs = {n: (torch.empty(shp, dtype=dt, device=self.device) if t is None else t, dt, shp) for n, (t, dt, shp) in bufs.items()}
+        for name, (t, dt, shp) in bufs.items():
+            if t.device != self.device or t.dtype != dt or not t.is_contiguous() or tuple(t.shape) != shp:
+                raise ValueError(f"{name} must be a contiguous {str(dt).replace('torch.', '')} {list(shp)} tensor on the batch device")
+        pp, stride = None, 0
+        if prefix is not None:
+            if prefix.device != self.device or prefix.dtype != torch.int32 or not prefix.is_contiguous() or prefix.dim() != 3 \
+                    or tuple(prefix.shape[:2]) != (rows, R) or prefix.shape[2] < 1:
+                raise ValueError(f"prefix must be a contiguous int32 [{rows}, {R}, stride >= 1] tensor on the batch device")
+            pp, stride = C.c_void_p(prefix.data_ptr()), int(prefix.shape[2])
+        ptr = {n: C.c_void_p(t.data_ptr()) for n, (t, _, _) in bufs.items()}
+        with torch.cuda.device(self.device):
+            _lib.check(self.L.xr_batch_rollout(self._h, g, R, int(pol), C.c_uint64(int(seed) & (2 ** 64 - 1)), pp, stride, int(max_plies),
+                                               ptr["out"], ptr["return_out"], ptr["hash_out"], ptr["order_out"], k, self._stream_arg(stream)))
+        return {"out": bufs["out"][0], "ret": bufs["return_out"][0], "hash": bufs["hash_out"][0], "order": bufs["order_out"][0]}
+
     def alloc_head(self) -> torch.Tensor:
         """[n_envs, 2*n_max] fp32 buffer for the compact-consumer step (planes 0..1 of every env)."""
         return torch.empty((self.n_envs, 2 * self.n_max), dtype=torch.float32, device=self.device)

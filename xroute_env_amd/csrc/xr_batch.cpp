@@ -156,13 +156,15 @@ struct xr_batch {
     int group_bank[XR_MAX_GROUPS] = {};
     ObsValid group_valid[XR_MAX_GROUPS];        // per group: buffer (row 0 = the group's first slot) that holds its observation
     // lookahead (xr_batch_lookahead): private memory of the callers that have used it — [0] the whole batch, [1 + g] env group g.  One pool =
-    // the rows of look_grid shadow slots (everything a router writes per env), the task list and two banks of {tasks listed, next task}
+    // the rows of look_grid shadow slots (everything a router writes per env), the task list and two banks of {tasks listed, next task}.
+    // Rollouts (xr_batch_rollout) play in the same shadow slots — calls on one pool are ordered by the caller — with claim counters of
+    // their own: roll_ctr, two alternating banks of one counter
     struct LookPool {
         DevBuf<uint8_t> mem;
-        DevBuf<uint32_t> tasks, ctr;
-        int bank = 0;
+        DevBuf<uint32_t> tasks, ctr, roll_ctr;
+        int bank = 0, roll_bank = 0;
         XrBatchDev shadow{};
-        void release() { mem.release(); tasks.release(); ctr.release(); bank = 0; }
+        void release() { mem.release(); tasks.release(); ctr.release(); roll_ctr.release(); bank = 0; roll_bank = 0; }
     } look[1 + XR_MAX_GROUPS];
     int look_grid = 0;                          // workgroups of the persistent lookahead launch the chip holds at once (0: not asked yet)
     XrBatchDev dev{};
@@ -1723,7 +1725,7 @@ int32_t xr_batch_fetch_group(xr_batch* b, int32_t group, int32_t what, void* dst
 namespace {
 // The pool of one caller (whole batch / one env group), allocated on its first lookahead: look_grid shadow slots carved out of one
 // allocation (every row starts on a 16-byte boundary), a task list for every (slot, net) pair the batch can hold, two banks of counters.
-int32_t look_pool(xr_batch* b, xr_batch::LookPool& lp, hipStream_t st) {
+int32_t look_pool(xr_batch* b, xr_batch::LookPool& lp, hipStream_t st, const char* who = "xr_batch_lookahead") {
     if (lp.mem.p) return XR_OK;
     const size_t G = (size_t)b->look_grid;
     size_t off = 0;
@@ -1741,12 +1743,12 @@ int32_t look_pool(xr_batch* b, xr_batch::LookPool& lp, hipStream_t st) {
     if (e == hipSuccess) e = lp.ctr.alloc(4);
     if (e != hipSuccess) {
         lp.release();
-        return fail(XR_ERR_NOMEM, "xr_batch_lookahead: hipMalloc of %zu bytes of shadow slots failed: %s", off, hipGetErrorString(e));
+        return fail(XR_ERR_NOMEM, "%s: hipMalloc of %zu bytes of shadow slots failed: %s", who, off, hipGetErrorString(e));
     }
     if (hipMemsetAsync(lp.ctr.p, 0, 4 * sizeof(uint32_t), st) != hipSuccess ||          // both banks start clean; every plan zeroes the other bank
         hipMemsetAsync(lp.mem.p, 0, off, st) != hipSuccess) {
         lp.release();
-        return fail(XR_ERR_HIP, "xr_batch_lookahead: clearing the shadow slots failed");
+        return fail(XR_ERR_HIP, "%s: clearing the shadow slots failed", who);
     }
     uint8_t* const m = lp.mem.p;
     XrBatchDev& d = lp.shadow;
@@ -1762,6 +1764,34 @@ int32_t look_pool(xr_batch* b, xr_batch::LookPool& lp, hipStream_t st) {
     d.touched = reinterpret_cast<int32_t*>(m + o_touched); d.env_region = reinterpret_cast<int32_t*>(m + o_region);
     d.env_replay = reinterpret_cast<int32_t*>(m + o_replay); d.done = m + o_done;
     return XR_OK;
+}
+
+// once per load: CUs x resident workgroups per CU of the persistent lookahead kernel (the rollout kernel has its launch bounds and its
+// dynamic LDS), at most one per possible (slot, net) pair
+hipError_t look_grid_once(xr_batch* b, const XrRouteVariant& v) {
+    if (b->look_grid != 0) return hipSuccess;
+    hipDeviceProp_t prop;
+    hipError_t e = hipGetDeviceProperties(&prop, b->cfg.device);
+    if (e != hipSuccess) return e;
+    int per_cu = 0;
+    e = xr_lookahead_occupancy(v, &per_cu);
+    if (e != hipSuccess) return e;
+    const int64_t pairs = (int64_t)b->cfg.n_envs * std::max(1, b->k_max);
+    b->look_grid = (int)std::min<int64_t>((int64_t)std::max(1, per_cu) * prop.multiProcessorCount, pairs);
+    return hipSuccess;
+}
+
+// the shadow view: the batch as it is configured NOW (guides may have been loaded since the pool was made), rows of the shadow slots
+XrBatchDev shadow_view(const xr_batch* b, const xr_batch::LookPool& lp) {
+    XrBatchDev sh = b->dev;
+    const XrBatchDev& p = lp.shadow;
+    sh.owner = p.owner; sh.path = p.path; sh.legal = p.legal; sh.hash = p.hash; sh.reward = p.reward; sh.env_steps = p.env_steps;
+    sh.total_steps = p.total_steps; sh.phase_cycles = p.phase_cycles; sh.records = p.records; sh.cum = p.cum; sh.delta = p.delta;
+    sh.nlegal = p.nlegal; sh.status = p.status; sh.path_len = p.path_len; sh.sweeps = p.sweeps; sh.touched = p.touched;
+    sh.env_region = p.env_region; sh.env_replay = p.env_replay; sh.done = p.done;
+    sh.auto_reset = 0; sh.net_meas = nullptr; sh.obs_out = nullptr; sh.obs_out_u8 = nullptr; sh.route_order = nullptr;
+    sh.n_envs = b->look_grid; sh.env_base = 0; sh.env_count = 0;
+    return sh;
 }
 }  // namespace
 
@@ -1783,25 +1813,10 @@ int32_t xr_batch_lookahead(xr_batch* b, int32_t group, const uint64_t* cand_mask
     XR_HIP(hipSetDevice(b->cfg.device));
     hipStream_t st = static_cast<hipStream_t>(stream);
     const XrRouteVariant v = route_variant(b);
-    if (b->look_grid == 0) {          // once per load: CUs x resident workgroups per CU of the persistent kernel, at most one per possible task
-        hipDeviceProp_t prop;
-        XR_HIP(hipGetDeviceProperties(&prop, b->cfg.device));
-        int per_cu = 0;
-        XR_HIP(xr_lookahead_occupancy(v, &per_cu));
-        const int64_t pairs = (int64_t)b->cfg.n_envs * std::max(1, b->k_max);
-        b->look_grid = (int)std::min<int64_t>((int64_t)std::max(1, per_cu) * prop.multiProcessorCount, pairs);
-    }
+    XR_HIP(look_grid_once(b, v));
     xr_batch::LookPool& lp = b->look[group + 1];
     if (const int32_t rc = look_pool(b, lp, st)) return rc;
-    // the shadow view: the batch as it is configured NOW (guides may have been loaded since the pool was made), rows of the shadow slots
-    XrBatchDev sh = b->dev;
-    const XrBatchDev& p = lp.shadow;
-    sh.owner = p.owner; sh.path = p.path; sh.legal = p.legal; sh.hash = p.hash; sh.reward = p.reward; sh.env_steps = p.env_steps;
-    sh.total_steps = p.total_steps; sh.phase_cycles = p.phase_cycles; sh.records = p.records; sh.cum = p.cum; sh.delta = p.delta;
-    sh.nlegal = p.nlegal; sh.status = p.status; sh.path_len = p.path_len; sh.sweeps = p.sweeps; sh.touched = p.touched;
-    sh.env_region = p.env_region; sh.env_replay = p.env_replay; sh.done = p.done;
-    sh.auto_reset = 0; sh.net_meas = nullptr; sh.obs_out = nullptr; sh.obs_out_u8 = nullptr; sh.route_order = nullptr;
-    sh.n_envs = b->look_grid; sh.env_base = 0; sh.env_count = 0;
+    const XrBatchDev sh = shadow_view(b, lp);
     uint32_t* const ctr = lp.ctr.p + 2 * lp.bank;
     uint32_t* const next_ctr = lp.ctr.p + 2 * (lp.bank ^ 1);
     lp.bank ^= 1;
@@ -1809,6 +1824,50 @@ int32_t xr_batch_lookahead(xr_batch* b, int32_t group, const uint64_t* cand_mask
     if (b->k_max < 1) return XR_OK;          // (no region has a net: the fill is the whole answer)
     const int blocks = (int)std::min<int64_t>(b->look_grid, (int64_t)rows * b->k_max);
     XR_HIP(xr_launch_lookahead(&b->dev, &sh, lo, lp.tasks.p, ctr, out_dev, reward_out_dev, k_cap, b->k_max, v, blocks, st));
+    return XR_OK;
+}
+
+// ---- rollouts ----------------------------------------------------------------------------------------------------------------------
+int32_t xr_batch_rollout(xr_batch* b, int32_t group, int32_t n_rollouts, int32_t policy, uint64_t seed, const int32_t* prefix_dev, int32_t prefix_stride,
+                         int32_t max_plies, int32_t* out_dev, double* return_out_dev, uint64_t* hash_out_dev, int32_t* order_out_dev, int32_t k_cap,
+                         void* stream) {
+    if (!b || !out_dev) return fail(XR_ERR_INVALID, "xr_batch_rollout: null argument");
+    if (!b->loaded) return fail(XR_ERR_STATE, "xr_batch_rollout: load regions first");
+    if (group < -1 || group >= b->n_groups) return fail(XR_ERR_INVALID, "xr_batch_rollout: group %d outside -1..%d", group, b->n_groups - 1);
+    if (policy != XR_ROLLOUT_STOP && policy != XR_ROLLOUT_RANDOM) return fail(XR_ERR_INVALID, "xr_batch_rollout: unknown policy %d", policy);
+    if (prefix_dev && prefix_stride < 1) return fail(XR_ERR_INVALID, "xr_batch_rollout: prefix_stride %d < 1 with a prefix", prefix_stride);
+    if (max_plies < 0) return fail(XR_ERR_INVALID, "xr_batch_rollout: max_plies %d is negative", max_plies);
+    if (n_rollouts < 1 || n_rollouts > XR_ROLLOUT_MAX)
+        return fail(XR_ERR_RANGE, "xr_batch_rollout: n_rollouts %d outside 1..%d", n_rollouts, XR_ROLLOUT_MAX);
+    if (order_out_dev && k_cap < b->k_max) return fail(XR_ERR_RANGE, "xr_batch_rollout: k_cap %d < k_max %d", k_cap, b->k_max);
+    if (!b->lds_dist || b->cfg.stream_per_region)
+        return fail(XR_ERR_RANGE, "xr_batch_rollout: not available for batches whose distance field lives in HBM scratch (regions too large for LDS, "
+                                  "force_scratch_field) or with stream_per_region");
+    const int lo = group < 0 ? 0 : b->group_bounds[group];
+    const int rows = group < 0 ? b->cfg.n_envs : b->group_bounds[group + 1] - lo;
+    const int64_t tasks = (int64_t)rows * n_rollouts;
+    if (tasks >= ((int64_t)1 << 31)) return fail(XR_ERR_RANGE, "xr_batch_rollout: rows x n_rollouts does not fit 31 bits");
+    if (!xr_lookahead_occupancy || !xr_launch_rollout) return fail(XR_ERR_STATE, "xr_batch_rollout: rollout kernels not linked");
+    XR_HIP(hipSetDevice(b->cfg.device));
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const XrRouteVariant v = route_variant(b);
+    XR_HIP(look_grid_once(b, v));
+    xr_batch::LookPool& lp = b->look[group + 1];
+    if (const int32_t rc = look_pool(b, lp, st, "xr_batch_rollout")) return rc;
+    if (!lp.roll_ctr.p) {          // both banks start clean; every launch zeroes the other bank
+        if (lp.roll_ctr.alloc(2) != hipSuccess) return fail(XR_ERR_NOMEM, "xr_batch_rollout: hipMalloc of the claim counters failed");
+        if (hipMemsetAsync(lp.roll_ctr.p, 0, 2 * sizeof(uint32_t), st) != hipSuccess) {
+            lp.roll_ctr.release();
+            return fail(XR_ERR_HIP, "xr_batch_rollout: clearing the claim counters failed");
+        }
+    }
+    const XrBatchDev sh = shadow_view(b, lp);
+    uint32_t* const ctr = lp.roll_ctr.p + lp.roll_bank;
+    uint32_t* const next_ctr = lp.roll_ctr.p + (lp.roll_bank ^ 1);
+    lp.roll_bank ^= 1;
+    const int blocks = (int)std::min<int64_t>(b->look_grid, tasks);
+    XR_HIP(xr_launch_rollout(&b->dev, &sh, lo, (int)tasks, n_rollouts, policy, seed, prefix_dev, prefix_dev ? prefix_stride : 0, max_plies, ctr, next_ctr,
+                             out_dev, return_out_dev, hash_out_dev, order_out_dev, order_out_dev ? k_cap : 0, v, blocks, st));
     return XR_OK;
 }
 

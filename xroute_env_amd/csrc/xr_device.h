@@ -227,6 +227,10 @@ hipError_t xr_launch_lookahead_plan(const XrBatchDev* b, int env_lo, int rows, c
                                     int k_max, uint32_t* tasks, uint32_t* ctr, uint32_t* next_ctr, hipStream_t st) __attribute__((weak));
 hipError_t xr_launch_lookahead(const XrBatchDev* src, const XrBatchDev* shadow, int env_lo, const uint32_t* tasks, uint32_t* ctr, int32_t* out,
                                double* reward_out, int k_cap, int k_max, XrRouteVariant v, int blocks, hipStream_t st) __attribute__((weak));
+// rollouts (xr_rollout.h).  Weak for the same reason: xr_batch_rollout answers XR_ERR_STATE where it is not linked
+hipError_t xr_launch_rollout(const XrBatchDev* src, const XrBatchDev* shadow, int env_lo, int n_tasks, int n_rollouts, int policy, uint64_t seed,
+                             const int32_t* prefix, int prefix_stride, int max_plies, uint32_t* ctr, uint32_t* next_ctr, int32_t* out, double* return_out,
+                             uint64_t* hash_out, int32_t* order_out, int k_cap, XrRouteVariant v, int blocks, hipStream_t st) __attribute__((weak));
 hipError_t xr_launch_guide_masks(const XrBatchDev* b, uint8_t* masks, int k_max, hipStream_t st);
 hipError_t xr_launch_ingest_state(const XrBatchDev* b, const int16_t* owner_in, const uint64_t* legal_in, const int32_t* cum_in, hipStream_t st);
 hipError_t xr_launch_pack_state(const XrBatchDev* b, uint8_t* rows, int64_t row_bytes, int region_base, hipStream_t st);

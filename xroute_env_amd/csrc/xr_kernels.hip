@@ -12,6 +12,7 @@
 //                         launch draining route tasks and net-plane units
 //   xr_netplane_kernel, xr_netplane_stream_kernel   the writer of the split form (XR_OBS_SPLIT)
 //   xr_lookahead_plan_kernel + xr_lookahead_kernel   (xr_lookahead.h) every candidate net of every env routed in a throw-away copy of its slot
+//   xr_rollout_kernel            (xr_rollout.h) every env's episode played to its end, R times, in throw-away copies of its slot
 //   xr_random_action_kernel
 //
 // Integer / index work throughout: no MFMA.  What matters here is coalescing (every sweep is
@@ -885,14 +886,14 @@ __device__ __forceinline__ void xr_route_dispatch(const XrBatchDev& b, const int
 // ------------------------------------------------------------------------------------------------
 // random net-order policy: j-th legal net, j from a counter-based hash
 // ------------------------------------------------------------------------------------------------
-__global__ void xr_random_action_kernel(XrBatchDev b, int32_t* __restrict__ actions, uint64_t seed) {
-    const int e = b.env_base + blockIdx.x * blockDim.x + threadIdx.x;      // (env_base / env_count: one env group, xr_batch_random_actions_group)
-    if (e >= XR_ENV_END(b)) return;
-    const int nl = b.nlegal[e];
-    if (nl == 0) { actions[e] = 0; return; }
-    const uint64_t r = splitmix64(seed ^ splitmix64((uint64_t)e * 0x100000001B3ULL + (uint64_t)b.env_steps[e]));
+// The pick of one env: `row` is where its state is read (its own slot, or a shadow slot that holds a copy of it: xr_rollout.h), `env_id`
+// the global env index the hash is keyed with — together with the row's env_steps, which a real route advances and a rejected action does not
+__device__ __forceinline__ int xr_random_pick(const XrBatchDev& b, const int row, const int env_id, const uint64_t seed) {
+    const int nl = b.nlegal[row];
+    if (nl == 0) return 0;
+    const uint64_t r = splitmix64(seed ^ splitmix64((uint64_t)env_id * 0x100000001B3ULL + (uint64_t)b.env_steps[row]));
     int j = (int)(r % (uint64_t)nl);
-    const uint64_t* lw = b.legal + (int64_t)e * b.legal_words;
+    const uint64_t* lw = b.legal + (int64_t)row * b.legal_words;
     int act = 0;
     for (int w = 0; w < b.legal_words; w++) {
         uint64_t m = lw[w];
@@ -902,7 +903,13 @@ __global__ void xr_random_action_kernel(XrBatchDev b, int32_t* __restrict__ acti
         act = w * 64 + __ffsll((long long)m);     // 1-based bit position == 1-based net id
         break;
     }
-    actions[e] = act;
+    return act;
+}
+
+__global__ void xr_random_action_kernel(XrBatchDev b, int32_t* __restrict__ actions, uint64_t seed) {
+    const int e = b.env_base + blockIdx.x * blockDim.x + threadIdx.x;      // (env_base / env_count: one env group, xr_batch_random_actions_group)
+    if (e >= XR_ENV_END(b)) return;
+    actions[e] = xr_random_pick(b, e, e, seed);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -2160,6 +2167,7 @@ __global__ void __launch_bounds__(256) xr_expand_state_kernel(XrBatchDev b, cons
 }
 
 #include "xr_lookahead.h"
+#include "xr_rollout.h"
 
 // ------------------------------------------------------------------------------------------------
 // host-callable launchers (kept here so that only this TU needs the <<<>>> syntax)
@@ -2213,10 +2221,11 @@ hipError_t xr_launch_reset(const XrBatchDev* b, const uint8_t* mask, int rotate,
 
 hipError_t xr_route_set_max_lds(size_t bytes) {
     return xr_each_variant([&](auto L, auto Z) {
-        const void* fns[5] = {reinterpret_cast<const void*>(&xr_route_kernel<L.value, Z.value>), reinterpret_cast<const void*>(&xr_order_kernel<L.value, Z.value>),
+        const void* fns[6] = {reinterpret_cast<const void*>(&xr_route_kernel<L.value, Z.value>), reinterpret_cast<const void*>(&xr_order_kernel<L.value, Z.value>),
                               reinterpret_cast<const void*>(&xr_step_queue_kernel<L.value, Z.value>),
                               reinterpret_cast<const void*>(&xr_step_queue_u8_kernel<L.value, Z.value>),
-                              reinterpret_cast<const void*>(&xr_lookahead_kernel<L.value, Z.value>)};
+                              reinterpret_cast<const void*>(&xr_lookahead_kernel<L.value, Z.value>),
+                              reinterpret_cast<const void*>(&xr_rollout_kernel<L.value, Z.value>)};
         for (const void* fn : fns) {
             const hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
             if (e != hipSuccess) return e;
@@ -2276,6 +2285,18 @@ hipError_t xr_launch_lookahead(const XrBatchDev* src, const XrBatchDev* shadow, 
     const dim3 g(blocks), t(v.threads);
     xr_with_variant(v.lds_dist, v.zch, [&](auto L, auto Z) {
         hipLaunchKernelGGL((xr_lookahead_kernel<L.value, Z.value>), g, t, v.lds_bytes, st, *src, *shadow, env_lo, tasks, ctr, out, reward_out, k_cap, k_max);
+    });
+    return hipGetLastError();
+}
+
+// rollouts (xr_rollout.h): the persistent launch; task t = (row t / n_rollouts, rollout t % n_rollouts)
+hipError_t xr_launch_rollout(const XrBatchDev* src, const XrBatchDev* shadow, int env_lo, int n_tasks, int n_rollouts, int policy, uint64_t seed,
+                             const int32_t* prefix, int prefix_stride, int max_plies, uint32_t* ctr, uint32_t* next_ctr, int32_t* out, double* return_out,
+                             uint64_t* hash_out, int32_t* order_out, int k_cap, XrRouteVariant v, int blocks, hipStream_t st) {
+    const dim3 g(blocks), t(v.threads);
+    xr_with_variant(v.lds_dist, v.zch, [&](auto L, auto Z) {
+        hipLaunchKernelGGL((xr_rollout_kernel<L.value, Z.value>), g, t, v.lds_bytes, st, *src, *shadow, env_lo, n_tasks, n_rollouts, policy, seed, prefix,
+                           prefix_stride, max_plies, ctr, next_ctr, out, return_out, hash_out, order_out, k_cap);
     });
     return hipGetLastError();
 }

@@ -158,6 +158,44 @@ class XRouteVectorEnv:
         first = torch.where(reward == best, idx, torch.full_like(idx, k)).min(dim=1).values      # (argmax does not promise the first maximum)
         return torch.where(best.squeeze(1) == float("-inf"), torch.zeros_like(first), first + 1).to(torch.int32)
 
+    # ---- rollouts: every env's episode played to its end from the current state, the env untouched ---------------------------------
+    def rollout(self, n_rollouts: int, seed: int = 0, policy="random", prefix: Optional[torch.Tensor] = None, max_plies: int = 0,
+                group: Optional[int] = None):
+        """RegionBatch.rollout's dict {out, ret, hash, order}.  group None: the whole batch, after every group's outstanding work.  A
+        group: on that group's stream, ordered like lookahead(group); the group's event then covers it."""
+        if group is None:
+            self._join_groups()
+            return self.batch.rollout(n_rollouts, seed, policy, prefix, max_plies)
+        (g,) = self._groups_of(group)
+        s = self.group_streams[g]
+        s.wait_stream(torch.cuda.current_stream(self.device))
+        with torch.cuda.stream(s):
+            res = self.batch.rollout(n_rollouts, seed, policy, prefix, max_plies, group=g, stream=s)
+            self.group_events[g].record(s)
+        return res
+
+    def rollout_actions(self, n_rollouts: int, seed: int, group: Optional[int] = None) -> torch.Tensor:
+        """int32 actions [rows]: per env the first net of its best random rollout (the highest return of n_rollouts; the first maximum
+        on a tie); 0 for a done env, like random_actions."""
+        if group is None:
+            return self._first_of_best(self.rollout(n_rollouts, seed))
+        (g,) = self._groups_of(group)
+        res = self.rollout(n_rollouts, seed, group=g)
+        s = self.group_streams[g]
+        with torch.cuda.stream(s):
+            act = self._first_of_best(res)
+            self.group_events[g].record(s)
+        return act
+
+    @staticmethod
+    def _first_of_best(res) -> torch.Tensor:
+        ret, first = res["ret"], res["order"][:, :, 0]
+        best = ret.max(dim=1, keepdim=True).values
+        R = ret.shape[1]
+        idx = torch.arange(R, device=ret.device).expand_as(ret)
+        r = torch.where(ret == best, idx, torch.full_like(idx, R)).min(dim=1, keepdim=True).values      # (the first maximum)
+        return first.gather(1, r).squeeze(1).to(torch.int32)          # (a done env's orders are all 0)
+
     # ---- independent stepping of env groups -----------------------------------------------------------------------------
     def _groups_of(self, group):
         if not self.n_groups:
