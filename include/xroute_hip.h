@@ -498,6 +498,38 @@ int32_t xr_batch_rollout(xr_batch* b, int32_t group, int32_t n_rollouts, int32_t
                          int32_t* out_dev, double* return_out_dev, uint64_t* hash_out_dev,
                          int32_t* order_out_dev, int32_t k_cap, void* stream);
 
+/* ---- branch: env slots take other slots' state, on the device ---- */
+/* The primitive of every search that keeps more than one line of play (beam search, the tree expansion of the reference's MCTS trainer,
+ * baseline/xroute/trainer4/dispatcher.py:113-118): slot i continues from the state slot parent[i] is in now.  A permuted copy of the
+ * per-env rows that never leaves device memory; the copied state is valid by construction, so nothing is checked on the host.
+ *   group            -1: the whole batch, rows [0, n_envs).  >= 0: that env group; rows AND parent indices are relative to the group's
+ *                    first slot, as in xr_batch_lookahead, and the work is enqueued on `stream` only.
+ *   parent_dev       int32 [rows]: row i takes the state of row parent[i].  parent[i] < 0 or parent[i] == i: the slot keeps its state.
+ *                    parent[i] >= rows (out of range — for a group, also an index that is valid for the batch but outside the group):
+ *                    the slot keeps its state and gets XR_ENV_BAD_ACTION OR-ed into its status (XR_FETCH_STATUS) and its record's
+ *                    status; nothing else of it changes.
+ * Gather semantics: every read sees the state BEFORE the call, whatever the map is — a swap, a cycle, a chain, a fan-out of one slot to
+ * many (also from a slot that is itself overwritten, or flagged: its children see it without the flag); the map need not be injective.
+ * After the call every per-env row xr_batch_fetch returns for slot i — owner, legal, nlegal, cum, delta, reward, done, status, path,
+ * path_len, hash, region, replay, env_steps, record, sweeps, touched, whole rows — is byte-identical to what it returned for slot
+ * parent[i] before the call.  total_steps, the measured net classes and the regions are untouched.  A slot may take the state of a slot
+ * that plays another region: it then plays that region (region and replay travel with it).  A branched slot is a full env: stepped on, it
+ * does bit for bit what its parent would have done (hash chain, rotation, auto-reset); xr_batch_random_actions stays keyed by the slot's
+ * own index.
+ * Works for every router variant, the HBM-scratch forms (force_scratch_field included) and stream_per_region too: the router scratch is
+ * clean between routes, so the rows above are all the state a slot has.
+ * Contract.  A branch never synchronises: it only enqueues on `stream` (two launches: the parents of overwritten parents go to a staging
+ * pool, then every moved slot is written from its untouched parent or from staging; no launch reads and writes the same slot, and no
+ * workgroup ever waits for another).  It may allocate its private memory on the first call, per batch and per group: one staging row of
+ * every array above per row of the caller, rows x (2 n_max + 4 path_cap + 8 legal_words + 125) bytes, rounded up to 16 per array.
+ * Observation validity is dropped the way a state-changing call drops it: a whole-batch call drops every in-place buffer's (fp32 and
+ * uint8, batch-wide and per group), a group call that group's and the batch-wide one.  Branches of DIFFERENT groups may be in flight at
+ * once on different streams under the xr_batch_step_group concurrency contract (each group has its own staging); within one group (or
+ * for the whole batch) branches, steps, lookaheads and rollouts are ordered by the caller.
+ * Errors (the batch is untouched after any of them): XR_ERR_INVALID null b / parent_dev, or a group outside -1 .. n_groups - 1;
+ * XR_ERR_STATE before xr_batch_load_regions; XR_ERR_NOMEM when the staging pool cannot be allocated. */
+int32_t xr_batch_branch(xr_batch* b, int32_t group, const int32_t* parent_dev, void* stream);
+
 /* ---- XR-Maze v2: global-route guides (optional) ---------------------------------------------- */
 /* The reference's simulator runs with `-follow_guide 1` (ispd/ispd18_test1/run-net-ordering-training.tcl:3) on the guide file
  * it ships (ispd/ispd18_test1/ispd18_test1.input.guide: per net, rectangles per metal layer).  With xr_config.guide_cost > 0 a

@@ -34,6 +34,7 @@ SYMBOLS = [
     "xr_batch_step_observe_u8", "xr_batch_observation_u8",
     "xr_batch_lookahead",
     "xr_batch_rollout",
+    "xr_batch_branch",
     "xr_observation_from_records", "xr_proto_decode", "xr_proto_encode_response", "xr_proto_encode_request",
 ]
 
@@ -131,6 +132,7 @@ def lib():
     L.xr_batch_observation_u8.argtypes = [vp, vp, C.c_int64, C.c_int32, C.c_int32, vp]
     L.xr_batch_lookahead.argtypes = [vp, C.c_int32, vp, vp, C.c_int32, vp, vp]
     L.xr_batch_rollout.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32, C.c_uint64, vp, C.c_int32, C.c_int32, vp, vp, vp, vp, C.c_int32, vp]
+    L.xr_batch_branch.argtypes = [vp, C.c_int32, vp, vp]
     L.xr_batch_random_actions_group.argtypes = [vp, C.c_int32, vp, C.c_uint64, vp]
     L.xr_batch_fetch_group.argtypes = [vp, C.c_int32, C.c_int32, vp, C.c_size_t, vp]
     L.xr_agent_obstacle_tower_weights.argtypes = []

@@ -367,6 +367,25 @@ class RegionBatch:
                                                ptr["out"], ptr["return_out"], ptr["hash_out"], ptr["order_out"], k, self._stream_arg(stream)))
         return {"out": bufs["out"][0], "ret": bufs["return_out"][0], "hash": bufs["hash_out"][0], "order": bufs["order_out"][0]}
 
+    # ---- branch: env slots take other slots' state, on the device (xr_batch_branch) ----------------------------------------------
+    def branch(self, parent: torch.Tensor, group: Optional[int] = None, stream=None) -> None:
+        """Row i continues from the state row parent[i] is in now (int32 [rows] on the device; rows and indices relative to the group's
+        first slot when `group` is given): every per-env array fetch() returns is copied, gather semantics — every read sees the state
+        before the call, so swaps, cycles, chains and fan-outs are fine.  parent[i] < 0 or == i keeps the slot; parent[i] >= rows keeps
+        it and flags BAD_ACTION in its status.  Nothing leaves the device and nothing synchronises.  A slot may now play another region:
+        region_epoch is bumped."""
+        if group is None:
+            g, rows = -1, self.n_envs
+        else:
+            lo, hi = self.group_bounds(group)
+            g, rows = int(group), hi - lo
+        if not isinstance(parent, torch.Tensor) or parent.device != self.device or parent.dtype != torch.int32 or not parent.is_contiguous() \
+                or tuple(parent.shape) != (rows,):
+            raise ValueError(f"parent must be a contiguous int32 [{rows}] tensor on the batch device")
+        with torch.cuda.device(self.device):
+            _lib.check(self.L.xr_batch_branch(self._h, g, C.c_void_p(parent.data_ptr()), self._stream_arg(stream)))
+        self.region_epoch += 1
+
     def alloc_head(self) -> torch.Tensor:
         """[n_envs, 2*n_max] fp32 buffer for the compact-consumer step (planes 0..1 of every env)."""
         return torch.empty((self.n_envs, 2 * self.n_max), dtype=torch.float32, device=self.device)

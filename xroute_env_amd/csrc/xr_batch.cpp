@@ -166,6 +166,14 @@ struct xr_batch {
         XrBatchDev shadow{};
         void release() { mem.release(); tasks.release(); ctr.release(); roll_ctr.release(); bank = 0; roll_bank = 0; }
     } look[1 + XR_MAX_GROUPS];
+    // branch (xr_batch_branch): the staging pool of a caller — [0] the whole batch, [1 + g] env group g — allocated on its first branch: one
+    // row of every state array per row of the caller (a map may stage every row: a permutation without fixed points)
+    struct BranchPool {
+        DevBuf<uint8_t> mem;
+        int rows = 0;
+        XrBranchRows stg{};
+        void release() { mem.release(); rows = 0; }
+    } branch[1 + XR_MAX_GROUPS];
     int look_grid = 0;                          // workgroups of the persistent lookahead launch the chip holds at once (0: not asked yet)
     XrBatchDev dev{};
     ~xr_batch() {
@@ -965,6 +973,7 @@ int32_t xr_batch_load_regions(xr_batch* b, const xr_region_desc* regs, int32_t n
     b->n_cus = 0;
     b->route_slots = 0;
     for (xr_batch::LookPool& lp : b->look) lp.release();         // shadow slots are sized for the regions they were allocated under
+    for (xr_batch::BranchPool& bp : b->branch) bp.release();     // and so are the staging rows of xr_batch_branch
     b->look_grid = 0;
     b->guide_csr.release(); b->guide_box.release(); b->guide_mask.release(); b->guide_mask_bytes = 0;        // guides belong to the regions they were loaded for
     memset(&b->dev, 0, sizeof(b->dev));
@@ -1868,6 +1877,73 @@ int32_t xr_batch_rollout(xr_batch* b, int32_t group, int32_t n_rollouts, int32_t
     const int blocks = (int)std::min<int64_t>(b->look_grid, tasks);
     XR_HIP(xr_launch_rollout(&b->dev, &sh, lo, (int)tasks, n_rollouts, policy, seed, prefix_dev, prefix_dev ? prefix_stride : 0, max_plies, ctr, next_ctr,
                              out_dev, return_out_dev, hash_out_dev, order_out_dev, order_out_dev ? k_cap : 0, v, blocks, st));
+    return XR_OK;
+}
+
+// ---- branch ------------------------------------------------------------------------------------------------------------------------
+namespace {
+// bytes of one slot's state: the rows xr_batch_branch moves, each array of a staging pool starting on a 16-byte boundary
+size_t branch_carve(const xr_batch* b, size_t rows, uint8_t* m, XrBranchRows* out) {
+    size_t off = 0;
+    auto carve = [&](size_t row_bytes) { const size_t o = off; off = (off + rows * row_bytes + 15) & ~(size_t)15; return o; };
+    const size_t o_owner = carve((size_t)b->n_max * sizeof(int16_t)), o_path = carve((size_t)b->path_cap * sizeof(int32_t));
+    const size_t o_legal = carve((size_t)b->legal_words * sizeof(uint64_t)), o_reward = carve(sizeof(double)), o_hash = carve(sizeof(uint64_t));
+    const size_t o_steps = carve(sizeof(int64_t)), o_rec = carve(sizeof(XrStepRecord)), o_cum = carve(3 * sizeof(int32_t));
+    const size_t o_delta = carve(3 * sizeof(int32_t)), o_nlegal = carve(sizeof(int32_t)), o_status = carve(sizeof(int32_t));
+    const size_t o_plen = carve(sizeof(int32_t)), o_region = carve(sizeof(int32_t)), o_replay = carve(sizeof(int32_t));
+    const size_t o_sweeps = carve(sizeof(int32_t)), o_touched = carve(sizeof(int32_t)), o_done = carve(1);
+    if (out) {
+        XrBranchRows& r = *out;
+        r.owner = reinterpret_cast<int16_t*>(m + o_owner); r.path = reinterpret_cast<int32_t*>(m + o_path);
+        r.legal = reinterpret_cast<uint64_t*>(m + o_legal); r.reward = reinterpret_cast<double*>(m + o_reward);
+        r.hash = reinterpret_cast<uint64_t*>(m + o_hash); r.env_steps = reinterpret_cast<int64_t*>(m + o_steps);
+        r.records = reinterpret_cast<XrStepRecord*>(m + o_rec); r.cum = reinterpret_cast<int32_t*>(m + o_cum);
+        r.delta = reinterpret_cast<int32_t*>(m + o_delta); r.nlegal = reinterpret_cast<int32_t*>(m + o_nlegal);
+        r.status = reinterpret_cast<int32_t*>(m + o_status); r.path_len = reinterpret_cast<int32_t*>(m + o_plen);
+        r.env_region = reinterpret_cast<int32_t*>(m + o_region); r.env_replay = reinterpret_cast<int32_t*>(m + o_replay);
+        r.sweeps = reinterpret_cast<int32_t*>(m + o_sweeps); r.touched = reinterpret_cast<int32_t*>(m + o_touched); r.done = m + o_done;
+    }
+    return off;
+}
+}  // namespace
+
+int32_t xr_batch_branch(xr_batch* b, int32_t group, const int32_t* parent_dev, void* stream) {
+    if (!b || !parent_dev) return fail(XR_ERR_INVALID, "xr_batch_branch: null argument");
+    if (!b->loaded) return fail(XR_ERR_STATE, "xr_batch_branch: load regions first");
+    if (group < -1 || group >= b->n_groups) return fail(XR_ERR_INVALID, "xr_batch_branch: group %d outside -1..%d", group, b->n_groups - 1);
+    if (!xr_launch_branch) return fail(XR_ERR_STATE, "xr_batch_branch: branch kernels not linked");
+    const int lo = group < 0 ? 0 : b->group_bounds[group];
+    const int rows = group < 0 ? b->cfg.n_envs : b->group_bounds[group + 1] - lo;
+    XR_HIP(hipSetDevice(b->cfg.device));
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    xr_batch::BranchPool& bp = b->branch[group + 1];
+    if (bp.rows < rows) {              // the first branch of this caller (or its group has grown since: xr_batch_set_groups)
+        bp.release();
+        const size_t bytes = branch_carve(b, (size_t)rows, nullptr, nullptr);
+        if (bp.mem.alloc(bytes) != hipSuccess) {
+            bp.release();
+            return fail(XR_ERR_NOMEM, "xr_batch_branch: hipMalloc of %zu bytes of staging rows failed", bytes);
+        }
+        bp.rows = rows;
+        branch_carve(b, (size_t)rows, bp.mem.p, &bp.stg);
+    }
+    const XrBatchDev& d = b->dev;
+    XrBranchRows env{};
+    env.owner = d.owner; env.path = d.path; env.legal = d.legal; env.nlegal = d.nlegal; env.cum = d.cum; env.delta = d.delta;
+    env.status = d.status; env.path_len = d.path_len; env.env_region = d.env_region; env.env_replay = d.env_replay; env.sweeps = d.sweeps;
+    env.touched = d.touched; env.reward = d.reward; env.done = d.done; env.hash = d.hash; env.env_steps = d.env_steps; env.records = d.records;
+    // workgroups per row: about 4 KB of the two long rows each (one 16-byte vector per thread), fewer once the rows alone fill the chip
+    const size_t long_bytes = (size_t)b->n_max * sizeof(int16_t) + (size_t)b->path_cap * sizeof(int32_t);
+    int chunks = (int)std::min<size_t>(32, std::max<size_t>(1, long_bytes / 4096));
+    if ((int64_t)rows * chunks > 16384) chunks = std::max(1, 16384 / rows);
+    // the state of slots changes: no caller buffer holds their observation any more (a group call: the group's and the batch-wide one)
+    if (group < 0) {
+        drop_obs_valid(b);
+    } else {
+        b->obs_valid.clear();
+        b->group_valid[group].clear();
+    }
+    XR_HIP(xr_launch_branch(&env, &bp.stg, lo, rows, parent_dev, b->n_max, b->path_cap, b->legal_words, chunks, st));
     return XR_OK;
 }
 

@@ -191,6 +191,20 @@ struct XrBatchDev {
     uint8_t* obs_out_u8;
 };
 
+// The per-env rows that ARE the state of a slot (everything xr_batch_fetch returns per env): the batch's own arrays, or the rows of a staging
+// pool of xr_batch_branch (xr_branch.h)
+struct XrBranchRows {
+    int16_t* owner;          // [rows][n_max]
+    int32_t* path;           // [rows][path_cap]
+    uint64_t* legal;         // [rows][legal_words]
+    int32_t *nlegal, *cum, *delta, *status, *path_len, *env_region, *env_replay, *sweeps, *touched;
+    double* reward;
+    uint8_t* done;
+    uint64_t* hash;
+    int64_t* env_steps;
+    XrStepRecord* records;
+};
+
 // Which instantiation of the route / order / step-queue kernels a launch takes, and its launch shape (xr_kernels.hip maps
 // (lds_dist, zch) to <LDS_DIST, ZCH> in one place: xr_with_variant)
 struct XrRouteVariant {
@@ -231,6 +245,9 @@ hipError_t xr_launch_lookahead(const XrBatchDev* src, const XrBatchDev* shadow, 
 hipError_t xr_launch_rollout(const XrBatchDev* src, const XrBatchDev* shadow, int env_lo, int n_tasks, int n_rollouts, int policy, uint64_t seed,
                              const int32_t* prefix, int prefix_stride, int max_plies, uint32_t* ctr, uint32_t* next_ctr, int32_t* out, double* return_out,
                              uint64_t* hash_out, int32_t* order_out, int k_cap, XrRouteVariant v, int blocks, hipStream_t st) __attribute__((weak));
+// branch (xr_branch.h): both passes, in stream order.  Weak for the same reason: xr_batch_branch answers XR_ERR_STATE where it is not linked
+hipError_t xr_launch_branch(const XrBranchRows* env, const XrBranchRows* stg, int env_lo, int rows, const int32_t* parent, int n_max, int path_cap,
+                            int legal_words, int chunks, hipStream_t st) __attribute__((weak));
 hipError_t xr_launch_guide_masks(const XrBatchDev* b, uint8_t* masks, int k_max, hipStream_t st);
 hipError_t xr_launch_ingest_state(const XrBatchDev* b, const int16_t* owner_in, const uint64_t* legal_in, const int32_t* cum_in, hipStream_t st);
 hipError_t xr_launch_pack_state(const XrBatchDev* b, uint8_t* rows, int64_t row_bytes, int region_base, hipStream_t st);

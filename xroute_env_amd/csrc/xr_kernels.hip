@@ -13,6 +13,7 @@
 //   xr_netplane_kernel, xr_netplane_stream_kernel   the writer of the split form (XR_OBS_SPLIT)
 //   xr_lookahead_plan_kernel + xr_lookahead_kernel   (xr_lookahead.h) every candidate net of every env routed in a throw-away copy of its slot
 //   xr_rollout_kernel            (xr_rollout.h) every env's episode played to its end, R times, in throw-away copies of its slot
+//   xr_branch_kernel<0 / 1>      (xr_branch.h) env slots take other slots' state: parents of overwritten parents to staging, then every moved slot
 //   xr_random_action_kernel
 //
 // Integer / index work throughout: no MFMA.  What matters here is coalescing (every sweep is
@@ -2168,6 +2169,7 @@ __global__ void __launch_bounds__(256) xr_expand_state_kernel(XrBatchDev b, cons
 
 #include "xr_lookahead.h"
 #include "xr_rollout.h"
+#include "xr_branch.h"
 
 // ------------------------------------------------------------------------------------------------
 // host-callable launchers (kept here so that only this TU needs the <<<>>> syntax)
@@ -2298,6 +2300,15 @@ hipError_t xr_launch_rollout(const XrBatchDev* src, const XrBatchDev* shadow, in
         hipLaunchKernelGGL((xr_rollout_kernel<L.value, Z.value>), g, t, v.lds_bytes, st, *src, *shadow, env_lo, n_tasks, n_rollouts, policy, seed, prefix,
                            prefix_stride, max_plies, ctr, next_ctr, out, return_out, hash_out, order_out, k_cap);
     });
+    return hipGetLastError();
+}
+
+// branch (xr_branch.h): workgroup (i, c) = chunk c of row i; the stream orders the staging pass before the writing pass
+hipError_t xr_launch_branch(const XrBranchRows* env, const XrBranchRows* stg, int env_lo, int rows, const int32_t* parent, int n_max, int path_cap,
+                            int legal_words, int chunks, hipStream_t st) {
+    const dim3 g(rows, chunks), t(256);
+    hipLaunchKernelGGL(xr_branch_kernel<0>, g, t, 0, st, *env, *stg, env_lo, rows, parent, n_max, path_cap, legal_words);
+    hipLaunchKernelGGL(xr_branch_kernel<1>, g, t, 0, st, *env, *stg, env_lo, rows, parent, n_max, path_cap, legal_words);
     return hipGetLastError();
 }
 

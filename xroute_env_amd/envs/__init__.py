@@ -3,6 +3,7 @@
 `facade`      single-env gym-style classes carrying the names the reference registers / reserves
               (reference xroute_env/__init__.py:3-6, xroute_env/envs/*.py are empty stubs)
 `vector_env`  the batched form: B regions per call, everything stays on the device
+`beam`        beam search over net orderings: lookahead -> select -> branch -> step (`from xroute_env_amd.envs.beam import beam_search`)
 """
 from .facade import OrderingEvaluationEnv, OrderingTrainingEnv, StaticRegionEnv, XRouteEnv
 from .vector_env import XRouteVectorEnv

@@ -196,6 +196,36 @@ class XRouteVectorEnv:
         r = torch.where(ret == best, idx, torch.full_like(idx, R)).min(dim=1, keepdim=True).values      # (the first maximum)
         return first.gather(1, r).squeeze(1).to(torch.int32)          # (a done env's orders are all 0)
 
+    # ---- branch: slots take other slots' state on the device -------------------------------------------------------------------------
+    def branch(self, parent: torch.Tensor, group: Optional[int] = None) -> None:
+        """RegionBatch.branch: row i continues from the state of row parent[i] (int32 [rows] on the device, relative to the group's first
+        slot when `group` is given).  group None: the whole batch, after every group's outstanding work, as step().  A group: on that
+        group's stream, after the current stream and the group's last work; the group's event then covers it.  The env's record / done /
+        legal / region tensors are fetched again (the slots' rows moved); the observation buffer is not — the next step rewrites it in full,
+        because a branch drops the in-place validity."""
+        b = self.batch
+        if group is None:
+            self._join_groups()
+            b.branch(parent)
+            b.fetch("record", self.record)
+            b.fetch("done", self.done)
+            b.fetch("legal", self.legal)
+            b.fetch("region", self.region)
+            return
+        (g,) = self._groups_of(group)
+        lo, hi = b.group_bounds(g)
+        s = self.group_streams[g]
+        s.wait_stream(torch.cuda.current_stream(self.device))
+        with torch.cuda.stream(s):
+            b.branch(parent, group=g, stream=s)
+            b.fetch_group("record", g, self.record[lo:hi], stream=s)
+            b.fetch_group("done", g, self.done[lo:hi], stream=s)
+            b.fetch_group("legal", g, self.legal[lo:hi], stream=s)
+            b.fetch_group("region", g, self.region[lo:hi], stream=s)
+            self.group_events[g].record(s)
+        if isinstance(parent, torch.Tensor):
+            parent.record_stream(s)
+
     # ---- independent stepping of env groups -----------------------------------------------------------------------------
     def _groups_of(self, group):
         if not self.n_groups:
