@@ -225,7 +225,9 @@ __device__ __forceinline__ void xt_conv1_strips(const float* __restrict__ wgt, c
 
 // The same, four cells per thread as TWO packed sums (v_pk_fma_f32): a tap row's pairs (v0 v1) (v1 v2) (v2 v3) (v3 v4) (v4 v5) are five two-word LDS reads —
 // a read lands in an aligned register pair, so the pairs cost no moves — and feed six packed FMAs with the weight on both halves (scalar pairs): 11
-// instructions per tap row and four cells where the strips of three take 3 reads + 9 FMAs for three.  Same order of the sums (kd, kh, kw): same bits.
+// instructions per tap row and four cells where the strips of three take 3 reads + 9 FMAs for three.  Same order of the sums (kd, kh, kw) — not the same bits as the
+// strips: which multiply-adds are fused is the compiler's choice (`acc += w * v`), and in the strips it leaves the tail of some cells' sums as a packed multiply and
+// two adds; normalised vectors of different strip widths are up to 1.4e-6 apart (tests/test_gpu_tower_shapes.py).  A shape always runs one width: same input, same bits.
 template <bool RES, bool PACK>
 __device__ __forceinline__ void xt_conv1_pk4(const float* __restrict__ wgt, const float* in, float* out, int D, int H, int W, int tid, int nthr) {
     const int Hp = H + 2, Wp = (W + 2) | 1, rows = D * H, nstrip = rows * ((W + 3) >> 2);
