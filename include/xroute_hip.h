@@ -530,6 +530,72 @@ int32_t xr_batch_rollout(xr_batch* b, int32_t group, int32_t n_rollouts, int32_t
  * XR_ERR_STATE before xr_batch_load_regions; XR_ERR_NOMEM when the staging pool cannot be allocated. */
 int32_t xr_batch_branch(xr_batch* b, int32_t group, const int32_t* parent_dev, void* stream);
 
+/* ---- tree search: MCTS over net orderings, the tree on the device ---- */
+/* The search of the reference's MuZero / MCTS agent (baseline/xroute/self_route.py:341-371, 482-568, 571-613, re-routing per selection in
+ * trainer4/dispatcher.py:113-118) as ONE enqueue-only call: pUCT selection, evaluation by rollouts (xr_batch_rollout's kernel) and backup
+ * all run on the device, n_waves x n_par simulations per row, no host round trip per simulation.  A row is an env of the whole batch
+ * (group -1) or of one env group, as in xr_batch_lookahead.  "XR-Tree v1" (build-defined, as XR-Maze is):
+ *   Nodes.   One tree per row, rebuilt on every call.  A node is a set of nets routed after the env's current state, in path order; its
+ *            legal set is the env's legal set minus the nets of its path (selection needs no env state); a node with an empty legal set
+ *            is terminal.  Expanding a node allocates one child per legal net: one contiguous block in ascending net order out of the
+ *            row's pool of node_cap nodes.  A block that does not fit leaves the node unexpanded and sets XR_TREE_POOL_FULL in the row's
+ *            info.  The root (node 0) is expanded when the call starts.  Per node: real visits N, pending visits V, value sum W (double),
+ *            prior P (double).
+ *   Prior.   prior_dev: NULL, or fp32 [rows][k_cap] weights per net (index net - 1); an entry that is not finite or is < 0 counts as 0.
+ *            P(child) = w[net] / S, S = the sum of w over the parent's legal nets, added in ascending net order in double; S == 0 or
+ *            prior_dev NULL: P = 1 / count.  Softmax is the caller's business.
+ *   Table.   E[n] = (log((n + c_base + 1) / c_base) + c_init) * sqrt(n), computed on the HOST in double for n = 0 .. n_waves * n_par and
+ *            uploaded with the call (the kernels call no log and no sqrt); xr_tree_exploration_table returns the same numbers.
+ *   Waves.   A search is n_waves waves of n_par simulations; a wave is three enqueues: select, the rollout launch, backup.
+ *   Select.  Per row the lanes j = 0 .. n_par - 1 descend one after the other: from the root to the best child for as long as the node is
+ *            expanded; a lane stops at an unexpanded or terminal node, and expands an unexpanded non-terminal one if the pool has room.
+ *            Its path is the nets from the root to that node; it then adds 1 to V of every node of the path, the root included.  Score
+ *            of child c under parent p, with n = N + V:  u = (E[n_p] * P_c) / (double)(n_c + 1);  v = (N_c > 0 && max > min) ?
+ *            (W_c / N_c - min) / (max - min) : 0.0;  score = u + v.  The best child is the maximum under >, so a tie goes to the lowest
+ *            net.  Every operation is one IEEE double operation, rounded on its own (no contraction, no fast-math).
+ *   Evaluate. Simulation (w, j) is rollout j of one rollout launch over the rows: n_rollouts = n_par, XR_ROLLOUT_RANDOM, max_plies 0,
+ *            seed_w = seed + w * 0xD1B54A32D192ED03 (mod 2^64), the prefix = the wave's paths.  G is the rollout's return: the return of
+ *            the whole line from the env's current state (siblings share everything above them, so ordering them by G is ordering them
+ *            by reward + value); the rollout's order row is the simulation's complete ordering.
+ *   Backup.  Per row the simulations are taken in lane order (the order of the double additions is part of the spec).  On every node of
+ *            the path: N += 1, V -= 1, W += G.  Then min = fmin(min, G), max = fmax(max, G), and if G > best (strictly: the first wins)
+ *            best = G and the best order becomes the order row.  min / max / best start at +inf / -inf / -inf.
+ *   Done rows. A row whose env is done (no legal net) runs no simulation — tree search never looks through an auto-reset: visits all 0,
+ *            values all -inf, info all 0, best order all 0, best return -inf, every path empty, every return 0.0.
+ *   n_waves, n_par   >= 1; n_par <= XR_ROLLOUT_MAX, n_waves * n_par <= 65536.
+ *   node_cap         >= 1 nodes per row, the root included (1 + (n_waves * n_par + 1) * k_max always suffices: the root's block and
+ *                    one per simulation).
+ *   visits_out_dev   int32 [rows][k_cap]: N of the root's child of net n at index n - 1; 0 for every non-candidate.
+ *   value_out_dev    double [rows][k_cap]: W / N of that child, -inf where N == 0.
+ *   info_out_dev     int32 [rows][4] = {simulations, nodes_used (the root included), max_depth (the longest path), flags}.
+ *   best_order_out_dev / best_return_out_dev   NULL, or int32 [rows][k_cap] / double [rows]: the best line any simulation saw.
+ *   paths_out_dev / returns_out_dev   NULL, or int32 [rows][n_waves * n_par][k_cap] (ended by 0) / double [rows][n_waves * n_par]: every
+ *                    simulation's path and G, in (w, j) order.
+ * Cuts: no tree reuse between calls, no Dirichlet noise, no network inside the tree, no discounting, no HBM-scratch forms.
+ * Contract, the same as the rollout's.  A tree search never synchronises: it only enqueues on `stream` (a reset launch, the table's
+ * copy, then select / rollout / backup per wave; no workgroup waits for another one).  It may allocate its private memory
+ * on the first call, per batch and per group, and again when a call needs more than any before it:
+ * rows x (40 node_cap + 40 + n_par x (8 k_cap + 40)) bytes, each of its six arrays rounded up to 16, plus 8 x (n_waves x n_par + 1) bytes per distinct (c_init, c_base) for the table, plus
+ * lookahead's shadow slots and the rollout's claim counters where the caller has not used them yet.  It leaves NO TRACE in the batch: it
+ * plays in lookahead's shadow slots, every array xr_batch_fetch returns is only read, and the validity of the in-place observation
+ * buffers (fp32 and uint8, batch-wide and per group) is kept.  Searches of DIFFERENT groups may be in flight at once on different
+ * streams; within one group (or for the whole batch) searches, rollouts, lookaheads, branches and steps are ordered by the caller.
+ * Errors (the batch is untouched after any of them): XR_ERR_INVALID null b / visits_out_dev / value_out_dev / info_out_dev, a group
+ * outside -1 .. n_groups - 1, n_waves < 1, n_par < 1, a c_init that is not finite, a c_base that is not > 0 and finite; XR_ERR_STATE
+ * before xr_batch_load_regions, or where the kernels are not linked; XR_ERR_RANGE n_par > XR_ROLLOUT_MAX, n_waves * n_par > 65536,
+ * node_cap < 1, k_cap < k_max, and for the HBM-scratch router forms (force_scratch_field included) and stream_per_region, for the
+ * rollout's reason; XR_ERR_NOMEM when the private memory cannot be allocated.
+ * xr_tree_exploration_table (host only, no batch, no device): E[0 .. n] into out_host[n + 1].  XR_ERR_INVALID for a null out_host, n < 0
+ * or the knobs refused above. */
+#define XR_TREE_POOL_FULL 1
+#define XR_TREE_MAX_SIMS 65536
+int32_t xr_tree_exploration_table(double c_init, double c_base, int32_t n, double* out_host);
+int32_t xr_batch_tree_search(xr_batch* b, int32_t group, int32_t n_waves, int32_t n_par, uint64_t seed,
+                             const float* prior_dev, int32_t node_cap, double c_init, double c_base,
+                             int32_t* visits_out_dev, double* value_out_dev, int32_t k_cap, int32_t* info_out_dev,
+                             int32_t* best_order_out_dev, double* best_return_out_dev,
+                             int32_t* paths_out_dev, double* returns_out_dev, void* stream);
+
 /* ---- XR-Maze v2: global-route guides (optional) ---------------------------------------------- */
 /* The reference's simulator runs with `-follow_guide 1` (ispd/ispd18_test1/run-net-ordering-training.tcl:3) on the guide file
  * it ships (ispd/ispd18_test1/ispd18_test1.input.guide: per net, rectangles per metal layer).  With xr_config.guide_cost > 0 a

@@ -35,6 +35,7 @@ SYMBOLS = [
     "xr_batch_lookahead",
     "xr_batch_rollout",
     "xr_batch_branch",
+    "xr_tree_exploration_table", "xr_batch_tree_search",
     "xr_observation_from_records", "xr_proto_decode", "xr_proto_encode_response", "xr_proto_encode_request",
 ]
 
@@ -62,6 +63,19 @@ XR_MAX_GROUPS, XR_GROUP_INPLACE = 64, 1
 XR_OBS_U8_INPLACE = 1
 XR_ROUTER_SWEEP, XR_ROUTER_DIAL = 1, 2
 XR_ROLLOUT_STOP, XR_ROLLOUT_RANDOM, XR_ROLLOUT_MAX = 0, 1, 4096
+XR_TREE_POOL_FULL, XR_TREE_MAX_SIMS = 1, 65536
+
+
+def tree_seed(seed: int, w: int) -> int:
+    """seed_w of xr_batch_tree_search: the seed of the rollout launch that evaluates wave w (mod 2^64)."""
+    return (int(seed) + int(w) * 0xD1B54A32D192ED03) & (2 ** 64 - 1)
+
+
+def tree_exploration_table(c_init: float, c_base: float, n: int):
+    """E[0 .. n] of XR-Tree v1 as the library computes it on the host (xr_tree_exploration_table): a list of n + 1 floats."""
+    out = (C.c_double * (int(n) + 1))()
+    check(lib().xr_tree_exploration_table(float(c_init), float(c_base), int(n), out))
+    return list(out)
 
 
 def rollout_seed(seed: int, r: int) -> int:
@@ -133,6 +147,9 @@ def lib():
     L.xr_batch_lookahead.argtypes = [vp, C.c_int32, vp, vp, C.c_int32, vp, vp]
     L.xr_batch_rollout.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32, C.c_uint64, vp, C.c_int32, C.c_int32, vp, vp, vp, vp, C.c_int32, vp]
     L.xr_batch_branch.argtypes = [vp, C.c_int32, vp, vp]
+    L.xr_tree_exploration_table.argtypes = [C.c_double, C.c_double, C.c_int32, vp]
+    L.xr_batch_tree_search.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32, C.c_uint64, vp, C.c_int32, C.c_double, C.c_double,
+                                       vp, vp, C.c_int32, vp, vp, vp, vp, vp, vp]
     L.xr_batch_random_actions_group.argtypes = [vp, C.c_int32, vp, C.c_uint64, vp]
     L.xr_batch_fetch_group.argtypes = [vp, C.c_int32, C.c_int32, vp, C.c_size_t, vp]
     L.xr_agent_obstacle_tower_weights.argtypes = []

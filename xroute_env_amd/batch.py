@@ -7,6 +7,7 @@ libxroute_hip.so.  One process per GPU; see xroute_env_amd/dist.py for the shard
 from __future__ import annotations
 
 import ctypes as C
+import math
 from typing import List, Optional, Sequence
 
 import numpy as np
@@ -385,6 +386,58 @@ class RegionBatch:
         with torch.cuda.device(self.device):
             _lib.check(self.L.xr_batch_branch(self._h, g, C.c_void_p(parent.data_ptr()), self._stream_arg(stream)))
         self.region_epoch += 1
+
+    # ---- tree search: MCTS over net orderings, the tree on the device (xr_batch_tree_search) ------------------------------------------
+    def tree_search(self, n_waves: int, n_par: int, seed: int = 0, prior: Optional[torch.Tensor] = None, node_cap: Optional[int] = None,
+                    c_init: float = 1.25, c_base: float = 19652.0, group: Optional[int] = None, stream=None, trace: bool = False):
+        """XR-Tree v1 (include/xroute_hip.h) from the state every env is in now: n_waves waves of n_par simulations per row, each a pUCT
+        descent of the row's tree, a random rollout below the selected node and a backup — one enqueue-only call; the batch is left
+        exactly as it was.  prior: None (uniform) or float32 [rows, k_max] weights per net (not finite or < 0 counts as 0; softmax is the
+        caller's business).  node_cap: nodes per row, default 1 + n_waves * n_par * k_max (1 + (n_waves * n_par + 1) * k_max always suffices).  Returns a dict of device
+        tensors: `visits` int32 [rows, k_max] (N of the root's child of net n at n - 1), `value` float64 [rows, k_max] (W / N, -inf
+        where N == 0), `info` int32 [rows, 4] = {simulations, nodes_used, max_depth, flags (XR_TREE_POOL_FULL)}, `best_order` int32
+        [rows, k_max] and `best_return` float64 [rows] (the best line any simulation saw); with trace=True also `paths` int32 [rows,
+        n_waves * n_par, k_max] and `returns` float64 [rows, n_waves * n_par], every simulation in (wave, lane) order.  A done env holds
+        the empty result.  group: an env group (rows = its slots, enqueued on `stream`); None: the whole batch."""
+        if group is None:
+            g, rows = -1, self.n_envs
+        else:
+            lo, hi = self.group_bounds(group)
+            g, rows = int(group), hi - lo
+        W, P = int(n_waves), int(n_par)
+        if W < 1:
+            raise ValueError(f"n_waves must be >= 1, got {n_waves}")
+        if not 1 <= P <= _lib.XR_ROLLOUT_MAX:
+            raise ValueError(f"n_par must be in 1..{_lib.XR_ROLLOUT_MAX}, got {n_par}")
+        if W * P > _lib.XR_TREE_MAX_SIMS:
+            raise ValueError(f"n_waves x n_par must be <= {_lib.XR_TREE_MAX_SIMS}, got {W * P}")
+        ci, cb = float(c_init), float(c_base)
+        if not math.isfinite(ci):
+            raise ValueError(f"c_init must be finite, got {c_init}")
+        if not (math.isfinite(cb) and cb > 0):
+            raise ValueError(f"c_base must be finite and > 0, got {c_base}")
+        k = max(int(self.k_max), 1)
+        cap = 1 + W * P * k if node_cap is None else int(node_cap)
+        if not 1 <= cap < 2 ** 31:
+            raise ValueError(f"node_cap must be in 1..2^31 - 1, got {node_cap}")
+        pp = None
+        if prior is not None:
+            if not isinstance(prior, torch.Tensor) or prior.device != self.device or prior.dtype != torch.float32 or not prior.is_contiguous() \
+                    or tuple(prior.shape) != (rows, k):
+                raise ValueError(f"prior must be a contiguous float32 [{rows}, {k}] tensor on the batch device")
+            pp = C.c_void_p(prior.data_ptr())
+        shapes = {"visits": (torch.int32, (rows, k)), "value": (torch.float64, (rows, k)), "info": (torch.int32, (rows, 4)),
+                  "best_order": (torch.int32, (rows, k)), "best_return": (torch.float64, (rows,))}
+        if trace:
+            shapes.update(paths=(torch.int32, (rows, W * P, k)), returns=(torch.float64, (rows, W * P)))
+        with torch.cuda.stream(stream if stream is not None else torch.cuda.current_stream(self.device)):
+            res = {n: torch.empty(shp, dtype=dt, device=self.device) for n, (dt, shp) in shapes.items()}
+        ptr = {n: C.c_void_p(t.data_ptr()) for n, t in res.items()}
+        with torch.cuda.device(self.device):
+            _lib.check(self.L.xr_batch_tree_search(self._h, g, W, P, C.c_uint64(int(seed) & (2 ** 64 - 1)), pp, cap, ci, cb, ptr["visits"],
+                                                   ptr["value"], k, ptr["info"], ptr["best_order"], ptr["best_return"], ptr.get("paths"),
+                                                   ptr.get("returns"), self._stream_arg(stream)))
+        return res
 
     def alloc_head(self) -> torch.Tensor:
         """[n_envs, 2*n_max] fp32 buffer for the compact-consumer step (planes 0..1 of every env)."""

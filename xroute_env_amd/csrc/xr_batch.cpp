@@ -5,11 +5,13 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <cmath>
 #include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <map>
+#include <memory>
 #include <new>
 #include <string>
 #include <vector>
@@ -174,6 +176,19 @@ struct xr_batch {
         XrBranchRows stg{};
         void release() { mem.release(); rows = 0; }
     } branch[1 + XR_MAX_GROUPS];
+    // tree search (xr_batch_tree_search): the private memory of a caller, indexed like look[] — the trees, the search state of every row
+    // and one wave's paths, orders, rollout records and returns in one allocation that only ever grows; and the exploration tables it has
+    // uploaded, one per (c_init, c_base), each with the host copy its asynchronous upload reads (never rewritten, so no call waits for it)
+    struct TreeTable {
+        double c_init = 0, c_base = 0;
+        std::vector<double> host;
+        DevBuf<double> dev;
+    };
+    struct TreePool {
+        DevBuf<uint8_t> mem;
+        std::vector<std::unique_ptr<TreeTable>> tables;
+        void release() { mem.release(); tables.clear(); }
+    } tree[1 + XR_MAX_GROUPS];
     int look_grid = 0;                          // workgroups of the persistent lookahead launch the chip holds at once (0: not asked yet)
     XrBatchDev dev{};
     ~xr_batch() {
@@ -974,6 +989,7 @@ int32_t xr_batch_load_regions(xr_batch* b, const xr_region_desc* regs, int32_t n
     b->route_slots = 0;
     for (xr_batch::LookPool& lp : b->look) lp.release();         // shadow slots are sized for the regions they were allocated under
     for (xr_batch::BranchPool& bp : b->branch) bp.release();     // and so are the staging rows of xr_batch_branch
+    for (xr_batch::TreePool& tp : b->tree) tp.release();
     b->look_grid = 0;
     b->guide_csr.release(); b->guide_box.release(); b->guide_mask.release(); b->guide_mask_bytes = 0;        // guides belong to the regions they were loaded for
     memset(&b->dev, 0, sizeof(b->dev));
@@ -1877,6 +1893,118 @@ int32_t xr_batch_rollout(xr_batch* b, int32_t group, int32_t n_rollouts, int32_t
     const int blocks = (int)std::min<int64_t>(b->look_grid, tasks);
     XR_HIP(xr_launch_rollout(&b->dev, &sh, lo, (int)tasks, n_rollouts, policy, seed, prefix_dev, prefix_dev ? prefix_stride : 0, max_plies, ctr, next_ctr,
                              out_dev, return_out_dev, hash_out_dev, order_out_dev, order_out_dev ? k_cap : 0, v, blocks, st));
+    return XR_OK;
+}
+
+// ---- tree search -------------------------------------------------------------------------------------------------------------------
+namespace {
+bool tree_knobs_ok(double c_init, double c_base) { return std::isfinite(c_init) && std::isfinite(c_base) && c_base > 0.0; }
+
+// E[n] of XR-Tree v1, one IEEE operation after the other
+void tree_table_fill(double c_init, double c_base, int64_t from, int64_t to, double* out) {
+    for (int64_t n = from; n <= to; n++) {
+        const double x = ((double)n + c_base + 1.0) / c_base;
+        out[n - from] = (std::log(x) + c_init) * std::sqrt((double)n);
+    }
+}
+}  // namespace
+
+int32_t xr_tree_exploration_table(double c_init, double c_base, int32_t n, double* out_host) {
+    if (!out_host || n < 0) return fail(XR_ERR_INVALID, "xr_tree_exploration_table: null out_host or n %d < 0", n);
+    if (!tree_knobs_ok(c_init, c_base)) return fail(XR_ERR_INVALID, "xr_tree_exploration_table: c_init must be finite and c_base finite and > 0");
+    tree_table_fill(c_init, c_base, 0, n, out_host);
+    return XR_OK;
+}
+
+int32_t xr_batch_tree_search(xr_batch* b, int32_t group, int32_t n_waves, int32_t n_par, uint64_t seed, const float* prior_dev, int32_t node_cap,
+                             double c_init, double c_base, int32_t* visits_out_dev, double* value_out_dev, int32_t k_cap, int32_t* info_out_dev,
+                             int32_t* best_order_out_dev, double* best_return_out_dev, int32_t* paths_out_dev, double* returns_out_dev, void* stream) {
+    if (!b || !visits_out_dev || !value_out_dev || !info_out_dev) return fail(XR_ERR_INVALID, "xr_batch_tree_search: null argument");
+    if (!b->loaded) return fail(XR_ERR_STATE, "xr_batch_tree_search: load regions first");
+    if (group < -1 || group >= b->n_groups) return fail(XR_ERR_INVALID, "xr_batch_tree_search: group %d outside -1..%d", group, b->n_groups - 1);
+    if (n_waves < 1) return fail(XR_ERR_INVALID, "xr_batch_tree_search: n_waves %d < 1", n_waves);
+    if (n_par < 1) return fail(XR_ERR_INVALID, "xr_batch_tree_search: n_par %d < 1", n_par);
+    if (!std::isfinite(c_init)) return fail(XR_ERR_INVALID, "xr_batch_tree_search: c_init is not finite");
+    if (!tree_knobs_ok(c_init, c_base)) return fail(XR_ERR_INVALID, "xr_batch_tree_search: c_base must be finite and > 0");
+    if (n_par > XR_ROLLOUT_MAX) return fail(XR_ERR_RANGE, "xr_batch_tree_search: n_par %d above %d", n_par, XR_ROLLOUT_MAX);
+    if ((int64_t)n_waves * n_par > XR_TREE_MAX_SIMS)
+        return fail(XR_ERR_RANGE, "xr_batch_tree_search: n_waves x n_par = %lld simulations above %d", (long long)n_waves * n_par, XR_TREE_MAX_SIMS);
+    if (node_cap < 1) return fail(XR_ERR_RANGE, "xr_batch_tree_search: node_cap %d < 1", node_cap);
+    if (k_cap < b->k_max) return fail(XR_ERR_RANGE, "xr_batch_tree_search: k_cap %d < k_max %d", k_cap, b->k_max);
+    if (!b->lds_dist || b->cfg.stream_per_region)
+        return fail(XR_ERR_RANGE, "xr_batch_tree_search: not available for batches whose distance field lives in HBM scratch (regions too large for LDS, "
+                                  "force_scratch_field) or with stream_per_region");
+    const int lo = group < 0 ? 0 : b->group_bounds[group];
+    const int rows = group < 0 ? b->cfg.n_envs : b->group_bounds[group + 1] - lo;
+    const int64_t tasks = (int64_t)rows * n_par;
+    if (tasks >= ((int64_t)1 << 31)) return fail(XR_ERR_RANGE, "xr_batch_tree_search: rows x n_par does not fit 31 bits");
+    if (!xr_lookahead_occupancy || !xr_launch_rollout || !xr_launch_tree_reset || !xr_launch_tree_select || !xr_launch_tree_backup)
+        return fail(XR_ERR_STATE, "xr_batch_tree_search: tree search kernels not linked");
+    if (k_cap < 1) k_cap = 1;
+    const int n_sims = n_waves * n_par;
+    // the private memory: six arrays in one allocation, each starting on a 16-byte boundary
+    if ((double)rows * ((double)node_cap * sizeof(XrTreeNode) + (double)n_par * (8.0 * k_cap + 40.0) + 64.0) > 1e15)
+        return fail(XR_ERR_NOMEM, "xr_batch_tree_search: %d rows x %d nodes do not fit any device", rows, node_cap);
+    size_t off = 0;
+    auto carve = [&](size_t bytes) { const size_t o = off; off = (off + bytes + 15) & ~(size_t)15; return o; };
+    const size_t R = (size_t)rows, P = (size_t)n_par, K = (size_t)k_cap;
+    const size_t o_nodes = carve(R * (size_t)node_cap * sizeof(XrTreeNode)), o_rs = carve(R * sizeof(XrTreeRow));
+    const size_t o_prefix = carve(R * P * K * sizeof(int32_t)), o_order = carve(R * P * K * sizeof(int32_t));
+    const size_t o_rec = carve(R * P * 8 * sizeof(int32_t)), o_ret = carve(R * P * sizeof(double));
+    XR_HIP(hipSetDevice(b->cfg.device));
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const XrRouteVariant v = route_variant(b);
+    XR_HIP(look_grid_once(b, v));
+    xr_batch::LookPool& lp = b->look[group + 1];
+    if (const int32_t rc = look_pool(b, lp, st, "xr_batch_tree_search")) return rc;
+    if (!lp.roll_ctr.p) {          // (as xr_batch_rollout: both banks start clean; every launch zeroes the other bank)
+        if (lp.roll_ctr.alloc(2) != hipSuccess) return fail(XR_ERR_NOMEM, "xr_batch_tree_search: hipMalloc of the claim counters failed");
+        if (hipMemsetAsync(lp.roll_ctr.p, 0, 2 * sizeof(uint32_t), st) != hipSuccess) {
+            lp.roll_ctr.release();
+            return fail(XR_ERR_HIP, "xr_batch_tree_search: clearing the claim counters failed");
+        }
+    }
+    xr_batch::TreePool& tp = b->tree[group + 1];
+    if (tp.mem.n < off && tp.mem.alloc(off) != hipSuccess) {
+        tp.mem.release();
+        return fail(XR_ERR_NOMEM, "xr_batch_tree_search: hipMalloc of %zu bytes of trees failed", off);
+    }
+    xr_batch::TreeTable* tab = nullptr;
+    for (auto& t : tp.tables)
+        if (t->c_init == c_init && t->c_base == c_base && t->host.size() >= (size_t)n_sims + 1) tab = t.get();
+    if (!tab) {
+        std::unique_ptr<xr_batch::TreeTable> t(new (std::nothrow) xr_batch::TreeTable);
+        if (!t) return fail(XR_ERR_NOMEM, "xr_batch_tree_search: no host memory for the exploration table");
+        t->c_init = c_init; t->c_base = c_base;
+        t->host.resize((size_t)n_sims + 1);
+        tree_table_fill(c_init, c_base, 0, n_sims, t->host.data());
+        if (t->dev.alloc(t->host.size()) != hipSuccess) return fail(XR_ERR_NOMEM, "xr_batch_tree_search: hipMalloc of the exploration table failed");
+        XR_HIP(hipMemcpyAsync(t->dev.p, t->host.data(), t->host.size() * sizeof(double), hipMemcpyHostToDevice, st));
+        tab = t.get();          // (a shorter table of the same knobs stays: a launch in flight may read it)
+        tp.tables.push_back(std::move(t));
+    }
+    uint8_t* const m = tp.mem.p;
+    XrTreeDev t{};
+    t.nodes = reinterpret_cast<XrTreeNode*>(m + o_nodes); t.rs = reinterpret_cast<XrTreeRow*>(m + o_rs);
+    t.prefix = reinterpret_cast<int32_t*>(m + o_prefix); t.order = reinterpret_cast<int32_t*>(m + o_order);
+    t.ret = reinterpret_cast<double*>(m + o_ret);
+    int32_t* const rec = reinterpret_cast<int32_t*>(m + o_rec);
+    t.E = tab->dev.p; t.prior = prior_dev;
+    t.node_cap = node_cap; t.n_par = n_par; t.k_cap = k_cap; t.n_sims = n_sims; t.env_lo = lo;
+    t.visits_out = visits_out_dev; t.value_out = value_out_dev; t.info_out = info_out_dev; t.best_order_out = best_order_out_dev;
+    t.best_return_out = best_return_out_dev; t.paths_out = paths_out_dev; t.returns_out = returns_out_dev;
+    const XrBatchDev sh = shadow_view(b, lp);
+    const int blocks = (int)std::min<int64_t>(b->look_grid, tasks);
+    XR_HIP(xr_launch_tree_reset(&b->dev, &t, rows, st));
+    for (int w = 0; w < n_waves; w++) {
+        XR_HIP(xr_launch_tree_select(&b->dev, &t, rows, w, st));
+        uint32_t* const ctr = lp.roll_ctr.p + lp.roll_bank;
+        uint32_t* const next_ctr = lp.roll_ctr.p + (lp.roll_bank ^ 1);
+        lp.roll_bank ^= 1;
+        XR_HIP(xr_launch_rollout(&b->dev, &sh, lo, (int)tasks, n_par, XR_ROLLOUT_RANDOM, seed + (uint64_t)w * 0xD1B54A32D192ED03ULL, t.prefix, k_cap, 0, ctr,
+                                 next_ctr, rec, t.ret, nullptr, t.order, k_cap, v, blocks, st));
+        XR_HIP(xr_launch_tree_backup(&b->dev, &t, rows, w, w == n_waves - 1 ? 1 : 0, st));
+    }
     return XR_OK;
 }
 

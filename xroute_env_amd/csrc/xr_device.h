@@ -205,6 +205,38 @@ struct XrBranchRows {
     XrStepRecord* records;
 };
 
+// Tree search (xr_tree.h, xr_batch_tree_search).  One node of a row's tree: a set of nets routed after the env's current state
+struct XrTreeNode {
+    double W, P;             // value sum of the real visits; prior
+    int32_t N, V;            // real visits; pending visits (selected in this wave, not backed up yet)
+    int32_t first, count;    // the children: nodes [first, first + count) of the row's pool, ascending net order (first < 0: unexpanded)
+    int32_t net, pad;        // the net that leads here from the parent (0: the root)
+};
+static_assert(sizeof(XrTreeNode) == 40, "XrTreeNode layout");
+struct XrTreeRow {
+    double mn, mx, best;     // smallest / largest / best return backed up so far
+    int32_t used, max_depth, flags, pad;
+};
+static_assert(sizeof(XrTreeRow) == 40, "XrTreeRow layout");
+// what the three tree kernels share, passed by value: the caller's private memory, the call's shape, the caller's buffers
+struct XrTreeDev {
+    XrTreeNode* nodes;       // [rows][node_cap]
+    XrTreeRow* rs;           // [rows]
+    int32_t* prefix;         // [rows][n_par][k_cap] the paths of the current wave, each ended by 0: the rollout launch's prefix
+    int32_t* order;          // [rows][n_par][k_cap] the rollout launch's order rows
+    double* ret;             // [rows][n_par] its returns
+    const double* E;         // [n_sims + 1] exploration table
+    const float* prior;      // null, or [rows][k_cap]
+    int32_t node_cap, n_par, k_cap, n_sims, env_lo;
+    int32_t* visits_out;
+    double* value_out;
+    int32_t* info_out;
+    int32_t* best_order_out;
+    double* best_return_out;
+    int32_t* paths_out;
+    double* returns_out;
+};
+
 // Which instantiation of the route / order / step-queue kernels a launch takes, and its launch shape (xr_kernels.hip maps
 // (lds_dist, zch) to <LDS_DIST, ZCH> in one place: xr_with_variant)
 struct XrRouteVariant {
@@ -248,6 +280,10 @@ hipError_t xr_launch_rollout(const XrBatchDev* src, const XrBatchDev* shadow, in
 // branch (xr_branch.h): both passes, in stream order.  Weak for the same reason: xr_batch_branch answers XR_ERR_STATE where it is not linked
 hipError_t xr_launch_branch(const XrBranchRows* env, const XrBranchRows* stg, int env_lo, int rows, const int32_t* parent, int n_max, int path_cap,
                             int legal_words, int chunks, hipStream_t st) __attribute__((weak));
+// tree search (xr_tree.h).  Weak for the same reason: xr_batch_tree_search answers XR_ERR_STATE where they are not linked
+hipError_t xr_launch_tree_reset(const XrBatchDev* src, const XrTreeDev* t, int rows, hipStream_t st) __attribute__((weak));
+hipError_t xr_launch_tree_select(const XrBatchDev* src, const XrTreeDev* t, int rows, int wave, hipStream_t st) __attribute__((weak));
+hipError_t xr_launch_tree_backup(const XrBatchDev* src, const XrTreeDev* t, int rows, int wave, int last, hipStream_t st) __attribute__((weak));
 hipError_t xr_launch_guide_masks(const XrBatchDev* b, uint8_t* masks, int k_max, hipStream_t st);
 hipError_t xr_launch_ingest_state(const XrBatchDev* b, const int16_t* owner_in, const uint64_t* legal_in, const int32_t* cum_in, hipStream_t st);
 hipError_t xr_launch_pack_state(const XrBatchDev* b, uint8_t* rows, int64_t row_bytes, int region_base, hipStream_t st);

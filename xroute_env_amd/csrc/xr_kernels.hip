@@ -14,6 +14,7 @@
 //   xr_lookahead_plan_kernel + xr_lookahead_kernel   (xr_lookahead.h) every candidate net of every env routed in a throw-away copy of its slot
 //   xr_rollout_kernel            (xr_rollout.h) every env's episode played to its end, R times, in throw-away copies of its slot
 //   xr_branch_kernel<0 / 1>      (xr_branch.h) env slots take other slots' state: parents of overwritten parents to staging, then every moved slot
+//   xr_tree_reset / select / backup_kernel   (xr_tree.h) pUCT over net orderings with the tree in device memory, one wavefront per row
 //   xr_random_action_kernel
 //
 // Integer / index work throughout: no MFMA.  What matters here is coalescing (every sweep is
@@ -2169,6 +2170,7 @@ __global__ void __launch_bounds__(256) xr_expand_state_kernel(XrBatchDev b, cons
 
 #include "xr_lookahead.h"
 #include "xr_rollout.h"
+#include "xr_tree.h"
 #include "xr_branch.h"
 
 // ------------------------------------------------------------------------------------------------
@@ -2309,6 +2311,23 @@ hipError_t xr_launch_branch(const XrBranchRows* env, const XrBranchRows* stg, in
     const dim3 g(rows, chunks), t(256);
     hipLaunchKernelGGL(xr_branch_kernel<0>, g, t, 0, st, *env, *stg, env_lo, rows, parent, n_max, path_cap, legal_words);
     hipLaunchKernelGGL(xr_branch_kernel<1>, g, t, 0, st, *env, *stg, env_lo, rows, parent, n_max, path_cap, legal_words);
+    return hipGetLastError();
+}
+
+// tree search (xr_tree.h): one wavefront per row.  select's dynamic LDS: the path's net mask, nodes and nets
+hipError_t xr_launch_tree_reset(const XrBatchDev* src, const XrTreeDev* t, int rows, hipStream_t st) {
+    hipLaunchKernelGGL(xr_tree_reset_kernel, dim3(rows), dim3(64), 0, st, *src, *t);
+    return hipGetLastError();
+}
+
+hipError_t xr_launch_tree_select(const XrBatchDev* src, const XrTreeDev* t, int rows, int wave, hipStream_t st) {
+    const size_t lds = (size_t)src->legal_words * sizeof(uint64_t) + (2 * (size_t)t->k_cap + 1) * sizeof(int32_t);
+    hipLaunchKernelGGL(xr_tree_select_kernel, dim3(rows), dim3(64), lds, st, *src, *t, wave);
+    return hipGetLastError();
+}
+
+hipError_t xr_launch_tree_backup(const XrBatchDev* src, const XrTreeDev* t, int rows, int wave, int last, hipStream_t st) {
+    hipLaunchKernelGGL(xr_tree_backup_kernel, dim3(rows), dim3(64), 0, st, *src, *t, wave, last);
     return hipGetLastError();
 }
 

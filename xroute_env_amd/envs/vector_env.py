@@ -226,6 +226,50 @@ class XRouteVectorEnv:
         if isinstance(parent, torch.Tensor):
             parent.record_stream(s)
 
+    # ---- tree search: MCTS over net orderings from the current state, the env untouched ------------------------------------------
+    def tree_search(self, n_waves: int, n_par: int, seed: int = 0, prior: Optional[torch.Tensor] = None, node_cap: Optional[int] = None,
+                    c_init: float = 1.25, c_base: float = 19652.0, group: Optional[int] = None, trace: bool = False):
+        """RegionBatch.tree_search's dict {visits, value, info, best_order, best_return[, paths, returns]}.  group None: the whole batch,
+        after every group's outstanding work.  A group: on that group's stream, ordered like rollout(group); the group's event then
+        covers it."""
+        if group is None:
+            self._join_groups()
+            return self.batch.tree_search(n_waves, n_par, seed, prior, node_cap, c_init, c_base, trace=trace)
+        (g,) = self._groups_of(group)
+        s = self.group_streams[g]
+        s.wait_stream(torch.cuda.current_stream(self.device))
+        with torch.cuda.stream(s):
+            res = self.batch.tree_search(n_waves, n_par, seed, prior, node_cap, c_init, c_base, group=g, stream=s, trace=trace)
+            self.group_events[g].record(s)
+        return res
+
+    def tree_actions(self, n_waves: int, n_par: int, seed: int = 0, prior: Optional[torch.Tensor] = None, node_cap: Optional[int] = None,
+                     c_init: float = 1.25, c_base: float = 19652.0, group: Optional[int] = None) -> torch.Tensor:
+        """int32 actions [rows]: per env the most visited child of its search's root; ties go to the higher value, then to the lower
+        net; 0 for a done env, like random_actions.  (A root that did not fit node_cap has no child: the first net of the best line.)"""
+        if group is None:
+            return self._most_visited(self.tree_search(n_waves, n_par, seed, prior, node_cap, c_init, c_base))
+        (g,) = self._groups_of(group)
+        res = self.tree_search(n_waves, n_par, seed, prior, node_cap, c_init, c_base, group=g)
+        s = self.group_streams[g]
+        with torch.cuda.stream(s):
+            act = self._most_visited(res)
+            self.group_events[g].record(s)
+        return act
+
+    @staticmethod
+    def _most_visited(res) -> torch.Tensor:
+        visits, value = res["visits"], res["value"]
+        k = visits.shape[1]
+        top = visits.max(dim=1, keepdim=True).values
+        cand = (visits == top) & (visits > 0)
+        val = torch.where(cand, value, torch.full_like(value, float("-inf")))
+        best = val.max(dim=1, keepdim=True).values
+        idx = torch.arange(k, device=visits.device).expand_as(visits)
+        first = torch.where(cand & (val == best), idx, torch.full_like(idx, k)).min(dim=1).values          # (the lowest net of the tie)
+        # no visited child: a done env (its best order is all 0), or a pool too small for the root (the first net of the best line seen)
+        return torch.where(first == k, res["best_order"][:, 0].to(first.dtype), first + 1).to(torch.int32)
+
     # ---- independent stepping of env groups -----------------------------------------------------------------------------
     def _groups_of(self, group):
         if not self.n_groups:
