@@ -1,5 +1,6 @@
 // Device write-bandwidth probe: what a pure-write kernel can sustain on this GPU as a function of footprint and of
-// the store pattern.  Build: hipcc --offload-arch=gfx950 -O3 -o write_bw write_bw.hip ; run: ./write_bw
+// the store pattern.  Build: hipcc --offload-arch=gfx950 -O3 -o write_bw write_bw.hip ; run: ./write_bw (every row) or ./write_bw slabs
+// (the slab-ticket rows only)
 #include <hip/hip_runtime.h>
 #include <cstdio>
 #include <cstdlib>
@@ -60,9 +61,100 @@ __global__ void k_ticket(f4* __restrict__ p, size_t n4, int blk4, unsigned* __re
     }
 }
 
+// slab tickets in the step kernel's geometry: rows `stride` floats apart, a unit = 7 planes of N floats at float (2 + 7 * rank) * N
+// of its row, units in address order (units[u] = row << 14 | rank, as the plan kernel lists them).  A ticket is T tiles of a unit
+// (tile = 256 float4 groups = 4 KB of each of the 7 planes, planes in rotation), ticket t -> unit t / S, slab t % S; thread 0 keeps
+// D claims in flight (a claim is consumed D tickets after it was issued).  The first ticket of a workgroup is static.
+template <int T, int D>
+__global__ void __launch_bounds__(256) k_slab(float* __restrict__ base, const unsigned* __restrict__ units, int nunits, size_t stride, int N,
+                                              unsigned* __restrict__ counter) {
+    constexpr int S = (9 + T - 1) / T;
+    const f4 v = {1.f, 2.f, 3.f, 4.f};
+    __shared__ unsigned s_t;
+    const int tid = threadIdx.x;
+    const unsigned total = (unsigned)nunits * S;
+    const int ngrp = N >> 2;
+    unsigned ring[D];
+    ring[0] = blockIdx.x;
+    if (tid == 0)
+        for (int d = 1; d < D; d++) ring[d] = gridDim.x + atomicAdd(counter, 1u);
+    for (;;) {
+        if (tid == 0) s_t = ring[0];
+        __syncthreads();
+        const unsigned t = __builtin_amdgcn_readfirstlane(s_t);
+        __syncthreads();
+        if (t >= total) break;
+        if (tid == 0) {
+#pragma unroll
+            for (int d = 0; d + 1 < D; d++) ring[d] = ring[d + 1];
+            ring[D - 1] = gridDim.x + atomicAdd(counter, 1u);
+        }
+        const unsigned u = t / S, p = t % S;
+        const unsigned ent = units[u];
+        float* __restrict__ out = base + (size_t)(ent >> 14) * stride + (size_t)(2 + 7 * (ent & 0x3FFFu)) * N;
+#pragma unroll
+        for (int j = 0; j < T; j++) {
+            const int g = ((int)p * T + j) * 256 + tid;
+            if (g < ngrp) {
+                float* __restrict__ pp = out + ((size_t)g << 2);
+#pragma unroll
+                for (int pl = 0; pl < 7; pl++) __builtin_nontemporal_store(v, (f4*)(pp + (size_t)pl * N));
+            }
+        }
+    }
+}
+
+template <int T, int D>
+static void run_slab(float* base, const unsigned* units, int nunits, size_t stride, int N, unsigned* ctr, hipEvent_t e0, hipEvent_t e1) {
+    const int grids[] = {512, 1024};
+    for (int G : grids) {
+        float best = 1e30f, worst = 0.f;
+        for (int rep = 0; rep < 4; rep++) {
+            CK(hipMemsetAsync(ctr, 0, 4, 0));
+            CK(hipEventRecord(e0));
+            hipLaunchKernelGGL((k_slab<T, D>), dim3(G), dim3(256), 0, 0, base, units, nunits, stride, N, ctr);
+            CK(hipEventRecord(e1)); CK(hipEventSynchronize(e1));
+            float ms; CK(hipEventElapsedTime(&ms, e0, e1));
+            if (rep > 0) { if (ms < best) best = ms; if (ms > worst) worst = ms; }
+        }
+        const double wr = (double)nunits * 7 * N * 4;
+        printf("%5.1f GB  slab T=%d (%6.1f KB) D=%d %4dx256  %8.3f ms  %6.2f TB/s  spread %.3f ms (%.1f %%)\n", wr / 1e9, T,
+               (T < 9 ? T * 28.0 : 241920 / 1024.0), D, G, best, wr / best / 1e9, worst - best, 100.0 * (worst - best) / best);
+    }
+}
+
+// the step's own span: 4096 rows of (2 + 7 * 36) * 8640 floats (8.78 MB, 36 GB in all), 2..19 units per row (10.4 GB written)
+static void slab_rows(hipEvent_t e0, hipEvent_t e1) {
+    const int rows = 4096, N = 8640;
+    const size_t stride = (size_t)(2 + 7 * 36) * N;
+    std::vector<unsigned> h;
+    for (int r = 0; r < rows; r++) {
+        const int k = 2 + (int)(((unsigned)r * 2654435761u >> 16) % 18u);
+        for (int j = 0; j < k; j++) h.push_back(((unsigned)r << 14) | (unsigned)j);
+    }
+    const int nunits = (int)h.size();
+    float* base; unsigned *units, *ctr;
+    if (hipMalloc(&base, rows * stride * 4) != hipSuccess) { printf("alloc of the 36 GB span failed\n"); return; }
+    CK(hipMalloc(&units, h.size() * 4)); CK(hipMalloc(&ctr, 4));
+    CK(hipMemcpy(units, h.data(), h.size() * 4, hipMemcpyHostToDevice));
+    printf("# slab tickets: %d units of %d B over %d rows %zu B apart, best of 3 timed launches (spread = worst - best)\n", nunits, 7 * N * 4, rows,
+           stride * 4);
+    run_slab<9, 1>(base, units, nunits, stride, N, ctr, e0, e1);
+    run_slab<9, 2>(base, units, nunits, stride, N, ctr, e0, e1);
+    run_slab<9, 4>(base, units, nunits, stride, N, ctr, e0, e1);
+    run_slab<3, 1>(base, units, nunits, stride, N, ctr, e0, e1);
+    run_slab<3, 2>(base, units, nunits, stride, N, ctr, e0, e1);
+    run_slab<3, 4>(base, units, nunits, stride, N, ctr, e0, e1);
+    run_slab<1, 1>(base, units, nunits, stride, N, ctr, e0, e1);
+    run_slab<1, 2>(base, units, nunits, stride, N, ctr, e0, e1);
+    run_slab<1, 4>(base, units, nunits, stride, N, ctr, e0, e1);
+    CK(hipFree(base)); CK(hipFree(units)); CK(hipFree(ctr));
+}
+
 int main(int argc, char** argv) {
     const double gbs[] = {4.0, 10.9, 36.0};
     hipEvent_t e0, e1; CK(hipEventCreate(&e0)); CK(hipEventCreate(&e1));
+    if (argc > 1 && argv[1][0] == 's') { slab_rows(e0, e1); return 0; }      // ./write_bw slabs: the slab-ticket rows only
     for (double gb : gbs) {
         size_t bytes = (size_t)(gb * 1e9) & ~(size_t)((1 << 22) - 1);
         f4* p; if (hipMalloc(&p, bytes) != hipSuccess) { printf("alloc %.1f GB failed\n", gb); continue; }
@@ -105,5 +197,6 @@ int main(int argc, char** argv) {
         }
         CK(hipFree(p));
     }
+    slab_rows(e0, e1);
     return 0;
 }

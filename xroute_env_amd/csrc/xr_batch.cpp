@@ -1345,6 +1345,7 @@ int32_t step_observe_impl(xr_batch* b, const int32_t* actions_dev, float* out_de
             XR_HIP(hipStreamWaitEvent(b->aux_stream, b->ev_fork, 0));
         }
         d.queue_grid = std::min(blocks, 4 * n);
+        d.queue_slab_tickets = use_helpers ? 0 : 1;       // (the helpers take whole units from the same counter)
         XR_HIP(xr_launch_step_queue(&d, actions_dev, qv, d.queue_grid, st));
         if (use_helpers) {
             XR_HIP(xr_launch_unit_helpers(&d, helpers, b->aux_stream));

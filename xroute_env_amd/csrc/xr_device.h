@@ -169,6 +169,7 @@ struct XrBatchDev {
     int32_t queue_skip_shift; // workgroups with bit `shift` of their index set start with units instead of a route (-1: none)
     int32_t obs_lds_bytes;   // dynamic LDS of the launch that runs xr_obs_epilogue (0: unknown -> the epilogue reads the state rows from global memory)
     int32_t queue_grid;      // workgroups of the queue-form step kernel of this call (their first tasks are static: xr_queue_first)
+    int32_t queue_slab_tickets; // 1: queue[1] of this launch may hand out slab tickets (xr_step_queue_body); 0: whole units (helper writers share it)
     // parameters
     int32_t via_cost, pen_cost, max_route_count, auto_reset;
     const int32_t* route_order;   // route kernel: workgroup i routes env route_order[i] (null: env_base + i); longest predicted first

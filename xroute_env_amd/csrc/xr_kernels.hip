@@ -1452,7 +1452,10 @@ __global__ void __launch_bounds__(BT) xr_plan_kernel(XrBatchDev b, const int32_t
 
 #define XR_NP_J 9            // float4 groups per thread per tile: 256 threads * 4 nodes * 9 = 9216 nodes
 // one unit = the 7 planes of one remaining net of one env (aligned planes: every region's N % 4 == 0)
-__device__ __forceinline__ void xr_unit_aligned(const XrBatchDev& b, int u) {
+// Writes the float4 groups of tiles t_lo .. t_hi - 1 of the unit (a tile = 256 groups = 4 KB of each plane), J tiles per pass; the
+// default range is the whole unit.  The step kernel's slab tickets call it with J = t_hi - t_lo: one pass.
+template <int J = XR_NP_J>
+__device__ __forceinline__ void xr_unit_aligned(const XrBatchDev& b, int u, int t_lo = 0, int t_hi = 1 << 22) {
     const int tid = threadIdx.x;
     const uint32_t ent = b.plan_units[u];
     const int id = b.plan_unit_net[u];
@@ -1467,24 +1470,25 @@ __device__ __forceinline__ void xr_unit_aligned(const XrBatchDev& b, int u) {
     // node array — a unit then reads ~50 bytes instead of 17 KB (round 1: 0.6 GB of HBM reads per 4096-env launch).
     const int ap_lo = b.net_csr[R.net_off + id], ap_hi = b.net_csr[R.net_off + id + 1];
     (void)nn; (void)X; (void)Y; (void)Z; (void)YZ;
-    for (int g0 = 0; g0 < ngrp; g0 += 256 * XR_NP_J) {
-        unsigned bits[XR_NP_J];                                // per group: AP mask (bits 0..3), neighbour mask (4..7)
+    const int gend = min(ngrp, t_hi << 8);
+    for (int g0 = t_lo << 8; g0 < gend; g0 += 256 * J) {
+        unsigned bits[J];                                      // per group: AP mask (bits 0..3), neighbour mask (4..7)
 #pragma unroll
-        for (int j = 0; j < XR_NP_J; j++) bits[j] = 0;
+        for (int j = 0; j < J; j++) bits[j] = 0;
         for (int i = ap_lo; i < ap_hi; i++) {
             const int v = b.ap_feat[R.ap_off + i];             // wave-uniform address: one scalar load
             const int f = v & 0x7FFFFFFF;
             const unsigned m = (1u | (v < 0 ? 16u : 0u)) << (f & 3);
             const int g = (f >> 2) - g0 - tid;                 // == j * 256 for the thread and slot that hold node f
 #pragma unroll
-            for (int j = 0; j < XR_NP_J; j++) bits[j] |= (g == j * 256) ? m : 0u;
+            for (int j = 0; j < J; j++) bits[j] |= (g == j * 256) ? m : 0u;
         }
         // plane 0 of the net: AP mask; planes 1..6: the six aliased "has a same-net axis neighbour" planes
         // rotation: 4 KB of each of the 7 planes in turn (the step kernel's own order)
 #pragma unroll
-        for (int j = 0; j < XR_NP_J; j++) {
+        for (int j = 0; j < J; j++) {
             const int g = g0 + j * 256 + tid;
-            if (g < ngrp) {
+            if (g < gend) {
                 float* __restrict__ pp = out + ((int64_t)g << 2);
                 const unsigned m0 = bits[j], m1 = bits[j] >> 4;
                 float4 v0, v1;
@@ -1787,7 +1791,14 @@ __global__ void __launch_bounds__(256) xr_obs_u8_kernel(XrBatchDev b, uint8_t* _
     }
 }
 
-constexpr int XR_QUEUE_BATCH = 1;      // units a workgroup claims per atomic
+constexpr int XR_QUEUE_BATCH = 1;      // tickets a workgroup claims per atomic (2: +1.5 %, 4: +7 % step time when a ticket was a whole unit)
+// Tiles (4 KB of each of a unit's 7 planes) per ticket of the fp32 aligned writer in the queue form; a whole unit of the workload is 9.
+// 3 (84 KB per claim, one claim kept ahead as before): step 1.761 -> 1.680 ms at 4096 envs, 0.4915 -> 0.478 at 1024, 0.2996 -> 0.296 at 512
+// (profiles/step_ticket_slabs_ab.json).  The pure-write micro (tools/micro/write_bw.hip slabs, profiles/step_ticket_slabs_micro.txt) has 3
+// level with 9 at 1024 writers and +0.8 % at 512; 1 is bound by the claim rate of one counter word (88 M/s: 2.4 TB/s); claims kept 2 or
+// 4 ahead are 1-4 % slower at every ticket size, so the claim stays one ahead.
+constexpr int XR_TICKET_TILES = 3;
+static_assert(XR_TICKET_TILES >= 1 && XR_TICKET_TILES <= XR_NP_J, "a slab is one pass of xr_unit_aligned");
 // Static first tasks of the queue form (see xr_step_queue_kernel): of G workgroups, those with bit `sh` of their index clear start with
 // a route (first_r of them), the others with a unit (first_u); sh < 0: every workgroup starts with a route.
 __device__ __forceinline__ void xr_queue_first(int G, int sh, int& first_r, int& first_u) {
@@ -1825,7 +1836,7 @@ __global__ void __launch_bounds__(256) xr_netplane_stream_kernel(XrBatchDev b) {
 // queue form of the step (XR_OBS_QUEUE): ONE persistent launch (as many workgroups as fit the chip) that drains two task
 // queues — envs to route (+ their planes 0..1) and net-plane units to write.  Units do not depend on routing
 // (xr_plan_kernel), so they are the filler that keeps HBM busy while other workgroups route, and the tail of the
-// launch is one 20 us unit instead of one whole env.  A workgroup alternates one route task with `quota` units (a little
+// launch is one ticket (a 3-tile slab of a unit, ~5 us) instead of one whole env.  A workgroup alternates one route task with `quota` units (a little
 // under the average units per env, so that the routes run out first and the launch ends in a pure-write drain);
 // half of the workgroups (bit 5 of the workgroup index: spread over every XCD and CU) start with units so that the launch writes
 // from its first microseconds.  No workgroup ever waits for another one.
@@ -1838,12 +1849,23 @@ __device__ __forceinline__ void xr_step_queue_body(XrBatchDev& b, const int32_t*
     __shared__ int s_task;
     const int tid = threadIdx.x;
     const int B = XR_ENV_END(b) - b.env_base;           // route tasks of this launch: task t = env env_base + t (the whole batch, or one env group)
-    const int total = (int)b.queue[2];
-    const int quota = max(1, (int)(((int64_t)total * b.queue_quota_pm) / (1000 * (int64_t)B)));
+    const int units = (int)b.queue[2];
+    // The unit counter (queue[1]) hands out TICKETS: ticket t = slab t % S of unit t / S, a slab = XR_TICKET_TILES tiles.  S comes from the
+    // batch's largest region, so regions of different N share one decode (a slab past its own unit's tiles writes nothing).  S = 1 (a
+    // ticket is a whole unit) for the uint8 and the unaligned writers, beside helper writers (they share queue[1] and count units), and
+    // where units * S would not fit 31 bits (the counters overshoot by one claim per workgroup).
+    int S = 1;
+    if (!U8 && b.obs_vec4 == 1 && b.queue_slab_tickets) {
+        S = ((b.n_max + 1023) / 1024 + XR_TICKET_TILES - 1) / XR_TICKET_TILES;
+        if ((int64_t)units * S > 0x7FF00000LL) S = 1;
+    }
+    const int total = units * S;                        // tickets of this launch
+    // (after a route: 0.75 x the average BYTES per env, whatever the ticket size)
+    const int quota = S * max(1, (int)(((int64_t)units * b.queue_quota_pm) / (1000 * (int64_t)B)));
     bool routes_left = true, units_left = total > 0;
     bool skip_route = b.queue_skip_shift >= 0 && ((blockIdx.x >> b.queue_skip_shift) & 1) != 0;
     // The FIRST task of every workgroup is static — the route-first workgroups take route tasks 0, 1, 2, ... by their rank among
-    // themselves, the unit-first ones units 0, 1, 2, ... — and the two counters hand out what follows: a thousand workgroups opening
+    // themselves, the unit-first ones tickets 0, 1, 2, ... — and the two counters hand out what follows: a thousand workgroups opening
     // the launch with an atomic on the same word serialise in L2 (tools/queue_timeline_probe.py: the first routes started 6-12 us into
     // the launch).
     int first_r = 0, first_u = 0, my_first = -1;          // tasks handed out statically; this workgroup's own one (-1: taken)
@@ -1886,8 +1908,9 @@ __device__ __forceinline__ void xr_step_queue_body(XrBatchDev& b, const int32_t*
         }
         skip_route = false;
         if (units_left) {
-            // the next claim is issued before the current unit is written (an atomic round trip costs ~4 us, a unit ~20 us);
-            // claiming several units at once measured slower (XR_QUEUE_BATCH 2: +1.5 %, 4: +7 %)
+            // the next claim is issued before the current ticket is written (an atomic round trip costs ~4 us, a whole unit ~20 us, a
+            // 3-tile slab ~5 us); claiming several at once measured slower (XR_QUEUE_BATCH), and so did whole units as tickets
+            // (XR_TICKET_TILES)
             const int nb = routes_left ? max(1, quota / XR_QUEUE_BATCH) : (1 << 30);
             unsigned nx = 0;
             const unsigned ubase = (unsigned)first_u * (unsigned)XR_QUEUE_BATCH;
@@ -1910,8 +1933,12 @@ __device__ __forceinline__ void xr_step_queue_body(XrBatchDev& b, const int32_t*
                         if (b.obs_vec4 == 1) xr_unit_u8_aligned(b, u);
                         else xr_unit_u8_stream(b, u, reinterpret_cast<uint32_t*>(smem));
                     } else {
-                        if (b.obs_vec4 == 1) xr_unit_aligned(b, u);
-                        else xr_unit_stream(b, u, reinterpret_cast<uint32_t*>(smem));
+                        if (b.obs_vec4 == 1) {
+                            if (S > 1) {                      // ticket u: slab p of unit uu
+                                const int uu = u / S, p = u - uu * S;
+                                xr_unit_aligned<XR_TICKET_TILES>(b, uu, p * XR_TICKET_TILES, (p + 1) * XR_TICKET_TILES);
+                            } else xr_unit_aligned(b, u);
+                        } else xr_unit_stream(b, u, reinterpret_cast<uint32_t*>(smem));
                     }
                 }
 #ifdef XR_TIMELINE
