@@ -634,7 +634,9 @@ int32_t xr_agent_obstacle_tower(const float* head_dev, int64_t head_stride, int3
  * cache_vec_dev [regions * cache_kmax][64] (row = region * cache_kmax + net - 1: agents.NetVectorCache, complete) or, when cache_pre_dev
  * [regions * cache_kmax][128] is given, from the first layer's net half already applied to them (W1[:, 64:] . vec, once per weight update), weights_dev =
  * xr_agent_actor_weights() floats (transposed by agents.FusedActorHead).  logits_dev: optional fp32 [n_envs][kcap], -inf beyond an env's
- * nets; action_dev int32 [n_envs]: first maximum in the channel's order, 0 without nets. */
+ * nets; action_dev int32 [n_envs]: first maximum in the channel's order, 0 without nets.  An env with nlegal <= 0 (a row that xr_batch_expand_state
+ * flagged with nlegal = region = -1 included) gets action 0 and a logits row of -inf.  With cache_pre_dev kcap is at most 256 (XR_ERR_RANGE beyond);
+ * with cache_pre_dev == NULL any kcap is taken. */
 int32_t xr_agent_actor_weights(void);
 int32_t xr_agent_actor(const float* state_dev, const float* head_dev, int64_t head_stride, int32_t ids_off, const int32_t* nlegal_dev,
                        const int32_t* region_dev, const float* cache_vec_dev, const float* cache_pre_dev, int32_t cache_kmax, const float* weights_dev,

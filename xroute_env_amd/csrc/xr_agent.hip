@@ -1122,7 +1122,7 @@ __global__ void __launch_bounds__(128) xr_actor_kernel(const float* __restrict__
     float hs = wt[XA_B1 + j];
 #pragma unroll 8
     for (int i = 0; i < 64; i++) hs += wt[XA_W1T + i * 128 + j] * s_st[i];
-    const int nl = min(nlegal[e], kcap);
+    const int nl = max(0, min(nlegal[e], kcap));       // (a row that did not parse carries nlegal = region = -1: no nets, and the tail fill below starts at 0)
     const int64_t rbase = (int64_t)region[e] * cache_kmax;
     const float* __restrict__ ids = head + (int64_t)e * head_stride + ids_off;
     const float b2 = j < 64 ? wt[XA_B2 + j] : 0.f, w3 = j < 64 ? wt[XA_W3 + j] : 0.f, b3 = wt[XA_B3];
@@ -1331,7 +1331,9 @@ int32_t xr_agent_actor_weights(void) { return XA_TOTAL; }
 // nlegal_dev / region_dev int32 [n_envs], cache_vec_dev fp32 [regions * cache_kmax][64] (normalised net vectors, row = region * cache_kmax + net - 1),
 // cache_pre_dev (optional) fp32 [regions * cache_kmax][128]: the net half of the first layer already applied to every cached vector (W1[:, 64:] . vec),
 // weights_dev: xr_agent_actor_weights() floats; logits_dev (optional) fp32 [n_envs][kcap] (-inf beyond an env's nets); action_dev int32 [n_envs]:
-// the greedy net id (0: no nets).
+// the greedy net id (0: no nets).  An env with nlegal <= 0 (xr_batch_expand_state flags a row that does not parse with nlegal = region = -1) gets
+// action 0 and a logits row of -inf; nothing of the cache or of its head row is read.  cache_pre_dev takes kcap <= 256 (XR_ERR_RANGE beyond:
+// the ids are staged in LDS); without it kcap is not limited.
 int32_t xr_agent_actor(const float* state_dev, const float* head_dev, int64_t head_stride, int32_t ids_off, const int32_t* nlegal_dev,
                        const int32_t* region_dev, const float* cache_vec_dev, const float* cache_pre_dev, int32_t cache_kmax, const float* weights_dev,
                        int32_t n_envs, int32_t kcap, float* logits_dev, int32_t* action_dev, void* stream) {
