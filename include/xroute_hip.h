@@ -58,6 +58,12 @@ extern "C" {
 #define XR_REC_PIN1(r)   (((r) >> 17) & 0x3FFFu)   /* pin + 1, 0 = none */
 #define XR_MAX_NETS      16382
 #define XR_MAX_LAYERS    32
+/* Track coordinates (xr_region_desc.xs_host / ys_host) lie in [-2^30, 2^30], both ends included, and the tracks of one axis of a
+ * region span less than XR_MAX_TRACK_SPAN DBU (last - first; XR_ERR_RANGE otherwise): the routers keep coordinates relative to the
+ * first track, x4, in 32-bit words and add two spans in the search heuristic.  The spec loses nothing: a distance of XR_DIST_CAP =
+ * 0x07F00000 (< 2^27) or more does not exist, so an edge that long is never crossed.  Costs: via_cost, guide_cost and
+ * drc_cost * drc_unit << (maze_end_iter - 1) are each below 2^22 (xr_batch_create) */
+#define XR_MAX_TRACK_SPAN (1ll << 28)
 
 /* owner value of nodes occupied by something that is not a net of this region
  * (blockages, pre-routed wires: is_used NORMAL nodes in the initial Request) */

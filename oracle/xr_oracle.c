@@ -276,6 +276,10 @@ int xro_env_observation(const xro_env* e, float* out) {
 }
 
 /* ---- XR-Maze v1 --------------------------------------------------------- */
+/* c[i + 1] - c[i] of a strictly increasing int32 table, taken in uint32: exact for every pair of int32 coordinates (the int32
+ * difference overflows from a gap of 2^31 on: tracks at -2^30 and +2^30) */
+static uint32_t track_gap(const int32_t* c, int i) { return (uint32_t)c[i + 1] - (uint32_t)c[i]; }
+
 /* neighbour of v in direction d (0 E x+1, 1 S y-1, 2 W x-1, 3 N y+1, 4 U z+1, 5 D z-1) if the grid
  * graph has that edge: planar edges only along the layer's preferred direction, vias everywhere.
  * Returns -1 when there is no such edge; *len = edge length (DBU) or via cost. */
@@ -284,10 +288,10 @@ static int graph_nbr(const xro_env* e, int v, int d, uint32_t* len, int* is_via)
     int z = v % Z, y = (v / Z) % Y, x = v / (Y * Z);
     *is_via = 0;
     switch (d) {
-    case 0: if (e->ldir[z] != 0 || x + 1 >= e->X) return -1; *len = (uint32_t)(e->xs[x + 1] - e->xs[x]); return v + Y * Z;
-    case 2: if (e->ldir[z] != 0 || x - 1 < 0) return -1;     *len = (uint32_t)(e->xs[x] - e->xs[x - 1]); return v - Y * Z;
-    case 1: if (e->ldir[z] != 1 || y - 1 < 0) return -1;     *len = (uint32_t)(e->ys[y] - e->ys[y - 1]); return v - Z;
-    case 3: if (e->ldir[z] != 1 || y + 1 >= Y) return -1;    *len = (uint32_t)(e->ys[y + 1] - e->ys[y]); return v + Z;
+    case 0: if (e->ldir[z] != 0 || x + 1 >= e->X) return -1; *len = track_gap(e->xs, x); return v + Y * Z;
+    case 2: if (e->ldir[z] != 0 || x - 1 < 0) return -1;     *len = track_gap(e->xs, x - 1); return v - Y * Z;
+    case 1: if (e->ldir[z] != 1 || y - 1 < 0) return -1;     *len = track_gap(e->ys, y - 1); return v - Z;
+    case 3: if (e->ldir[z] != 1 || y + 1 >= Y) return -1;    *len = track_gap(e->ys, y); return v + Z;
     case 4: if (z + 1 >= Z) return -1; *len = (uint32_t)e->via_cost; *is_via = 1; return v + 1;
     default: if (z - 1 < 0) return -1; *len = (uint32_t)e->via_cost; *is_via = 1; return v - 1;
     }
@@ -391,6 +395,32 @@ static void dijkstra(xro_env* e, int net) {
     }
 }
 
+/* guide of the net (v2): its boxes when the region carries them, else the bounding box of its access points on every layer */
+static void set_net_guide(xro_env* e, int net) {
+    const int lo = e->net_off[net], hi = e->net_off[net + 1];
+    e->n_gb = 0;
+    if (e->guide_off && e->guide_off[net] > e->guide_off[net - 1]) {
+        for (int i = e->guide_off[net - 1]; i < e->guide_off[net]; i++) {
+            const int16_t* g = e->guide_box + 6 * (size_t)i;
+            int* o = e->gb[e->n_gb++];
+            o[0] = g[0] - e->guide_margin; o[1] = g[2] + e->guide_margin; o[2] = g[1] - e->guide_margin; o[3] = g[3] + e->guide_margin;
+            o[4] = g[4]; o[5] = g[5];
+        }
+    } else {
+        int gx0 = 1 << 30, gy0 = 1 << 30, gx1 = -1, gy1 = -1;
+        for (int i = lo; i < hi; i++) {
+            int f = e->ap_node[i], y = (f / e->Z) % e->Y, x = f / (e->Y * e->Z);
+            if (x < gx0) gx0 = x;
+            if (x > gx1) gx1 = x;
+            if (y < gy0) gy0 = y;
+            if (y > gy1) gy1 = y;
+        }
+        int* o = e->gb[e->n_gb++];
+        o[0] = gx0 - e->guide_margin; o[1] = gx1 + e->guide_margin; o[2] = gy0 - e->guide_margin; o[3] = gy1 + e->guide_margin;
+        o[4] = 0; o[5] = e->Z - 1;
+    }
+}
+
 int xro_env_distance_field(xro_env* e, int action, uint32_t* dist_out) {
     if (action < 1 || action > e->n_nets) return -1;
     int lo = e->net_off[action], hi = e->net_off[action + 1];
@@ -399,6 +429,7 @@ int xro_env_distance_field(xro_env* e, int action, uint32_t* dist_out) {
     for (int i = lo; i < hi; i++) if (e->ap_pin[i] < first) first = e->ap_pin[i];
     memset(e->comp, 0, e->N);
     for (int i = lo; i < hi; i++) if (e->ap_pin[i] == first) e->comp[e->ap_node[i]] = 1;
+    set_net_guide(e, action);      /* the field of the net's first search, first attempt: its own guide, the penalty drc_cost * drc_unit */
     dijkstra(e, action);
     memcpy(dist_out, e->dist, sizeof(uint32_t) * e->N);
     return 0;
@@ -426,28 +457,7 @@ int xro_env_step(xro_env* e, int action, int32_t delta[3], int* done, int32_t* p
         for (int j = 0; j < npins; j++) if (pins[j] == p) { seen = 1; break; }
         if (!seen) pins[npins++] = p;
     }
-    /* guide of the net (v2): its boxes when the region carries them, else the bounding box of its access points on every layer */
-    e->n_gb = 0;
-    if (e->guide_off && e->guide_off[net] > e->guide_off[net - 1]) {
-        for (int i = e->guide_off[net - 1]; i < e->guide_off[net]; i++) {
-            const int16_t* g = e->guide_box + 6 * (size_t)i;
-            int* o = e->gb[e->n_gb++];
-            o[0] = g[0] - e->guide_margin; o[1] = g[2] + e->guide_margin; o[2] = g[1] - e->guide_margin; o[3] = g[3] + e->guide_margin;
-            o[4] = g[4]; o[5] = g[5];
-        }
-    } else {
-        int gx0 = 1 << 30, gy0 = 1 << 30, gx1 = -1, gy1 = -1;
-        for (int i = lo; i < hi; i++) {
-            int f = e->ap_node[i], y = (f / e->Z) % e->Y, x = f / (e->Y * e->Z);
-            if (x < gx0) gx0 = x;
-            if (x > gx1) gx1 = x;
-            if (y < gy0) gy0 = y;
-            if (y > gy1) gy1 = y;
-        }
-        int* o = e->gb[e->n_gb++];
-        o[0] = gx0 - e->guide_margin; o[1] = gx1 + e->guide_margin; o[2] = gy0 - e->guide_margin; o[3] = gy1 + e->guide_margin;
-        o[4] = 0; o[5] = e->Z - 1;
-    }
+    set_net_guide(e, net);
     /* XR-Maze v2 rip-up and reroute (`-maze_end_iter`, `-ripup_mode 1`): attempt t routes the whole net with the penalty
      * pen_cost << t; an attempt whose path uses a node held by another net is ripped up (owners restored, nothing
      * recorded) unless it is the last one.  maze_end_iter 1 = XR-Maze v1. */

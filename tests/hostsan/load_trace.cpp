@@ -252,6 +252,125 @@ void run_case(const char* name, const xr_config& cfg, const std::vector<const Re
     check(xr_stub_alloc_live == 0, "no device buffer outlives the batch");
 }
 
+// ---- the numeric thresholds of the router choice (place_route, choose_window) and of check_desc, each from both sides ------------------
+// Tracks from their gaps: the case decides every coordinate
+void retrack(std::vector<int32_t>& t, const std::vector<int64_t>& gaps, int64_t origin) {
+    t.assign(1, (int32_t)origin);
+    int64_t c = origin;
+    for (int64_t g : gaps) t.push_back((int32_t)(c += g));
+}
+Reg with_x(Reg r, const std::vector<int64_t>& gaps, int64_t origin = 0) { retrack(r.xs, gaps, origin); return r; }
+Reg with_y(Reg r, const std::vector<int64_t>& gaps, int64_t origin = 0) { retrack(r.ys, gaps, origin); return r; }
+// n - 1 gaps of `pitch`, the one in the middle `wide`
+std::vector<int64_t> one_wide(int n, int64_t wide, int64_t pitch = 400) {
+    std::vector<int64_t> g(n - 1, pitch);
+    g[(n - 1) / 2] = wide;
+    return g;
+}
+// n - 1 nearly equal gaps that span `ext`
+std::vector<int64_t> spanning(int n, int64_t ext) {
+    std::vector<int64_t> g(n - 1, ext / (n - 1));
+    g.back() = ext - (ext / (n - 1)) * (n - 2);
+    return g;
+}
+
+void range_case(const char* name, const xr_config& cfg, const std::vector<const Reg*>& regs, const std::string& reaches, int win_x = 0) {
+    run_case(name, cfg, regs, reaches, false);
+    if (reaches.compare(0, 3, "rc=") == 0) return;
+    printf("  seen: zch=%d lds_dist=%d win_x=%d\n", g_seen.kzch, g_seen.lds, g_seen.win);
+    check(g_seen.win == win_x, "the window the case is marked with");
+}
+
+void range_cases() {
+    g_reached.clear();
+    const Reg a662 = gen(1, 6, 6, 2, 3), r4040 = gen(12, 40, 40, 9, 5), r6448 = gen(7, 64, 48, 12, 6);
+    const int64_t step = XR3_STEP_LIMIT, extent = XR3_EXTENT_LIMIT, pen = 3200;       // (the default penalty: drc_cost 8 x drc_unit 400)
+    const std::vector<int64_t> p400(5, 400);
+    xr_config c, v2 = config();
+    v2.maze_end_iter = 2;                                                             // pen_max = 6400
+    Reg r, q;
+    // edge_max + pen_max + guide_cost against 2^20: the largest term a pitch in x, a pitch in y, the via, the penalty, the guide cost
+    r = with_x(a662, one_wide(6, step - 1 - pen));
+    range_case("step 2^20 - 1, a pitch in x", config(), {&r}, "kzch=-3");
+    r = with_x(a662, one_wide(6, step - pen));
+    range_case("step 2^20, a pitch in x", config(), {&r}, "kzch=-1 (LDS)");
+    r = with_y(a662, one_wide(6, step - 1 - pen));
+    range_case("step 2^20 - 1, a pitch in y", config(), {&r, &a662}, "kzch=-3");
+    r = with_y(a662, one_wide(6, step - pen));
+    range_case("step 2^20, a pitch in y", config(), {&a662, &r}, "kzch=-1 (LDS)");
+    r = with_x(a662, one_wide(6, step - 1 - 2 * pen));
+    range_case("step 2^20 - 1, a pitch in x, maze_end_iter 2", v2, {&r}, "kzch=-4");
+    r = with_x(a662, one_wide(6, step - 2 * pen));
+    range_case("step 2^20, a pitch in x, maze_end_iter 2", v2, {&r}, "kzch=-2");
+    c = config(); c.via_cost = (int32_t)(step - 1 - pen);
+    range_case("step 2^20 - 1, the via", c, {&a662}, "kzch=-3");
+    c.via_cost = (int32_t)(step - pen);
+    range_case("step 2^20, the via", c, {&a662}, "kzch=-1 (LDS)");
+    c = config(); c.drc_unit = 1; c.drc_cost = (int32_t)(step - 1 - 800);              // (edge_max: the via, 800)
+    range_case("step 2^20 - 1, the penalty", c, {&a662}, "kzch=-3");
+    c.drc_cost = (int32_t)(step - 800);
+    range_case("step 2^20, the penalty", c, {&a662}, "kzch=-1 (LDS)");
+    c = config(); c.drc_unit = 1; c.drc_cost = (int32_t)((step - 4 - 800) >> 2); c.maze_end_iter = 3;
+    range_case("step 2^20 - 4, the penalty of attempt 3", c, {&a662}, "kzch=-4");
+    c.drc_cost = (int32_t)((step - 800) >> 2);
+    range_case("step 2^20, the penalty of attempt 3", c, {&a662}, "kzch=-2");
+    c = config(); c.guide_cost = (int32_t)(step - 1 - pen - 800);
+    range_case("step 2^20 - 1, the guide cost", c, {&a662}, "kzch=-4");
+    c.guide_cost = (int32_t)(step - pen - 800);
+    range_case("step 2^20, the guide cost", c, {&a662}, "kzch=-2");
+    // ext_max against 2^25, every single edge far below 2^20
+    r = with_x(r4040, spanning(40, extent - 1));
+    range_case("extent 2^25 - 1 in x", config(), {&r}, "kzch=-3");
+    range_case("extent 2^25 - 1 in x, maze_end_iter 2", v2, {&r}, "kzch=-4");
+    r = with_x(r4040, spanning(40, extent));
+    range_case("extent 2^25 in x", config(), {&r}, "kzch=-1 (LDS)");
+    range_case("extent 2^25 in x, maze_end_iter 2", v2, {&r}, "kzch=-2");
+    r = with_y(r4040, spanning(40, extent - 1), -(1 << 30));
+    range_case("extent 2^25 - 1 in y, from -2^30", config(), {&a662, &r}, "kzch=-3");
+    r = with_y(r4040, spanning(40, extent), (1 << 30) - extent);
+    range_case("extent 2^25 in y, up to 2^30", config(), {&r, &a662}, "kzch=-1 (LDS)");
+    // via_cost * 32 against 2^25 (no penalty: the via is an edge, the step limit would decide first)
+    c = config(); c.drc_cost = 0; c.via_cost = (int32_t)(step - 1);
+    range_case("via_cost 2^20 - 1", c, {&a662}, "kzch=-3");
+    c.maze_end_iter = 2;
+    range_case("via_cost 2^20 - 1, maze_end_iter 2", c, {&a662}, "kzch=-4");
+    c.via_cost = (int32_t)step;
+    range_case("via_cost 2^20, maze_end_iter 2", c, {&a662}, "kzch=-2");
+    c.maze_end_iter = 1;
+    range_case("via_cost 2^20", c, {&a662}, "kzch=-1 (LDS)");
+    // the window form's two conditions: edge_max + penalty below 2^20, window tracks x edge_max below 2^25
+    c = config(4); c.window = 52;
+    r = with_x(r6448, one_wide(64, step - 1 - pen));
+    range_case("window 52, step 2^20 - 1: 32 tracks x edge_max stay below 2^25", c, {&r}, "kzch=-1 (scratch)", 32);
+    r = with_x(r6448, one_wide(64, step - pen));
+    range_case("window 52, step 2^20 (off)", c, {&r}, "kzch=-1 (scratch)", 0);
+    r = with_y(r6448, one_wide(48, (extent - 1) / 48));                               // (48 rows: the window has at most 48 tracks)
+    range_case("window 52, 48 x edge_max = 2^25 - 32", c, {&r}, "kzch=-1 (scratch)", 48);
+    r = with_y(r6448, one_wide(48, (extent - 1) / 48 + 1));
+    range_case("window 52, 48 x edge_max = 2^25 + 16: 46 tracks", c, {&r}, "kzch=-1 (scratch)", 46);
+    // coordinates in [-2^30, 2^30], both ends included; the span of an axis below 2^28
+    r = with_x(a662, p400, -(1 << 30));
+    q = with_y(a662, p400, (1 << 30) - 2000);
+    range_case("xs from -2^30, ys up to 2^30", config(), {&r, &q}, "kzch=-3");
+    r = with_x(a662, one_wide(6, XR_MAX_TRACK_SPAN - 1 - 1600), -(1 << 27));
+    range_case("xs span 2^28 - 1", config(), {&r}, "kzch=-1 (LDS)");
+    r = with_x(a662, one_wide(6, XR_MAX_TRACK_SPAN - 1600), -(1 << 27));
+    range_case("xs span 2^28", config(), {&r}, "rc=-5");
+    r = with_y(a662, one_wide(6, XR_MAX_TRACK_SPAN - 1 - 1600));
+    c = config(); c.force_scratch_field = 1;
+    range_case("ys span 2^28 - 1, force_scratch_field", c, {&a662, &r}, "kzch=-1 (scratch)");
+    r = with_y(a662, one_wide(6, XR_MAX_TRACK_SPAN - 1600));
+    range_case("ys span 2^28", config(), {&a662, &r}, "rc=-5");
+    r = with_x(a662, one_wide(6, ((int64_t)1 << 31) - 1600), -(1 << 30));
+    range_case("xs from -2^30 to 2^30 (a span of 2^31)", config(), {&r}, "rc=-5");
+    c = config(); c.router = XR_ROUTER_SWEEP;
+    r = with_x(a662, one_wide(6, XR_MAX_TRACK_SPAN - 1 - 1600));
+    range_case("xs span 2^28 - 1, sweeps", c, {&r}, "kzch=0");
+
+    printf("reached (thresholds):\n");
+    for (const auto& kv : g_reached) printf("  %-20s %d\n", kv.first.c_str(), kv.second);
+}
+
 }  // namespace
 
 int main() {
@@ -424,6 +543,9 @@ int main() {
     for (const auto& kv : g_reached) printf("  %-20s %d\n", kv.first.c_str(), kv.second);
     for (const char* need : {"kzch=9", "kzch=12", "kzch=0", "kzch=-1 (LDS)", "kzch=-1 (scratch)", "kzch=-2", "kzch=-3", "kzch=-4", "window", "sweep_full", "stream_ok=false"})
         if (!g_reached.count(need)) { printf("NOT REACHED: %s\n", need); g_failures++; }
+    if (g_failures) printf("LOAD_TRACE_FAILED %d\n", g_failures);
+    else printf("LOAD_TRACE_OK\n");
+    range_cases();
     if (g_failures) printf("LOAD_TRACE_FAILED %d\n", g_failures);
     else printf("LOAD_TRACE_OK\n");
     return g_failures ? 1 : 0;

@@ -307,7 +307,8 @@ int32_t check_desc(const xr_region_desc& d, int r) {
     if (!d.xs_host || !d.ys_host || !d.layer_dir_host || !d.nodes_host)
         return fail(XR_ERR_INVALID, "region %d: null array", r);
     if (d.n_nets < 0 || d.n_nets > XR_MAX_NETS) return fail(XR_ERR_RANGE, "region %d: n_nets %d", r, d.n_nets);
-    // track coordinates within +-2^30 DBU: every difference of two of them (edge lengths, extents) then fits the kernels' int32 arithmetic
+    // track coordinates within +-2^30 DBU, both ends included: a difference of two of them reaches 2^31 and does NOT fit int32, so the
+    // span of each axis is bounded as well (below, once the tables are known to ascend)
     for (int i = 0; i < d.dim_x; i++)
         if (d.xs_host[i] < -(1 << 30) || d.xs_host[i] > (1 << 30)) return fail(XR_ERR_RANGE, "region %d: xs[%d] = %d outside +-2^30", r, i, d.xs_host[i]);
     for (int i = 0; i < d.dim_y; i++)
@@ -316,6 +317,14 @@ int32_t check_desc(const xr_region_desc& d, int r) {
         if (d.xs_host[i] <= d.xs_host[i - 1]) return fail(XR_ERR_INVALID, "region %d: xs not strictly increasing", r);
     for (int i = 1; i < d.dim_y; i++)
         if (d.ys_host[i] <= d.ys_host[i - 1]) return fail(XR_ERR_INVALID, "region %d: ys not strictly increasing", r);
+    // XR_MAX_TRACK_SPAN: the routers other than xr_dial3.h keep coordinates relative to the first track, x4, in 32-bit words and take
+    // them as int in the search heuristic, which adds an x and a y span: 2 * 4 * span < 2^31.  Edge lengths x4 (< 2^30) plus a
+    // distance word (< XR_DIST_CAP * 4 < 2^29) plus both penalties x4 (< 2^25) then stay inside the word too.  Nothing is lost to
+    // the spec: an edge of XR_DIST_CAP (< 2^27) or more is never crossed, whatever its length
+    const int64_t span_x = (int64_t)d.xs_host[d.dim_x - 1] - d.xs_host[0], span_y = (int64_t)d.ys_host[d.dim_y - 1] - d.ys_host[0];
+    if (span_x >= XR_MAX_TRACK_SPAN || span_y >= XR_MAX_TRACK_SPAN)
+        return fail(XR_ERR_RANGE, "region %d: tracks span %lld DBU in %s, the routers take spans below 2^28 (XR_MAX_TRACK_SPAN)", r,
+                    (long long)(span_x >= XR_MAX_TRACK_SPAN ? span_x : span_y), span_x >= XR_MAX_TRACK_SPAN ? "x" : "y");
     return XR_OK;
 }
 
