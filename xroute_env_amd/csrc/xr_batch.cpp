@@ -158,22 +158,24 @@ struct xr_batch {
     int group_bank[XR_MAX_GROUPS] = {};
     ObsValid group_valid[XR_MAX_GROUPS];        // per group: buffer (row 0 = the group's first slot) that holds its observation
     // lookahead (xr_batch_lookahead): private memory of the callers that have used it — [0] the whole batch, [1 + g] env group g.  One pool =
-    // the rows of look_grid shadow slots (everything a router writes per env), the task list and two banks of {tasks listed, next task}.
-    // Rollouts (xr_batch_rollout) play in the same shadow slots — calls on one pool are ordered by the caller — with claim counters of
-    // their own: roll_ctr, two alternating banks of one counter
+    // the slot rows of look_grid shadow slots plus the two per-launch rows a router also writes (carve_slots), the task list and two banks
+    // of {tasks listed, next task}.  Rollouts (xr_batch_rollout) play in the same shadow slots — calls on one pool are ordered by the
+    // caller — with claim counters of their own: roll_ctr, two alternating banks of one counter
     struct LookPool {
         DevBuf<uint8_t> mem;
         DevBuf<uint32_t> tasks, ctr, roll_ctr;
         int bank = 0, roll_bank = 0;
-        XrBatchDev shadow{};
+        XrSlotRows rows{};
+        unsigned long long* total_steps = nullptr;
+        long long* phase_cycles = nullptr;
         void release() { mem.release(); tasks.release(); ctr.release(); roll_ctr.release(); bank = 0; roll_bank = 0; }
     } look[1 + XR_MAX_GROUPS];
     // branch (xr_batch_branch): the staging pool of a caller — [0] the whole batch, [1 + g] env group g — allocated on its first branch: one
-    // row of every state array per row of the caller (a map may stage every row: a permutation without fixed points)
+    // slot of rows per row of the caller (a map may stage every row: a permutation without fixed points)
     struct BranchPool {
         DevBuf<uint8_t> mem;
         int rows = 0;
-        XrBranchRows stg{};
+        XrSlotRows stg{};
         void release() { mem.release(); rows = 0; }
     } branch[1 + XR_MAX_GROUPS];
     // tree search (xr_batch_tree_search): the private memory of a caller, indexed like look[] — the trees, the search state of every row
@@ -243,6 +245,51 @@ void mark_obs_valid(xr_batch* b, const void* out, int64_t stride, bool u8, int e
     for (int g = 0; g < b->n_groups; g++)
         if (env_lo <= b->group_bounds[g] && b->group_bounds[g + 1] <= env_hi)
             b->group_valid[g].set(static_cast<const char*>(out) + (b->group_bounds[g] - env_lo) * row_bytes, stride, u8);
+}
+
+// ---- the state rows of an env slot, listed once (with XrSlotRows itself and fill_dev) ---------------------------------------------
+// f(row of a, the same row of b, elements per slot) for every row.  A, B: XrSlotRows or XrBatchDev (rows of the same names and types:
+// xr_device.h), the same object twice where one is enough.  Every pool of slots is carved by this, every view of one in the other made by it
+template <class A, class B, class F>
+constexpr void for_each_slot_row(A& a, B& b, size_t n_max, size_t path_cap, size_t legal_words, F&& f) {
+    f(a.owner, b.owner, n_max); f(a.path, b.path, path_cap); f(a.legal, b.legal, legal_words);
+    f(a.hash, b.hash, 1); f(a.reward, b.reward, 1); f(a.env_steps, b.env_steps, 1); f(a.records, b.records, 1);
+    f(a.cum, b.cum, 3); f(a.delta, b.delta, 3);
+    f(a.nlegal, b.nlegal, 1); f(a.status, b.status, 1); f(a.path_len, b.path_len, 1); f(a.sweeps, b.sweeps, 1); f(a.touched, b.touched, 1);
+    f(a.env_region, b.env_region, 1); f(a.env_replay, b.env_replay, 1); f(a.done, b.done, 1);
+}
+// the DISTINCT members it visits: a row listed twice counts once, so a row left out cannot hide behind it
+constexpr size_t slot_row_count() {
+    XrSlotRows r{};
+    const void* seen[64] = {};
+    size_t n = 0;
+    for_each_slot_row(r, r, 0, 0, 0, [&](auto*& p, auto*&, size_t) {
+        for (size_t i = 0; i < n; i++)
+            if (seen[i] == &p) return;
+        if (n < 64) seen[n++] = &p;
+    });
+    return n;
+}
+static_assert(sizeof(XrSlotRows) == slot_row_count() * sizeof(void*), "every row of XrSlotRows is listed in for_each_slot_row, once");
+
+// the rows of `from` into `to` (each an XrSlotRows or an XrBatchDev): the one conversion between the two, pointer types checked row by row
+template <class A, class B>
+void copy_slot_rows(A& to, const B& from) {
+    for_each_slot_row(to, from, 0, 0, 0, [](auto& t, auto& f, size_t) { t = f; });
+}
+
+// One allocation cut into arrays, each starting on a 16-byte boundary
+struct Carver {
+    size_t off = 0;
+    size_t take(size_t bytes) { const size_t o = off; off += (bytes + 15) & ~(size_t)15; return o; }
+    // the next array, `count` elements: with the allocation's base its pointer into p; without one, sizing only
+    template <class T>
+    void place(uint8_t* base, T*& p, size_t count) { const size_t o = take(count * sizeof(T)); if (base) p = reinterpret_cast<T*>(base + o); }
+};
+
+// `slots` slots of every state row
+void carve_slots(const xr_batch* b, Carver& c, uint8_t* base, XrSlotRows& r, size_t slots) {
+    for_each_slot_row(r, r, b->n_max, b->path_cap, b->legal_words, [&](auto*& p, auto*&, size_t per_slot) { c.place(base, p, slots * per_slot); });
 }
 
 
@@ -1758,47 +1805,39 @@ int32_t xr_batch_fetch_group(xr_batch* b, int32_t group, int32_t what, void* dst
 
 // ---- lookahead -------------------------------------------------------------------------------------------------------------------
 namespace {
-// The pool of one caller (whole batch / one env group), allocated on its first lookahead: look_grid shadow slots carved out of one
-// allocation (every row starts on a 16-byte boundary), a task list for every (slot, net) pair the batch can hold, two banks of counters.
-int32_t look_pool(xr_batch* b, xr_batch::LookPool& lp, hipStream_t st, const char* who = "xr_batch_lookahead") {
-    if (lp.mem.p) return XR_OK;
-    const size_t G = (size_t)b->look_grid;
-    size_t off = 0;
-    auto carve = [&](size_t bytes) { const size_t o = off; off += (bytes + 15) & ~(size_t)15; return o; };
-    const size_t o_owner = carve(G * b->n_max * sizeof(int16_t)), o_path = carve(G * b->path_cap * sizeof(int32_t));
-    const size_t o_legal = carve(G * b->legal_words * sizeof(uint64_t)), o_hash = carve(G * sizeof(uint64_t));
-    const size_t o_reward = carve(G * sizeof(double)), o_steps = carve(G * sizeof(int64_t)), o_total = carve(sizeof(unsigned long long));
-    const size_t o_phase = carve(G * 8 * sizeof(long long)), o_rec = carve(G * sizeof(XrStepRecord));
-    const size_t o_cum = carve(G * 3 * sizeof(int32_t)), o_delta = carve(G * 3 * sizeof(int32_t));
-    const size_t o_nlegal = carve(G * sizeof(int32_t)), o_status = carve(G * sizeof(int32_t)), o_plen = carve(G * sizeof(int32_t));
-    const size_t o_sweeps = carve(G * sizeof(int32_t)), o_touched = carve(G * sizeof(int32_t)), o_region = carve(G * sizeof(int32_t));
-    const size_t o_replay = carve(G * sizeof(int32_t)), o_done = carve(G);
-    hipError_t e = lp.mem.alloc(off);
-    if (e == hipSuccess) e = lp.tasks.alloc((size_t)b->cfg.n_envs * std::max(1, b->k_max));
-    if (e == hipSuccess) e = lp.ctr.alloc(4);
-    if (e != hipSuccess) {
-        lp.release();
-        return fail(XR_ERR_NOMEM, "%s: hipMalloc of %zu bytes of shadow slots failed: %s", who, off, hipGetErrorString(e));
-    }
-    if (hipMemsetAsync(lp.ctr.p, 0, 4 * sizeof(uint32_t), st) != hipSuccess ||          // both banks start clean; every plan zeroes the other bank
-        hipMemsetAsync(lp.mem.p, 0, off, st) != hipSuccess) {
-        lp.release();
-        return fail(XR_ERR_HIP, "%s: clearing the shadow slots failed", who);
-    }
-    uint8_t* const m = lp.mem.p;
-    XrBatchDev& d = lp.shadow;
-    d = b->dev;
-    d.owner = reinterpret_cast<int16_t*>(m + o_owner); d.path = reinterpret_cast<int32_t*>(m + o_path);
-    d.legal = reinterpret_cast<uint64_t*>(m + o_legal); d.hash = reinterpret_cast<uint64_t*>(m + o_hash);
-    d.reward = reinterpret_cast<double*>(m + o_reward); d.env_steps = reinterpret_cast<int64_t*>(m + o_steps);
-    d.total_steps = reinterpret_cast<unsigned long long*>(m + o_total); d.phase_cycles = reinterpret_cast<long long*>(m + o_phase);
-    d.records = reinterpret_cast<XrStepRecord*>(m + o_rec);
-    d.cum = reinterpret_cast<int32_t*>(m + o_cum); d.delta = reinterpret_cast<int32_t*>(m + o_delta);
-    d.nlegal = reinterpret_cast<int32_t*>(m + o_nlegal); d.status = reinterpret_cast<int32_t*>(m + o_status);
-    d.path_len = reinterpret_cast<int32_t*>(m + o_plen); d.sweeps = reinterpret_cast<int32_t*>(m + o_sweeps);
-    d.touched = reinterpret_cast<int32_t*>(m + o_touched); d.env_region = reinterpret_cast<int32_t*>(m + o_region);
-    d.env_replay = reinterpret_cast<int32_t*>(m + o_replay); d.done = m + o_done;
+// What the calls that take "group -1 (the whole batch) or an env group" share; every refusal names the entry point (fn).
+// The caller's slots: [lo, lo + rows)
+int32_t group_rows(const xr_batch* b, int32_t group, const char* fn, int& lo, int& rows) {
+    if (group < -1 || group >= b->n_groups) return fail(XR_ERR_INVALID, "%s: group %d outside -1..%d", fn, group, b->n_groups - 1);
+    lo = group < 0 ? 0 : b->group_bounds[group];
+    rows = (group < 0 ? b->cfg.n_envs : b->group_bounds[group + 1]) - lo;
     return XR_OK;
+}
+
+// shadow slots route with the distance field in LDS, in one launch
+int32_t lds_field_check(const xr_batch* b, const char* fn) {
+    if (!b->lds_dist || b->cfg.stream_per_region)
+        return fail(XR_ERR_RANGE, "%s: not available for batches whose distance field lives in HBM scratch (regions too large for LDS, "
+                                  "force_scratch_field) or with stream_per_region", fn);
+    return XR_OK;
+}
+
+// two alternating banks of `width` counters: this call's and the other one, which the next call takes
+struct Banks { uint32_t *cur, *next; };
+Banks flip_banks(uint32_t* ctr, int& bank, int width) {
+    const Banks k{ctr + width * bank, ctr + width * (bank ^ 1)};
+    bank ^= 1;
+    return k;
+}
+
+// the shadow slots of a pool: look_grid slots of every state row, and the two rows of a launch that a router writes besides
+size_t shadow_carve(const xr_batch* b, uint8_t* base, xr_batch::LookPool& lp) {
+    const size_t G = (size_t)b->look_grid;
+    Carver c;
+    carve_slots(b, c, base, lp.rows, G);
+    c.place(base, lp.total_steps, 1);
+    c.place(base, lp.phase_cycles, G * 8);
+    return c.off;
 }
 
 // once per load: CUs x resident workgroups per CU of the persistent lookahead kernel (the rollout kernel has its launch bounds and its
@@ -1816,17 +1855,44 @@ hipError_t look_grid_once(xr_batch* b, const XrRouteVariant& v) {
     return hipSuccess;
 }
 
-// the shadow view: the batch as it is configured NOW (guides may have been loaded since the pool was made), rows of the shadow slots
+// the shadow view: the batch as it is configured NOW (guides may have been loaded since the pool was made), slot rows of the shadow slots
 XrBatchDev shadow_view(const xr_batch* b, const xr_batch::LookPool& lp) {
     XrBatchDev sh = b->dev;
-    const XrBatchDev& p = lp.shadow;
-    sh.owner = p.owner; sh.path = p.path; sh.legal = p.legal; sh.hash = p.hash; sh.reward = p.reward; sh.env_steps = p.env_steps;
-    sh.total_steps = p.total_steps; sh.phase_cycles = p.phase_cycles; sh.records = p.records; sh.cum = p.cum; sh.delta = p.delta;
-    sh.nlegal = p.nlegal; sh.status = p.status; sh.path_len = p.path_len; sh.sweeps = p.sweeps; sh.touched = p.touched;
-    sh.env_region = p.env_region; sh.env_replay = p.env_replay; sh.done = p.done;
+    copy_slot_rows(sh, lp.rows);
+    sh.total_steps = lp.total_steps; sh.phase_cycles = lp.phase_cycles;
     sh.auto_reset = 0; sh.net_meas = nullptr; sh.obs_out = nullptr; sh.obs_out_u8 = nullptr; sh.route_order = nullptr;
     sh.n_envs = b->look_grid; sh.env_base = 0; sh.env_count = 0;
     return sh;
+}
+
+// The pool of one caller (whole batch / one env group), brought up on its first call: look_grid shadow slots in one allocation, a task list
+// for every (slot, net) pair the batch can hold, two banks of counters; with roll_ctr, the claim counters of the rollout kernel too
+int32_t shadow_pool(xr_batch* b, xr_batch::LookPool& lp, const XrRouteVariant& v, hipStream_t st, const char* fn, bool roll_ctr) {
+    XR_HIP(look_grid_once(b, v));
+    if (!lp.mem.p) {
+        const size_t bytes = shadow_carve(b, nullptr, lp);
+        hipError_t e = lp.mem.alloc(bytes);
+        if (e == hipSuccess) e = lp.tasks.alloc((size_t)b->cfg.n_envs * std::max(1, b->k_max));
+        if (e == hipSuccess) e = lp.ctr.alloc(4);
+        if (e != hipSuccess) {
+            lp.release();
+            return fail(XR_ERR_NOMEM, "%s: hipMalloc of %zu bytes of shadow slots failed: %s", fn, bytes, hipGetErrorString(e));
+        }
+        if (hipMemsetAsync(lp.ctr.p, 0, 4 * sizeof(uint32_t), st) != hipSuccess ||          // both banks start clean; every plan zeroes the other bank
+            hipMemsetAsync(lp.mem.p, 0, bytes, st) != hipSuccess) {
+            lp.release();
+            return fail(XR_ERR_HIP, "%s: clearing the shadow slots failed", fn);
+        }
+        shadow_carve(b, lp.mem.p, lp);
+    }
+    if (roll_ctr && !lp.roll_ctr.p) {          // both banks start clean; every launch zeroes the other bank
+        if (lp.roll_ctr.alloc(2) != hipSuccess) return fail(XR_ERR_NOMEM, "%s: hipMalloc of the claim counters failed", fn);
+        if (hipMemsetAsync(lp.roll_ctr.p, 0, 2 * sizeof(uint32_t), st) != hipSuccess) {
+            lp.roll_ctr.release();
+            return fail(XR_ERR_HIP, "%s: clearing the claim counters failed", fn);
+        }
+    }
+    return XR_OK;
 }
 }  // namespace
 
@@ -1834,13 +1900,10 @@ int32_t xr_batch_lookahead(xr_batch* b, int32_t group, const uint64_t* cand_mask
                            void* stream) {
     if (!b || !out_dev) return fail(XR_ERR_INVALID, "xr_batch_lookahead: null argument");
     if (!b->loaded) return fail(XR_ERR_STATE, "xr_batch_lookahead: load regions first");
-    if (group < -1 || group >= b->n_groups) return fail(XR_ERR_INVALID, "xr_batch_lookahead: group %d outside -1..%d", group, b->n_groups - 1);
+    int lo, rows;
+    if (const int32_t rc = group_rows(b, group, "xr_batch_lookahead", lo, rows)) return rc;
     if (k_cap < b->k_max) return fail(XR_ERR_RANGE, "xr_batch_lookahead: k_cap %d < k_max %d", k_cap, b->k_max);
-    if (!b->lds_dist || b->cfg.stream_per_region)
-        return fail(XR_ERR_RANGE, "xr_batch_lookahead: not available for batches whose distance field lives in HBM scratch (regions too large for LDS, "
-                                  "force_scratch_field) or with stream_per_region");
-    const int lo = group < 0 ? 0 : b->group_bounds[group];
-    const int rows = group < 0 ? b->cfg.n_envs : b->group_bounds[group + 1] - lo;
+    if (const int32_t rc = lds_field_check(b, "xr_batch_lookahead")) return rc;
     if ((int64_t)b->cfg.n_envs * std::max(1, b->k_max) >= ((int64_t)1 << 31) || (int64_t)rows * k_cap >= ((int64_t)1 << 31))
         return fail(XR_ERR_RANGE, "xr_batch_lookahead: n_envs x k_max (or rows x k_cap) does not fit 31 bits");
     if (!xr_lookahead_occupancy || !xr_launch_lookahead_plan || !xr_launch_lookahead)
@@ -1848,17 +1911,14 @@ int32_t xr_batch_lookahead(xr_batch* b, int32_t group, const uint64_t* cand_mask
     XR_HIP(hipSetDevice(b->cfg.device));
     hipStream_t st = static_cast<hipStream_t>(stream);
     const XrRouteVariant v = route_variant(b);
-    XR_HIP(look_grid_once(b, v));
     xr_batch::LookPool& lp = b->look[group + 1];
-    if (const int32_t rc = look_pool(b, lp, st)) return rc;
+    if (const int32_t rc = shadow_pool(b, lp, v, st, "xr_batch_lookahead", false)) return rc;
     const XrBatchDev sh = shadow_view(b, lp);
-    uint32_t* const ctr = lp.ctr.p + 2 * lp.bank;
-    uint32_t* const next_ctr = lp.ctr.p + 2 * (lp.bank ^ 1);
-    lp.bank ^= 1;
-    XR_HIP(xr_launch_lookahead_plan(&b->dev, lo, rows, cand_mask_dev, out_dev, reward_out_dev, k_cap, b->k_max, lp.tasks.p, ctr, next_ctr, st));
+    const Banks ctr = flip_banks(lp.ctr.p, lp.bank, 2);
+    XR_HIP(xr_launch_lookahead_plan(&b->dev, lo, rows, cand_mask_dev, out_dev, reward_out_dev, k_cap, b->k_max, lp.tasks.p, ctr.cur, ctr.next, st));
     if (b->k_max < 1) return XR_OK;          // (no region has a net: the fill is the whole answer)
     const int blocks = (int)std::min<int64_t>(b->look_grid, (int64_t)rows * b->k_max);
-    XR_HIP(xr_launch_lookahead(&b->dev, &sh, lo, lp.tasks.p, ctr, out_dev, reward_out_dev, k_cap, b->k_max, v, blocks, st));
+    XR_HIP(xr_launch_lookahead(&b->dev, &sh, lo, lp.tasks.p, ctr.cur, out_dev, reward_out_dev, k_cap, b->k_max, v, blocks, st));
     return XR_OK;
 }
 
@@ -1868,40 +1928,27 @@ int32_t xr_batch_rollout(xr_batch* b, int32_t group, int32_t n_rollouts, int32_t
                          void* stream) {
     if (!b || !out_dev) return fail(XR_ERR_INVALID, "xr_batch_rollout: null argument");
     if (!b->loaded) return fail(XR_ERR_STATE, "xr_batch_rollout: load regions first");
-    if (group < -1 || group >= b->n_groups) return fail(XR_ERR_INVALID, "xr_batch_rollout: group %d outside -1..%d", group, b->n_groups - 1);
+    int lo, rows;
+    if (const int32_t rc = group_rows(b, group, "xr_batch_rollout", lo, rows)) return rc;
     if (policy != XR_ROLLOUT_STOP && policy != XR_ROLLOUT_RANDOM) return fail(XR_ERR_INVALID, "xr_batch_rollout: unknown policy %d", policy);
     if (prefix_dev && prefix_stride < 1) return fail(XR_ERR_INVALID, "xr_batch_rollout: prefix_stride %d < 1 with a prefix", prefix_stride);
     if (max_plies < 0) return fail(XR_ERR_INVALID, "xr_batch_rollout: max_plies %d is negative", max_plies);
     if (n_rollouts < 1 || n_rollouts > XR_ROLLOUT_MAX)
         return fail(XR_ERR_RANGE, "xr_batch_rollout: n_rollouts %d outside 1..%d", n_rollouts, XR_ROLLOUT_MAX);
     if (order_out_dev && k_cap < b->k_max) return fail(XR_ERR_RANGE, "xr_batch_rollout: k_cap %d < k_max %d", k_cap, b->k_max);
-    if (!b->lds_dist || b->cfg.stream_per_region)
-        return fail(XR_ERR_RANGE, "xr_batch_rollout: not available for batches whose distance field lives in HBM scratch (regions too large for LDS, "
-                                  "force_scratch_field) or with stream_per_region");
-    const int lo = group < 0 ? 0 : b->group_bounds[group];
-    const int rows = group < 0 ? b->cfg.n_envs : b->group_bounds[group + 1] - lo;
+    if (const int32_t rc = lds_field_check(b, "xr_batch_rollout")) return rc;
     const int64_t tasks = (int64_t)rows * n_rollouts;
     if (tasks >= ((int64_t)1 << 31)) return fail(XR_ERR_RANGE, "xr_batch_rollout: rows x n_rollouts does not fit 31 bits");
     if (!xr_lookahead_occupancy || !xr_launch_rollout) return fail(XR_ERR_STATE, "xr_batch_rollout: rollout kernels not linked");
     XR_HIP(hipSetDevice(b->cfg.device));
     hipStream_t st = static_cast<hipStream_t>(stream);
     const XrRouteVariant v = route_variant(b);
-    XR_HIP(look_grid_once(b, v));
     xr_batch::LookPool& lp = b->look[group + 1];
-    if (const int32_t rc = look_pool(b, lp, st, "xr_batch_rollout")) return rc;
-    if (!lp.roll_ctr.p) {          // both banks start clean; every launch zeroes the other bank
-        if (lp.roll_ctr.alloc(2) != hipSuccess) return fail(XR_ERR_NOMEM, "xr_batch_rollout: hipMalloc of the claim counters failed");
-        if (hipMemsetAsync(lp.roll_ctr.p, 0, 2 * sizeof(uint32_t), st) != hipSuccess) {
-            lp.roll_ctr.release();
-            return fail(XR_ERR_HIP, "xr_batch_rollout: clearing the claim counters failed");
-        }
-    }
+    if (const int32_t rc = shadow_pool(b, lp, v, st, "xr_batch_rollout", true)) return rc;
     const XrBatchDev sh = shadow_view(b, lp);
-    uint32_t* const ctr = lp.roll_ctr.p + lp.roll_bank;
-    uint32_t* const next_ctr = lp.roll_ctr.p + (lp.roll_bank ^ 1);
-    lp.roll_bank ^= 1;
+    const Banks ctr = flip_banks(lp.roll_ctr.p, lp.roll_bank, 1);
     const int blocks = (int)std::min<int64_t>(b->look_grid, tasks);
-    XR_HIP(xr_launch_rollout(&b->dev, &sh, lo, (int)tasks, n_rollouts, policy, seed, prefix_dev, prefix_dev ? prefix_stride : 0, max_plies, ctr, next_ctr,
+    XR_HIP(xr_launch_rollout(&b->dev, &sh, lo, (int)tasks, n_rollouts, policy, seed, prefix_dev, prefix_dev ? prefix_stride : 0, max_plies, ctr.cur, ctr.next,
                              out_dev, return_out_dev, hash_out_dev, order_out_dev, order_out_dev ? k_cap : 0, v, blocks, st));
     return XR_OK;
 }
@@ -1931,7 +1978,8 @@ int32_t xr_batch_tree_search(xr_batch* b, int32_t group, int32_t n_waves, int32_
                              int32_t* best_order_out_dev, double* best_return_out_dev, int32_t* paths_out_dev, double* returns_out_dev, void* stream) {
     if (!b || !visits_out_dev || !value_out_dev || !info_out_dev) return fail(XR_ERR_INVALID, "xr_batch_tree_search: null argument");
     if (!b->loaded) return fail(XR_ERR_STATE, "xr_batch_tree_search: load regions first");
-    if (group < -1 || group >= b->n_groups) return fail(XR_ERR_INVALID, "xr_batch_tree_search: group %d outside -1..%d", group, b->n_groups - 1);
+    int lo, rows;
+    if (const int32_t rc = group_rows(b, group, "xr_batch_tree_search", lo, rows)) return rc;
     if (n_waves < 1) return fail(XR_ERR_INVALID, "xr_batch_tree_search: n_waves %d < 1", n_waves);
     if (n_par < 1) return fail(XR_ERR_INVALID, "xr_batch_tree_search: n_par %d < 1", n_par);
     if (!std::isfinite(c_init)) return fail(XR_ERR_INVALID, "xr_batch_tree_search: c_init is not finite");
@@ -1941,11 +1989,7 @@ int32_t xr_batch_tree_search(xr_batch* b, int32_t group, int32_t n_waves, int32_
         return fail(XR_ERR_RANGE, "xr_batch_tree_search: n_waves x n_par = %lld simulations above %d", (long long)n_waves * n_par, XR_TREE_MAX_SIMS);
     if (node_cap < 1) return fail(XR_ERR_RANGE, "xr_batch_tree_search: node_cap %d < 1", node_cap);
     if (k_cap < b->k_max) return fail(XR_ERR_RANGE, "xr_batch_tree_search: k_cap %d < k_max %d", k_cap, b->k_max);
-    if (!b->lds_dist || b->cfg.stream_per_region)
-        return fail(XR_ERR_RANGE, "xr_batch_tree_search: not available for batches whose distance field lives in HBM scratch (regions too large for LDS, "
-                                  "force_scratch_field) or with stream_per_region");
-    const int lo = group < 0 ? 0 : b->group_bounds[group];
-    const int rows = group < 0 ? b->cfg.n_envs : b->group_bounds[group + 1] - lo;
+    if (const int32_t rc = lds_field_check(b, "xr_batch_tree_search")) return rc;
     const int64_t tasks = (int64_t)rows * n_par;
     if (tasks >= ((int64_t)1 << 31)) return fail(XR_ERR_RANGE, "xr_batch_tree_search: rows x n_par does not fit 31 bits");
     if (!xr_lookahead_occupancy || !xr_launch_rollout || !xr_launch_tree_reset || !xr_launch_tree_select || !xr_launch_tree_backup)
@@ -1955,29 +1999,21 @@ int32_t xr_batch_tree_search(xr_batch* b, int32_t group, int32_t n_waves, int32_
     // the private memory: six arrays in one allocation, each starting on a 16-byte boundary
     if ((double)rows * ((double)node_cap * sizeof(XrTreeNode) + (double)n_par * (8.0 * k_cap + 40.0) + 64.0) > 1e15)
         return fail(XR_ERR_NOMEM, "xr_batch_tree_search: %d rows x %d nodes do not fit any device", rows, node_cap);
-    size_t off = 0;
-    auto carve = [&](size_t bytes) { const size_t o = off; off = (off + bytes + 15) & ~(size_t)15; return o; };
+    Carver c;
     const size_t R = (size_t)rows, P = (size_t)n_par, K = (size_t)k_cap;
-    const size_t o_nodes = carve(R * (size_t)node_cap * sizeof(XrTreeNode)), o_rs = carve(R * sizeof(XrTreeRow));
-    const size_t o_prefix = carve(R * P * K * sizeof(int32_t)), o_order = carve(R * P * K * sizeof(int32_t));
-    const size_t o_rec = carve(R * P * 8 * sizeof(int32_t)), o_ret = carve(R * P * sizeof(double));
+    const size_t o_nodes = c.take(R * (size_t)node_cap * sizeof(XrTreeNode)), o_rs = c.take(R * sizeof(XrTreeRow));
+    const size_t o_prefix = c.take(R * P * K * sizeof(int32_t)), o_order = c.take(R * P * K * sizeof(int32_t));
+    const size_t o_rec = c.take(R * P * 8 * sizeof(int32_t)), o_ret = c.take(R * P * sizeof(double));
     XR_HIP(hipSetDevice(b->cfg.device));
     hipStream_t st = static_cast<hipStream_t>(stream);
     const XrRouteVariant v = route_variant(b);
-    XR_HIP(look_grid_once(b, v));
     xr_batch::LookPool& lp = b->look[group + 1];
-    if (const int32_t rc = look_pool(b, lp, st, "xr_batch_tree_search")) return rc;
-    if (!lp.roll_ctr.p) {          // (as xr_batch_rollout: both banks start clean; every launch zeroes the other bank)
-        if (lp.roll_ctr.alloc(2) != hipSuccess) return fail(XR_ERR_NOMEM, "xr_batch_tree_search: hipMalloc of the claim counters failed");
-        if (hipMemsetAsync(lp.roll_ctr.p, 0, 2 * sizeof(uint32_t), st) != hipSuccess) {
-            lp.roll_ctr.release();
-            return fail(XR_ERR_HIP, "xr_batch_tree_search: clearing the claim counters failed");
-        }
-    }
+    if (const int32_t rc = shadow_pool(b, lp, v, st, "xr_batch_tree_search", true)) return rc;
+    const XrBatchDev sh = shadow_view(b, lp);
     xr_batch::TreePool& tp = b->tree[group + 1];
-    if (tp.mem.n < off && tp.mem.alloc(off) != hipSuccess) {
+    if (tp.mem.n < c.off && tp.mem.alloc(c.off) != hipSuccess) {
         tp.mem.release();
-        return fail(XR_ERR_NOMEM, "xr_batch_tree_search: hipMalloc of %zu bytes of trees failed", off);
+        return fail(XR_ERR_NOMEM, "xr_batch_tree_search: hipMalloc of %zu bytes of trees failed", c.off);
     }
     xr_batch::TreeTable* tab = nullptr;
     for (auto& t : tp.tables)
@@ -2003,73 +2039,39 @@ int32_t xr_batch_tree_search(xr_batch* b, int32_t group, int32_t n_waves, int32_
     t.node_cap = node_cap; t.n_par = n_par; t.k_cap = k_cap; t.n_sims = n_sims; t.env_lo = lo;
     t.visits_out = visits_out_dev; t.value_out = value_out_dev; t.info_out = info_out_dev; t.best_order_out = best_order_out_dev;
     t.best_return_out = best_return_out_dev; t.paths_out = paths_out_dev; t.returns_out = returns_out_dev;
-    const XrBatchDev sh = shadow_view(b, lp);
     const int blocks = (int)std::min<int64_t>(b->look_grid, tasks);
     XR_HIP(xr_launch_tree_reset(&b->dev, &t, rows, st));
     for (int w = 0; w < n_waves; w++) {
         XR_HIP(xr_launch_tree_select(&b->dev, &t, rows, w, st));
-        uint32_t* const ctr = lp.roll_ctr.p + lp.roll_bank;
-        uint32_t* const next_ctr = lp.roll_ctr.p + (lp.roll_bank ^ 1);
-        lp.roll_bank ^= 1;
-        XR_HIP(xr_launch_rollout(&b->dev, &sh, lo, (int)tasks, n_par, XR_ROLLOUT_RANDOM, seed + (uint64_t)w * 0xD1B54A32D192ED03ULL, t.prefix, k_cap, 0, ctr,
-                                 next_ctr, rec, t.ret, nullptr, t.order, k_cap, v, blocks, st));
+        const Banks ctr = flip_banks(lp.roll_ctr.p, lp.roll_bank, 1);
+        XR_HIP(xr_launch_rollout(&b->dev, &sh, lo, (int)tasks, n_par, XR_ROLLOUT_RANDOM, seed + (uint64_t)w * 0xD1B54A32D192ED03ULL, t.prefix, k_cap, 0, ctr.cur,
+                                 ctr.next, rec, t.ret, nullptr, t.order, k_cap, v, blocks, st));
         XR_HIP(xr_launch_tree_backup(&b->dev, &t, rows, w, w == n_waves - 1 ? 1 : 0, st));
     }
     return XR_OK;
 }
 
 // ---- branch ------------------------------------------------------------------------------------------------------------------------
-namespace {
-// bytes of one slot's state: the rows xr_batch_branch moves, each array of a staging pool starting on a 16-byte boundary
-size_t branch_carve(const xr_batch* b, size_t rows, uint8_t* m, XrBranchRows* out) {
-    size_t off = 0;
-    auto carve = [&](size_t row_bytes) { const size_t o = off; off = (off + rows * row_bytes + 15) & ~(size_t)15; return o; };
-    const size_t o_owner = carve((size_t)b->n_max * sizeof(int16_t)), o_path = carve((size_t)b->path_cap * sizeof(int32_t));
-    const size_t o_legal = carve((size_t)b->legal_words * sizeof(uint64_t)), o_reward = carve(sizeof(double)), o_hash = carve(sizeof(uint64_t));
-    const size_t o_steps = carve(sizeof(int64_t)), o_rec = carve(sizeof(XrStepRecord)), o_cum = carve(3 * sizeof(int32_t));
-    const size_t o_delta = carve(3 * sizeof(int32_t)), o_nlegal = carve(sizeof(int32_t)), o_status = carve(sizeof(int32_t));
-    const size_t o_plen = carve(sizeof(int32_t)), o_region = carve(sizeof(int32_t)), o_replay = carve(sizeof(int32_t));
-    const size_t o_sweeps = carve(sizeof(int32_t)), o_touched = carve(sizeof(int32_t)), o_done = carve(1);
-    if (out) {
-        XrBranchRows& r = *out;
-        r.owner = reinterpret_cast<int16_t*>(m + o_owner); r.path = reinterpret_cast<int32_t*>(m + o_path);
-        r.legal = reinterpret_cast<uint64_t*>(m + o_legal); r.reward = reinterpret_cast<double*>(m + o_reward);
-        r.hash = reinterpret_cast<uint64_t*>(m + o_hash); r.env_steps = reinterpret_cast<int64_t*>(m + o_steps);
-        r.records = reinterpret_cast<XrStepRecord*>(m + o_rec); r.cum = reinterpret_cast<int32_t*>(m + o_cum);
-        r.delta = reinterpret_cast<int32_t*>(m + o_delta); r.nlegal = reinterpret_cast<int32_t*>(m + o_nlegal);
-        r.status = reinterpret_cast<int32_t*>(m + o_status); r.path_len = reinterpret_cast<int32_t*>(m + o_plen);
-        r.env_region = reinterpret_cast<int32_t*>(m + o_region); r.env_replay = reinterpret_cast<int32_t*>(m + o_replay);
-        r.sweeps = reinterpret_cast<int32_t*>(m + o_sweeps); r.touched = reinterpret_cast<int32_t*>(m + o_touched); r.done = m + o_done;
-    }
-    return off;
-}
-}  // namespace
-
 int32_t xr_batch_branch(xr_batch* b, int32_t group, const int32_t* parent_dev, void* stream) {
     if (!b || !parent_dev) return fail(XR_ERR_INVALID, "xr_batch_branch: null argument");
     if (!b->loaded) return fail(XR_ERR_STATE, "xr_batch_branch: load regions first");
-    if (group < -1 || group >= b->n_groups) return fail(XR_ERR_INVALID, "xr_batch_branch: group %d outside -1..%d", group, b->n_groups - 1);
+    int lo, rows;
+    if (const int32_t rc = group_rows(b, group, "xr_batch_branch", lo, rows)) return rc;
     if (!xr_launch_branch) return fail(XR_ERR_STATE, "xr_batch_branch: branch kernels not linked");
-    const int lo = group < 0 ? 0 : b->group_bounds[group];
-    const int rows = group < 0 ? b->cfg.n_envs : b->group_bounds[group + 1] - lo;
     XR_HIP(hipSetDevice(b->cfg.device));
     hipStream_t st = static_cast<hipStream_t>(stream);
     xr_batch::BranchPool& bp = b->branch[group + 1];
     if (bp.rows < rows) {              // the first branch of this caller (or its group has grown since: xr_batch_set_groups)
         bp.release();
-        const size_t bytes = branch_carve(b, (size_t)rows, nullptr, nullptr);
-        if (bp.mem.alloc(bytes) != hipSuccess) {
+        Carver size, place;            // the staging rows: one slot of every state row per row of the caller
+        carve_slots(b, size, nullptr, bp.stg, (size_t)rows);
+        if (bp.mem.alloc(size.off) != hipSuccess) {
             bp.release();
-            return fail(XR_ERR_NOMEM, "xr_batch_branch: hipMalloc of %zu bytes of staging rows failed", bytes);
+            return fail(XR_ERR_NOMEM, "xr_batch_branch: hipMalloc of %zu bytes of staging rows failed", size.off);
         }
         bp.rows = rows;
-        branch_carve(b, (size_t)rows, bp.mem.p, &bp.stg);
+        carve_slots(b, place, bp.mem.p, bp.stg, (size_t)rows);
     }
-    const XrBatchDev& d = b->dev;
-    XrBranchRows env{};
-    env.owner = d.owner; env.path = d.path; env.legal = d.legal; env.nlegal = d.nlegal; env.cum = d.cum; env.delta = d.delta;
-    env.status = d.status; env.path_len = d.path_len; env.env_region = d.env_region; env.env_replay = d.env_replay; env.sweeps = d.sweeps;
-    env.touched = d.touched; env.reward = d.reward; env.done = d.done; env.hash = d.hash; env.env_steps = d.env_steps; env.records = d.records;
     // workgroups per row: about 4 KB of the two long rows each (one 16-byte vector per thread), fewer once the rows alone fill the chip
     const size_t long_bytes = (size_t)b->n_max * sizeof(int16_t) + (size_t)b->path_cap * sizeof(int32_t);
     int chunks = (int)std::min<size_t>(32, std::max<size_t>(1, long_bytes / 4096));
@@ -2081,6 +2083,8 @@ int32_t xr_batch_branch(xr_batch* b, int32_t group, const int32_t* parent_dev, v
         b->obs_valid.clear();
         b->group_valid[group].clear();
     }
+    XrSlotRows env{};
+    copy_slot_rows(env, b->dev);
     XR_HIP(xr_launch_branch(&env, &bp.stg, lo, rows, parent_dev, b->n_max, b->path_cap, b->legal_words, chunks, st));
     return XR_OK;
 }

@@ -36,7 +36,8 @@ __device__ __forceinline__ void xr_branch_copy_row(const void* __restrict__ s, v
 }
 
 // everything that is state of one slot: row sr of `s` to row dr of `d`
-__device__ __forceinline__ void xr_branch_copy_slot(const XrBranchRows& s, const int64_t sr, const XrBranchRows& d, const int64_t dr, const int n_max,
+static_assert(sizeof(XrSlotRows) == 17 * sizeof(void*), "xr_branch_copy_slot moves 17 rows");   // a row added to XrSlotRows is moved here too, or branch drops it
+__device__ __forceinline__ void xr_branch_copy_slot(const XrSlotRows& s, const int64_t sr, const XrSlotRows& d, const int64_t dr, const int n_max,
                                                     const int path_cap, const int words) {
     const int t = blockIdx.y * blockDim.x + threadIdx.x, nt = gridDim.y * blockDim.x;
     xr_branch_copy_row(s.owner + sr * n_max, d.owner + dr * n_max, (uint32_t)n_max * 2u, t, nt);
@@ -67,7 +68,7 @@ __device__ __forceinline__ void xr_branch_copy_slot(const XrBranchRows& s, const
 
 // env: the batch's rows (absolute slots; the map's row i is slot env_lo + i).  stg: the caller's staging pool, `rows` rows.
 template <int PASS>
-__global__ void __launch_bounds__(256) xr_branch_kernel(XrBranchRows env, XrBranchRows stg, int env_lo, int rows, const int32_t* __restrict__ parent,
+__global__ void __launch_bounds__(256) xr_branch_kernel(XrSlotRows env, XrSlotRows stg, int env_lo, int rows, const int32_t* __restrict__ parent,
                                                         int n_max, int path_cap, int words) {
     const int i = blockIdx.x;
     const int p = parent[i];

@@ -79,13 +79,30 @@ struct XrStepRecord {
 };
 static_assert(sizeof(XrStepRecord) == 48, "xr_step_record layout");
 
+// The per-env rows that ARE the state of a slot (everything xr_batch_fetch returns per env): the rows of a pool of shadow slots
+// (xr_lookahead.h), of a staging pool of xr_batch_branch (xr_branch.h), or a view of the batch's own arrays.  XrBatchDev holds members of
+// the same names and types at offsets of its own: deriving from this struct would move them to the front of the kernel argument, which
+// costs the route kernel 2 % (LAB_NOTES.md section 15).  The host pairs the two in ONE list, for_each_slot_row (xr_batch.cpp)
+struct XrSlotRows {
+    int16_t* owner;          // [rows][n_max]
+    int32_t* path;           // [rows][path_cap]
+    uint64_t* legal;         // [rows][legal_words]
+    int32_t *nlegal, *cum, *delta, *status, *path_len, *env_region, *env_replay, *sweeps, *touched;   // cum, delta: [rows][3]; touched: nodes whose
+                             // field word the last route created (HBM-scratch form of the frontier router; else 0)
+    double* reward;
+    uint8_t* done;
+    uint64_t* hash;
+    int64_t* env_steps;
+    XrStepRecord* records;
+};
+
 // one past the last env slot of a launch (XrBatchDev::env_base / env_count)
 #define XR_ENV_END(b) ((b).env_count > 0 ? (b).env_base + (b).env_count : (b).n_envs)
 
-// Everything a kernel needs, passed by value.
 // nets of an env with K nets left whose planes the step kernel writes itself in the split form
 #define XR_SPLIT_KEEP(b, K) ((K) - (int)(((int64_t)(K) * (b).obs_split_pm) / 1000))
 
+// Everything a kernel needs, passed by value.
 struct XrBatchDev {
     // regions (static)
     const XrRegionDev* regions;
@@ -125,6 +142,7 @@ struct XrBatchDev {
     int32_t x_max, y_max;    // largest dims over regions (edge-length tables)
     int32_t legal_words;
     int32_t path_cap;
+    // the slot rows (XrSlotRows above: same names, same types): the batch's own env slots, or the shadow slots of a shadow view
     int32_t* env_region;
     int32_t* env_replay;
     int16_t* owner;
@@ -139,9 +157,9 @@ struct XrBatchDev {
     int32_t* path_len;
     uint64_t* hash;
     int64_t* env_steps;
-    unsigned long long* total_steps;
+    unsigned long long* total_steps;   // (not slot state: branch does not move it, a pool of shadow slots has one of its own)
     int32_t* sweeps;
-    int32_t* touched;        // [B] nodes whose field word the last route created (HBM-scratch form of the frontier router; else 0)
+    int32_t* touched;
     XrStepRecord* records;   // [B]
     uint32_t* dist_scratch;  // [B][n_max] only when the distance field does not fit LDS, else null
     uint8_t* cls_scratch;
@@ -151,7 +169,7 @@ struct XrBatchDev {
     uint32_t* dg_masks;      // [B][2][n_max/32 + 1]  open bits, cached word minima
     uint32_t* dg_touch;      // [B][n_max]  nodes touched by the current route
     uint32_t* dg_path;       // [B][2][n_max]  path of the current trace; deferred nodes
-    long long* phase_cycles; // [B][8] thread-0 cycle counts per kernel phase (only written with -DXR_PHASE_TIMING)
+    long long* phase_cycles; // [B][8] thread-0 cycle counts per kernel phase (only written with -DXR_PHASE_TIMING); not slot state either
     // fused observation output of the step kernel (null: route only)
     float* obs_out;
     int64_t obs_stride;      // floats per env
@@ -191,20 +209,7 @@ struct XrBatchDev {
     // (xr_unit_u8_aligned), 2 = any N (xr_unit_u8_stream, LDS masks)
     uint8_t* obs_out_u8;
 };
-
-// The per-env rows that ARE the state of a slot (everything xr_batch_fetch returns per env): the batch's own arrays, or the rows of a staging
-// pool of xr_batch_branch (xr_branch.h)
-struct XrBranchRows {
-    int16_t* owner;          // [rows][n_max]
-    int32_t* path;           // [rows][path_cap]
-    uint64_t* legal;         // [rows][legal_words]
-    int32_t *nlegal, *cum, *delta, *status, *path_len, *env_region, *env_replay, *sweeps, *touched;
-    double* reward;
-    uint8_t* done;
-    uint64_t* hash;
-    int64_t* env_steps;
-    XrStepRecord* records;
-};
+static_assert(__is_trivially_copyable(XrBatchDev), "XrBatchDev is a kernel argument");
 
 // Tree search (xr_tree.h, xr_batch_tree_search).  One node of a row's tree: a set of nets routed after the env's current state
 struct XrTreeNode {
@@ -279,7 +284,7 @@ hipError_t xr_launch_rollout(const XrBatchDev* src, const XrBatchDev* shadow, in
                              const int32_t* prefix, int prefix_stride, int max_plies, uint32_t* ctr, uint32_t* next_ctr, int32_t* out, double* return_out,
                              uint64_t* hash_out, int32_t* order_out, int k_cap, XrRouteVariant v, int blocks, hipStream_t st) __attribute__((weak));
 // branch (xr_branch.h): both passes, in stream order.  Weak for the same reason: xr_batch_branch answers XR_ERR_STATE where it is not linked
-hipError_t xr_launch_branch(const XrBranchRows* env, const XrBranchRows* stg, int env_lo, int rows, const int32_t* parent, int n_max, int path_cap,
+hipError_t xr_launch_branch(const XrSlotRows* env, const XrSlotRows* stg, int env_lo, int rows, const int32_t* parent, int n_max, int path_cap,
                             int legal_words, int chunks, hipStream_t st) __attribute__((weak));
 // tree search (xr_tree.h).  Weak for the same reason: xr_batch_tree_search answers XR_ERR_STATE where they are not linked
 hipError_t xr_launch_tree_reset(const XrBatchDev* src, const XrTreeDev* t, int rows, hipStream_t st) __attribute__((weak));

@@ -2333,7 +2333,7 @@ hipError_t xr_launch_rollout(const XrBatchDev* src, const XrBatchDev* shadow, in
 }
 
 // branch (xr_branch.h): workgroup (i, c) = chunk c of row i; the stream orders the staging pass before the writing pass
-hipError_t xr_launch_branch(const XrBranchRows* env, const XrBranchRows* stg, int env_lo, int rows, const int32_t* parent, int n_max, int path_cap,
+hipError_t xr_launch_branch(const XrSlotRows* env, const XrSlotRows* stg, int env_lo, int rows, const int32_t* parent, int n_max, int path_cap,
                             int legal_words, int chunks, hipStream_t st) {
     const dim3 g(rows, chunks), t(256);
     hipLaunchKernelGGL(xr_branch_kernel<0>, g, t, 0, st, *env, *stg, env_lo, rows, parent, n_max, path_cap, legal_words);

@@ -5,9 +5,9 @@
 //                              task list for the env (one atomic per env), writes one task per candidate and the {0, 0, 0, -1} / -inf fill
 //                              of every other entry of the output tables; zeroes the counters of the NEXT call (two alternating banks).
 //   xr_lookahead_kernel        persistent launch (as many workgroups as the chip holds).  Every workgroup owns one SHADOW SLOT: private rows
-//                              for everything a router writes per env, reached through a copy of XrBatchDev whose mutable per-env pointers
-//                              point at them (auto_reset = 0, net_meas = null, obs_out = null).  Per task, claimed with one atomic on a global
-//                              counter: copy the env's owner row and scalars into the shadow slot, run the SAME router instantiation the step
+//                              for everything a router writes per env, reached through a copy of XrBatchDev whose slot rows (and
+//                              total_steps, phase_cycles) point at them (auto_reset = 0, net_meas = null, obs_out = null).  Per task, claimed
+//                              with one atomic on a global counter: xr_shadow_load the env into the shadow slot, run the SAME router instantiation the step
 //                              takes (xr_route_dispatch) on the shadow slot, copy the shadow delta / status / reward to the task's entry.
 // The batch's own rows are only ever read.  No workgroup waits for another one, so launches of different env groups (each with a pool of
 // shadow slots and counters of its own) may share the chip in any interleaving.
@@ -61,6 +61,28 @@ __global__ void __launch_bounds__(256) xr_lookahead_plan_kernel(XrBatchDev b, in
     }
 }
 
+// Env e of src into shadow slot s of sh, by the whole workgroup (the caller's barrier comes after it): what a router reads of a slot before
+// it writes it.  The owner row as 16-byte vectors (n_max is a multiple of 8 elements, rows are 16-byte aligned), legal words, thread 0's scalars.
+// ord (null: none): a rollout's order row, zeroed HERE, before thread 0's scalars — after them the rollout kernel measured 1 % slower
+__device__ __forceinline__ void xr_shadow_load(const XrBatchDev& src, const int e, const XrBatchDev& sh, const int s, int16_t* const sh_owner,
+                                               const int words, const int tid, int32_t* const ord = nullptr, const int k_cap = 0) {
+    const int N = src.regions[src.env_region[e]].N;
+    const int4* s4 = reinterpret_cast<const int4*>(src.owner + (int64_t)e * src.n_max);
+    int4* d4 = reinterpret_cast<int4*>(sh_owner);
+    const int nvec = (N + 7) >> 3;
+    for (int i = tid; i < nvec; i += blockDim.x) d4[i] = s4[i];
+    for (int w = tid; w < words; w += blockDim.x) sh.legal[(int64_t)s * words + w] = src.legal[(int64_t)e * words + w];
+    if (ord)
+        for (int k = tid; k < k_cap; k += blockDim.x) ord[k] = 0;
+    if (tid == 0) {
+        sh.env_region[s] = src.env_region[e]; sh.env_replay[s] = src.env_replay[e];
+        sh.nlegal[s] = src.nlegal[e];
+        sh.cum[3 * s] = src.cum[3 * e]; sh.cum[3 * s + 1] = src.cum[3 * e + 1]; sh.cum[3 * s + 2] = src.cum[3 * e + 2];
+        sh.hash[s] = src.hash[e];
+        sh.env_steps[s] = src.env_steps[e];
+    }
+}
+
 // src: the batch (read only).  sh: its shadow view — per-env rows of `grid` shadow slots, slot s = workgroup s.
 template <bool LDS_DIST, int ZCH>
 __global__ void __launch_bounds__(1024, 4) xr_lookahead_kernel(XrBatchDev src, XrBatchDev sh, int env_lo, const uint32_t* __restrict__ tasks,
@@ -82,22 +104,7 @@ __global__ void __launch_bounds__(1024, 4) xr_lookahead_kernel(XrBatchDev src, X
         if (task < 0) break;
         const int row = task / k_max, net = task - row * k_max + 1;
         const int e = env_lo + row;
-        // the env's state into the shadow slot: the owner row as 16-byte vectors (n_max is a multiple of 8 elements, rows are 16-byte aligned)
-        {
-            const int N = src.regions[src.env_region[e]].N;
-            const int4* s4 = reinterpret_cast<const int4*>(src.owner + (int64_t)e * src.n_max);
-            int4* d4 = reinterpret_cast<int4*>(sh_owner);
-            const int nvec = (N + 7) >> 3;
-            for (int i = tid; i < nvec; i += blockDim.x) d4[i] = s4[i];
-            for (int w = tid; w < words; w += blockDim.x) sh.legal[(int64_t)s * words + w] = src.legal[(int64_t)e * words + w];
-            if (tid == 0) {
-                sh.env_region[s] = src.env_region[e]; sh.env_replay[s] = src.env_replay[e];
-                sh.nlegal[s] = src.nlegal[e];
-                sh.cum[3 * s] = src.cum[3 * e]; sh.cum[3 * s + 1] = src.cum[3 * e + 1]; sh.cum[3 * s + 2] = src.cum[3 * e + 2];
-                sh.hash[s] = src.hash[e];
-                sh.env_steps[s] = src.env_steps[e];
-            }
-        }
+        xr_shadow_load(src, e, sh, s, sh_owner, words, tid);          // the env's state into the shadow slot
         __syncthreads();
         xr_route_dispatch<LDS_DIST, ZCH>(sh, s, net, smem);
         __syncthreads();              // (the router's epilogue runs on one thread of its choice: its stores are visible to thread 0 from here)

@@ -39,25 +39,8 @@ __global__ void __launch_bounds__(1024, 4) xr_rollout_kernel(XrBatchDev src, XrB
         const int row = task / n_rollouts, r = task - row * n_rollouts;
         const int e = env_lo + row;
         int32_t* const ord = order_out ? order_out + (int64_t)task * k_cap : nullptr;
-        // the env's state into the shadow slot, as xr_lookahead_kernel copies it: the owner row as 16-byte vectors (n_max is a multiple of
-        // 8 elements, rows are 16-byte aligned); the task's order row starts as "nothing routed"
-        {
-            const int N = src.regions[src.env_region[e]].N;
-            const int4* s4 = reinterpret_cast<const int4*>(src.owner + (int64_t)e * src.n_max);
-            int4* d4 = reinterpret_cast<int4*>(sh_owner);
-            const int nvec = (N + 7) >> 3;
-            for (int i = tid; i < nvec; i += blockDim.x) d4[i] = s4[i];
-            for (int w = tid; w < words; w += blockDim.x) sh.legal[(int64_t)s * words + w] = src.legal[(int64_t)e * words + w];
-            if (ord)
-                for (int k = tid; k < k_cap; k += blockDim.x) ord[k] = 0;
-            if (tid == 0) {
-                sh.env_region[s] = src.env_region[e]; sh.env_replay[s] = src.env_replay[e];
-                sh.nlegal[s] = src.nlegal[e];
-                sh.cum[3 * s] = src.cum[3 * e]; sh.cum[3 * s + 1] = src.cum[3 * e + 1]; sh.cum[3 * s + 2] = src.cum[3 * e + 2];
-                sh.hash[s] = src.hash[e];
-                sh.env_steps[s] = src.env_steps[e];
-            }
-        }
+        // the env's state into the shadow slot, as xr_lookahead_kernel copies it; the task's order row starts as "nothing routed"
+        xr_shadow_load(src, e, sh, s, sh_owner, words, tid, ord, k_cap);
         __syncthreads();
         // thread 0's view of the rollout.  pk: next entry of the prefix; -1: the prefix is over, the policy picks; -2: the rollout is over
         // (a pick of the policy that the router rejected — it cannot happen while legal and nlegal agree, and must not spin if they do not)
