@@ -602,6 +602,57 @@ int32_t xr_batch_tree_search(xr_batch* b, int32_t group, int32_t n_waves, int32_
                              int32_t* best_order_out_dev, double* best_return_out_dev,
                              int32_t* paths_out_dev, double* returns_out_dev, void* stream);
 
+/* ---- weighted net sampling: actions, rollouts and tree simulations that follow per-net weights ---- */
+/* One more built-in policy beside the uniform pick of xr_batch_random_actions: a legal net drawn with probability proportional to a
+ * caller-supplied weight per net — the Categorical(action_probs) sample of the reference's PPO (baseline/PPO/PPO.py:124-146) and the
+ * learned policy under which its MCTS plays simulations (baseline/xroute/self_route.py:482-568), for any caller that has per-net scores
+ * (an actor head's logits, lookahead rewards, elite statistics of earlier rollouts), without leaving the device loop.  Weights are
+ * integers and fixed for the call, so a whole rollout is a Plackett-Luce sample of an ordering.  "XR-Pick v1" (build-defined, exact in
+ * integers, bit for bit reproducible on the host):
+ *   Inputs.   A row's legal set, its env_steps, the global env index e, a 64-bit seed, and a weight row int32 w[k_cap] with net n at index
+ *             n - 1.
+ *   Effective weight.  q(n) = 0 if w <= 0, else min(w, XR_WEIGHT_MAX); XR_WEIGHT_MAX = 1 << 24, so the sum over any 64 nets fits 31 bits
+ *             and only the total needs 64.  Entries of nets that are not legal, or lie beyond the region's nets, are never read into the
+ *             result.
+ *   Hash.     r = splitmix64(seed ^ splitmix64(e * 0x100000001B3 + env_steps)) (mod 2^64): the same bits xr_batch_random_actions uses.
+ *   Pick.     L = the number of legal nets, S = the sum of q(n) over them.  L == 0: the pick is 0.  S == 0: the uniform pick, legal net
+ *             number r % L in ascending order.  Otherwise t = r % S, and the pick is the lowest legal net whose running sum of q over
+ *             the legal nets in ascending order exceeds t.  Everything is integer: any summation order gives the same answer.
+ *   Consequences.  All effective weights 1 gives exactly the net xr_batch_random_actions returns.  A net with q = 0 is picked only when
+ *             every legal net has q = 0.
+ * Weights are device data and are never validated on the host: the clamp is the validation.
+ * xr_batch_weighted_actions     actions_dev[i] = the XR-Pick of row i from weights_dev[i][0 .. k_cap), k_cap >= k_max.  group -1: the whole
+ *                               batch; >= 0: that env group, rows start at the group's first slot.  It only enqueues on `stream`.  Keyed
+ *                               by the global env index: sharding- and group-invariant like xr_batch_random_actions.  XR_ERR_INVALID null
+ *                               b / weights_dev / actions_dev, a group outside -1 .. n_groups - 1; XR_ERR_STATE before
+ *                               xr_batch_load_regions, or where the kernel is not linked; XR_ERR_RANGE k_cap < k_max.
+ * xr_batch_rollout_weighted     xr_batch_rollout with one more policy.  policy XR_ROLLOUT_STOP / XR_ROLLOUT_RANDOM: exactly what
+ *                               xr_batch_rollout does (weights_dev is not looked at).  XR_ROLLOUT_WEIGHTED: after the prefix, at every
+ *                               ply the net xr_batch_weighted_actions(seed_r) would choose for THIS env from the shadow state, from the
+ *                               weights of the env's row: weights_dev int32 [rows][weights_k_cap], shared by the row's rollouts.  seed_r,
+ *                               prefix, max_plies, outputs, done envs, pools, claim counters and the no-trace / concurrency contract are
+ *                               the rollout's.  Errors as xr_batch_rollout, and XR_ERR_INVALID null weights_dev with XR_ROLLOUT_WEIGHTED,
+ *                               XR_ERR_RANGE weights_k_cap < k_max with it.  xr_batch_rollout itself keeps refusing policy 2.
+ * xr_batch_tree_search_weighted XR-Tree v1 unchanged, except that Evaluate runs XR_ROLLOUT_WEIGHTED with sim_weights_dev (int32
+ *                               [rows][k_cap], the k_cap of the call).  NULL sim_weights_dev: xr_batch_tree_search exactly.  Errors as
+ *                               xr_batch_tree_search.
+ * Cuts: the weights are fixed for the call (no per-ply update), one weight row per env (no per-rollout weights), no network in the loop. */
+#define XR_ROLLOUT_WEIGHTED 2   /* after the prefix: XR-Pick v1 under the row's weights (xr_batch_rollout_weighted only) */
+#define XR_WEIGHT_MAX (1 << 24)
+int32_t xr_batch_weighted_actions(xr_batch* b, int32_t group, const int32_t* weights_dev, int32_t k_cap, int32_t* actions_dev, uint64_t seed,
+                                  void* stream);
+int32_t xr_batch_rollout_weighted(xr_batch* b, int32_t group, int32_t n_rollouts, int32_t policy, uint64_t seed,
+                                  const int32_t* prefix_dev, int32_t prefix_stride, int32_t max_plies,
+                                  int32_t* out_dev, double* return_out_dev, uint64_t* hash_out_dev,
+                                  int32_t* order_out_dev, int32_t k_cap,
+                                  const int32_t* weights_dev, int32_t weights_k_cap, void* stream);
+int32_t xr_batch_tree_search_weighted(xr_batch* b, int32_t group, int32_t n_waves, int32_t n_par, uint64_t seed,
+                                      const float* prior_dev, int32_t node_cap, double c_init, double c_base,
+                                      int32_t* visits_out_dev, double* value_out_dev, int32_t k_cap, int32_t* info_out_dev,
+                                      int32_t* best_order_out_dev, double* best_return_out_dev,
+                                      int32_t* paths_out_dev, double* returns_out_dev,
+                                      const int32_t* sim_weights_dev, void* stream);
+
 /* ---- XR-Maze v2: global-route guides (optional) ---------------------------------------------- */
 /* The reference's simulator runs with `-follow_guide 1` (ispd/ispd18_test1/run-net-ordering-training.tcl:3) on the guide file
  * it ships (ispd/ispd18_test1/ispd18_test1.input.guide: per net, rectangles per metal layer).  With xr_config.guide_cost > 0 a

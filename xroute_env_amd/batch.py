@@ -318,16 +318,51 @@ class RegionBatch:
                                                  self._stream_arg(stream)))
         return out, reward_out
 
+    # ---- weighted net sampling: a legal net in proportion to per-net integer weights (xr_batch_weighted_actions, XR-Pick v1) ----
+    def weighted_actions(self, weights: torch.Tensor, seed: int, out: Optional[torch.Tensor] = None, group: Optional[int] = None,
+                         stream=None) -> torch.Tensor:
+        """random_actions() under per-net weights: action i is drawn from the legal nets of row i with probability proportional to
+        weights[i, net - 1] (int32 [rows, k_max]; <= 0 counts as 0, values are clamped to XR_WEIGHT_MAX = 2^24; when every legal net
+        counts 0 the pick is the uniform one).  Exact in integers and keyed by (seed, global env index, env_steps) like random_actions:
+        unit weights give random_actions(seed) bit for bit.  0 for a done env.  group: an env group (rows = its slots, enqueued on
+        `stream`, default the current stream); None: the whole batch."""
+        if group is None:
+            g, rows = -1, self.n_envs
+        else:
+            lo, hi = self.group_bounds(group)
+            g, rows = int(group), hi - lo
+        wp = self._check_weights(weights, rows)
+        if out is None:
+            with torch.cuda.stream(stream if stream is not None else torch.cuda.current_stream(self.device)):
+                out = torch.empty(rows, dtype=torch.int32, device=self.device)
+        if not isinstance(out, torch.Tensor) or out.device != self.device or out.dtype != torch.int32 or not out.is_contiguous() \
+                or tuple(out.shape) != (rows,):
+            raise ValueError(f"out must be a contiguous int32 [{rows}] tensor on the batch device")
+        with torch.cuda.device(self.device):
+            _lib.check(self.L.xr_batch_weighted_actions(self._h, g, wp, max(int(self.k_max), 1), C.c_void_p(out.data_ptr()),
+                                                        C.c_uint64(int(seed) & (2 ** 64 - 1)), self._stream_arg(stream)))
+        return out
+
     # ---- rollouts: every env's episode played to its end, without stepping (xr_batch_rollout) -----------------------------------
-    _ROLLOUT_POLICY = {"stop": _lib.XR_ROLLOUT_STOP, "random": _lib.XR_ROLLOUT_RANDOM}
+    _ROLLOUT_POLICY = {"stop": _lib.XR_ROLLOUT_STOP, "random": _lib.XR_ROLLOUT_RANDOM, "weighted": _lib.XR_ROLLOUT_WEIGHTED}
+
+    def _check_weights(self, weights, rows: int, name: str = "weights") -> C.c_void_p:
+        """A weight table of XR-Pick v1: contiguous int32 [rows, k_max] on the batch device (net n at column n - 1)."""
+        k = max(int(self.k_max), 1)
+        if not isinstance(weights, torch.Tensor) or weights.device != self.device or weights.dtype != torch.int32 or not weights.is_contiguous() \
+                or tuple(weights.shape) != (rows, k):
+            raise ValueError(f"{name} must be a contiguous int32 [{rows}, {k}] tensor on the batch device")
+        return C.c_void_p(weights.data_ptr())
 
     def rollout(self, n_rollouts: int, seed: int = 0, policy="random", prefix: Optional[torch.Tensor] = None, max_plies: int = 0,
                 group: Optional[int] = None, stream=None, out: Optional[torch.Tensor] = None, return_out: Optional[torch.Tensor] = None,
-                hash_out: Optional[torch.Tensor] = None, order_out: Optional[torch.Tensor] = None):
+                hash_out: Optional[torch.Tensor] = None, order_out: Optional[torch.Tensor] = None, weights: Optional[torch.Tensor] = None):
         """From the state every env is in now, play the rest of its episode n_rollouts times; the batch is left exactly as it was.
         Rollout r routes its prefix (int32 [rows, n_rollouts, stride] of 1-based net ids, <= 0 ends a list; entries that are not legal
         are skipped and flagged BAD_ACTION), then continues under `policy`: "stop" (the prefix only) or "random" (what random_actions(
-        _lib.rollout_seed(seed, r)) would pick at every ply, until no net is left or max_plies real routes were made).  Returns a dict
+        _lib.rollout_seed(seed, r)) would pick at every ply, until no net is left or max_plies real routes were made) or "weighted"
+        (the same with weighted_actions(weights, ...): `weights` int32 [rows, k_max], one row per env shared by its rollouts; XR-Pick v1
+        of include/xroute_hip.h, so unit weights are the random policy bit for bit).  Returns a dict
         of device tensors: `out` int32 [rows, R, 8] = {d_violation, d_wirelength, d_via, status OR, plies, nlegal_end, path_len_sum, 0},
         `ret` float64 [rows, R] (the sum of the per-step rewards), `hash` int64 [rows, R] (the env's hash chain continued) and `order`
         int32 [rows, R, k_max] (the nets routed, 0 past `plies`).  A done env holds the empty rollout.  group: an env group (rows = its
@@ -343,8 +378,12 @@ class RegionBatch:
         if rows * R >= 2 ** 31:
             raise ValueError("rows x n_rollouts does not fit 31 bits")
         pol = self._ROLLOUT_POLICY.get(policy, policy) if isinstance(policy, str) else policy
-        if isinstance(pol, bool) or pol not in (_lib.XR_ROLLOUT_STOP, _lib.XR_ROLLOUT_RANDOM):
-            raise ValueError(f"policy must be 'stop' or 'random' (XR_ROLLOUT_STOP / XR_ROLLOUT_RANDOM), got {policy!r}")
+        if isinstance(pol, bool) or pol not in (_lib.XR_ROLLOUT_STOP, _lib.XR_ROLLOUT_RANDOM, _lib.XR_ROLLOUT_WEIGHTED):
+            raise ValueError(f"policy must be 'stop', 'random' or 'weighted' (XR_ROLLOUT_STOP / _RANDOM / _WEIGHTED), got {policy!r}")
+        if (pol == _lib.XR_ROLLOUT_WEIGHTED) != (weights is not None):
+            raise ValueError(f"policy 'weighted' takes `weights`, and no other policy does: got policy {policy!r} "
+                             f"{'with' if weights is not None else 'without'} weights")
+        wp = self._check_weights(weights, rows) if weights is not None else None
         if int(max_plies) < 0:
             raise ValueError(f"max_plies must be >= 0, got {max_plies}")
         k = max(int(self.k_max), 1)
@@ -364,8 +403,13 @@ class RegionBatch:
             pp, stride = C.c_void_p(prefix.data_ptr()), int(prefix.shape[2])
         ptr = {n: C.c_void_p(t.data_ptr()) for n, (t, _, _) in bufs.items()}
         with torch.cuda.device(self.device):
-            _lib.check(self.L.xr_batch_rollout(self._h, g, R, int(pol), C.c_uint64(int(seed) & (2 ** 64 - 1)), pp, stride, int(max_plies),
-                                               ptr["out"], ptr["return_out"], ptr["hash_out"], ptr["order_out"], k, self._stream_arg(stream)))
+            if wp is not None:
+                _lib.check(self.L.xr_batch_rollout_weighted(self._h, g, R, int(pol), C.c_uint64(int(seed) & (2 ** 64 - 1)), pp, stride, int(max_plies),
+                                                            ptr["out"], ptr["return_out"], ptr["hash_out"], ptr["order_out"], k, wp, k,
+                                                            self._stream_arg(stream)))
+            else:
+                _lib.check(self.L.xr_batch_rollout(self._h, g, R, int(pol), C.c_uint64(int(seed) & (2 ** 64 - 1)), pp, stride, int(max_plies),
+                                                   ptr["out"], ptr["return_out"], ptr["hash_out"], ptr["order_out"], k, self._stream_arg(stream)))
         return {"out": bufs["out"][0], "ret": bufs["return_out"][0], "hash": bufs["hash_out"][0], "order": bufs["order_out"][0]}
 
     # ---- branch: env slots take other slots' state, on the device (xr_batch_branch) ----------------------------------------------
@@ -389,7 +433,8 @@ class RegionBatch:
 
     # ---- tree search: MCTS over net orderings, the tree on the device (xr_batch_tree_search) ------------------------------------------
     def tree_search(self, n_waves: int, n_par: int, seed: int = 0, prior: Optional[torch.Tensor] = None, node_cap: Optional[int] = None,
-                    c_init: float = 1.25, c_base: float = 19652.0, group: Optional[int] = None, stream=None, trace: bool = False):
+                    c_init: float = 1.25, c_base: float = 19652.0, group: Optional[int] = None, stream=None, trace: bool = False,
+                    sim_weights: Optional[torch.Tensor] = None):
         """XR-Tree v1 (include/xroute_hip.h) from the state every env is in now: n_waves waves of n_par simulations per row, each a pUCT
         descent of the row's tree, a random rollout below the selected node and a backup — one enqueue-only call; the batch is left
         exactly as it was.  prior: None (uniform) or float32 [rows, k_max] weights per net (not finite or < 0 counts as 0; softmax is the
@@ -398,7 +443,9 @@ class RegionBatch:
         where N == 0), `info` int32 [rows, 4] = {simulations, nodes_used, max_depth, flags (XR_TREE_POOL_FULL)}, `best_order` int32
         [rows, k_max] and `best_return` float64 [rows] (the best line any simulation saw); with trace=True also `paths` int32 [rows,
         n_waves * n_par, k_max] and `returns` float64 [rows, n_waves * n_par], every simulation in (wave, lane) order.  A done env holds
-        the empty result.  group: an env group (rows = its slots, enqueued on `stream`); None: the whole batch."""
+        the empty result.  group: an env group (rows = its slots, enqueued on `stream`); None: the whole batch.  sim_weights: None, or
+        int32 [rows, k_max]: the simulations below a selected node follow rollout(policy="weighted", weights=sim_weights) instead of the
+        random policy (xr_batch_tree_search_weighted)."""
         if group is None:
             g, rows = -1, self.n_envs
         else:
@@ -426,6 +473,7 @@ class RegionBatch:
                     or tuple(prior.shape) != (rows, k):
                 raise ValueError(f"prior must be a contiguous float32 [{rows}, {k}] tensor on the batch device")
             pp = C.c_void_p(prior.data_ptr())
+        wp = self._check_weights(sim_weights, rows, "sim_weights") if sim_weights is not None else None
         shapes = {"visits": (torch.int32, (rows, k)), "value": (torch.float64, (rows, k)), "info": (torch.int32, (rows, 4)),
                   "best_order": (torch.int32, (rows, k)), "best_return": (torch.float64, (rows,))}
         if trace:
@@ -434,9 +482,14 @@ class RegionBatch:
             res = {n: torch.empty(shp, dtype=dt, device=self.device) for n, (dt, shp) in shapes.items()}
         ptr = {n: C.c_void_p(t.data_ptr()) for n, t in res.items()}
         with torch.cuda.device(self.device):
-            _lib.check(self.L.xr_batch_tree_search(self._h, g, W, P, C.c_uint64(int(seed) & (2 ** 64 - 1)), pp, cap, ci, cb, ptr["visits"],
-                                                   ptr["value"], k, ptr["info"], ptr["best_order"], ptr["best_return"], ptr.get("paths"),
-                                                   ptr.get("returns"), self._stream_arg(stream)))
+            if wp is not None:
+                _lib.check(self.L.xr_batch_tree_search_weighted(self._h, g, W, P, C.c_uint64(int(seed) & (2 ** 64 - 1)), pp, cap, ci, cb, ptr["visits"],
+                                                                ptr["value"], k, ptr["info"], ptr["best_order"], ptr["best_return"],
+                                                                ptr.get("paths"), ptr.get("returns"), wp, self._stream_arg(stream)))
+            else:
+                _lib.check(self.L.xr_batch_tree_search(self._h, g, W, P, C.c_uint64(int(seed) & (2 ** 64 - 1)), pp, cap, ci, cb, ptr["visits"],
+                                                       ptr["value"], k, ptr["info"], ptr["best_order"], ptr["best_return"], ptr.get("paths"),
+                                                       ptr.get("returns"), self._stream_arg(stream)))
         return res
 
     def alloc_head(self) -> torch.Tensor:

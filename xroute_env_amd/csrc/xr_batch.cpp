@@ -1787,6 +1787,21 @@ int32_t xr_batch_random_actions_group(xr_batch* b, int32_t group, int32_t* actio
     return XR_OK;
 }
 
+// group -1: the whole batch; else an env group, whose rows start at its first slot.  The kernel indexes the caller's rows from env_base
+int32_t xr_batch_weighted_actions(xr_batch* b, int32_t group, const int32_t* weights_dev, int32_t k_cap, int32_t* actions_dev, uint64_t seed, void* stream) {
+    if (!b || !weights_dev || !actions_dev) return fail(XR_ERR_INVALID, "xr_batch_weighted_actions: null argument");
+    if (!b->loaded) return fail(XR_ERR_STATE, "xr_batch_weighted_actions: load regions first");
+    if (group < -1 || group >= b->n_groups)
+        return fail(XR_ERR_INVALID, "xr_batch_weighted_actions: group %d outside -1..%d", group, b->n_groups - 1);
+    if (k_cap < b->k_max) return fail(XR_ERR_RANGE, "xr_batch_weighted_actions: k_cap %d < k_max %d", k_cap, b->k_max);
+    if (!xr_launch_weighted_actions) return fail(XR_ERR_STATE, "xr_batch_weighted_actions: weighted sampling kernels not linked");
+    XR_HIP(hipSetDevice(b->cfg.device));
+    XrBatchDev d = b->dev;
+    if (group >= 0) group_view(b, group, d);
+    XR_HIP(xr_launch_weighted_actions(&d, weights_dev, k_cap, actions_dev, seed, static_cast<hipStream_t>(stream)));
+    return XR_OK;
+}
+
 int32_t xr_batch_fetch_group(xr_batch* b, int32_t group, int32_t what, void* dst_dev, size_t dst_bytes, void* stream) {
     if (!b || !dst_dev) return fail(XR_ERR_INVALID, "xr_batch_fetch_group: null argument");
     if (const int32_t rc = group_check(b, group, "xr_batch_fetch_group")) return rc;
@@ -1923,34 +1938,60 @@ int32_t xr_batch_lookahead(xr_batch* b, int32_t group, const uint64_t* cand_mask
 }
 
 // ---- rollouts ----------------------------------------------------------------------------------------------------------------------
-int32_t xr_batch_rollout(xr_batch* b, int32_t group, int32_t n_rollouts, int32_t policy, uint64_t seed, const int32_t* prefix_dev, int32_t prefix_stride,
-                         int32_t max_plies, int32_t* out_dev, double* return_out_dev, uint64_t* hash_out_dev, int32_t* order_out_dev, int32_t k_cap,
-                         void* stream) {
-    if (!b || !out_dev) return fail(XR_ERR_INVALID, "xr_batch_rollout: null argument");
-    if (!b->loaded) return fail(XR_ERR_STATE, "xr_batch_rollout: load regions first");
+namespace {
+// xr_batch_rollout (weighted = false: policy 2 is unknown, the weights are not looked at) and xr_batch_rollout_weighted; every refusal
+// names the entry point (fn)
+int32_t rollout_impl(const char* fn, bool weighted, xr_batch* b, int32_t group, int32_t n_rollouts, int32_t policy, uint64_t seed, const int32_t* prefix_dev,
+                     int32_t prefix_stride, int32_t max_plies, int32_t* out_dev, double* return_out_dev, uint64_t* hash_out_dev, int32_t* order_out_dev,
+                     int32_t k_cap, const int32_t* weights_dev, int32_t weights_k_cap, void* stream) {
+    if (!b || !out_dev) return fail(XR_ERR_INVALID, "%s: null argument", fn);
+    if (!b->loaded) return fail(XR_ERR_STATE, "%s: load regions first", fn);
     int lo, rows;
-    if (const int32_t rc = group_rows(b, group, "xr_batch_rollout", lo, rows)) return rc;
-    if (policy != XR_ROLLOUT_STOP && policy != XR_ROLLOUT_RANDOM) return fail(XR_ERR_INVALID, "xr_batch_rollout: unknown policy %d", policy);
-    if (prefix_dev && prefix_stride < 1) return fail(XR_ERR_INVALID, "xr_batch_rollout: prefix_stride %d < 1 with a prefix", prefix_stride);
-    if (max_plies < 0) return fail(XR_ERR_INVALID, "xr_batch_rollout: max_plies %d is negative", max_plies);
+    if (const int32_t rc = group_rows(b, group, fn, lo, rows)) return rc;
+    const bool by_weights = weighted && policy == XR_ROLLOUT_WEIGHTED;
+    if (policy != XR_ROLLOUT_STOP && policy != XR_ROLLOUT_RANDOM && !by_weights) return fail(XR_ERR_INVALID, "%s: unknown policy %d", fn, policy);
+    if (by_weights && !weights_dev) return fail(XR_ERR_INVALID, "%s: null weights_dev with XR_ROLLOUT_WEIGHTED", fn);
+    if (prefix_dev && prefix_stride < 1) return fail(XR_ERR_INVALID, "%s: prefix_stride %d < 1 with a prefix", fn, prefix_stride);
+    if (max_plies < 0) return fail(XR_ERR_INVALID, "%s: max_plies %d is negative", fn, max_plies);
     if (n_rollouts < 1 || n_rollouts > XR_ROLLOUT_MAX)
-        return fail(XR_ERR_RANGE, "xr_batch_rollout: n_rollouts %d outside 1..%d", n_rollouts, XR_ROLLOUT_MAX);
-    if (order_out_dev && k_cap < b->k_max) return fail(XR_ERR_RANGE, "xr_batch_rollout: k_cap %d < k_max %d", k_cap, b->k_max);
-    if (const int32_t rc = lds_field_check(b, "xr_batch_rollout")) return rc;
+        return fail(XR_ERR_RANGE, "%s: n_rollouts %d outside 1..%d", fn, n_rollouts, XR_ROLLOUT_MAX);
+    if (order_out_dev && k_cap < b->k_max) return fail(XR_ERR_RANGE, "%s: k_cap %d < k_max %d", fn, k_cap, b->k_max);
+    if (by_weights && weights_k_cap < b->k_max) return fail(XR_ERR_RANGE, "%s: weights_k_cap %d < k_max %d", fn, weights_k_cap, b->k_max);
+    if (const int32_t rc = lds_field_check(b, fn)) return rc;
     const int64_t tasks = (int64_t)rows * n_rollouts;
-    if (tasks >= ((int64_t)1 << 31)) return fail(XR_ERR_RANGE, "xr_batch_rollout: rows x n_rollouts does not fit 31 bits");
-    if (!xr_lookahead_occupancy || !xr_launch_rollout) return fail(XR_ERR_STATE, "xr_batch_rollout: rollout kernels not linked");
+    if (tasks >= ((int64_t)1 << 31)) return fail(XR_ERR_RANGE, "%s: rows x n_rollouts does not fit 31 bits", fn);
+    if (!xr_lookahead_occupancy || !xr_launch_rollout || (by_weights && !xr_launch_rollout_weighted)) return fail(XR_ERR_STATE, "%s: rollout kernels not linked", fn);
     XR_HIP(hipSetDevice(b->cfg.device));
     hipStream_t st = static_cast<hipStream_t>(stream);
     const XrRouteVariant v = route_variant(b);
     xr_batch::LookPool& lp = b->look[group + 1];
-    if (const int32_t rc = shadow_pool(b, lp, v, st, "xr_batch_rollout", true)) return rc;
+    if (const int32_t rc = shadow_pool(b, lp, v, st, fn, true)) return rc;
     const XrBatchDev sh = shadow_view(b, lp);
     const Banks ctr = flip_banks(lp.roll_ctr.p, lp.roll_bank, 1);
     const int blocks = (int)std::min<int64_t>(b->look_grid, tasks);
+    if (by_weights) {
+        XR_HIP(xr_launch_rollout_weighted(&b->dev, &sh, lo, (int)tasks, n_rollouts, seed, prefix_dev, prefix_dev ? prefix_stride : 0, max_plies, ctr.cur, ctr.next,
+                                          out_dev, return_out_dev, hash_out_dev, order_out_dev, order_out_dev ? k_cap : 0, weights_dev, weights_k_cap, v, blocks, st));
+        return XR_OK;
+    }
     XR_HIP(xr_launch_rollout(&b->dev, &sh, lo, (int)tasks, n_rollouts, policy, seed, prefix_dev, prefix_dev ? prefix_stride : 0, max_plies, ctr.cur, ctr.next,
                              out_dev, return_out_dev, hash_out_dev, order_out_dev, order_out_dev ? k_cap : 0, v, blocks, st));
     return XR_OK;
+}
+}  // namespace
+
+int32_t xr_batch_rollout(xr_batch* b, int32_t group, int32_t n_rollouts, int32_t policy, uint64_t seed, const int32_t* prefix_dev, int32_t prefix_stride,
+                         int32_t max_plies, int32_t* out_dev, double* return_out_dev, uint64_t* hash_out_dev, int32_t* order_out_dev, int32_t k_cap,
+                         void* stream) {
+    return rollout_impl("xr_batch_rollout", false, b, group, n_rollouts, policy, seed, prefix_dev, prefix_stride, max_plies, out_dev, return_out_dev, hash_out_dev,
+                        order_out_dev, k_cap, nullptr, 0, stream);
+}
+
+int32_t xr_batch_rollout_weighted(xr_batch* b, int32_t group, int32_t n_rollouts, int32_t policy, uint64_t seed, const int32_t* prefix_dev,
+                                  int32_t prefix_stride, int32_t max_plies, int32_t* out_dev, double* return_out_dev, uint64_t* hash_out_dev,
+                                  int32_t* order_out_dev, int32_t k_cap, const int32_t* weights_dev, int32_t weights_k_cap, void* stream) {
+    return rollout_impl("xr_batch_rollout_weighted", true, b, group, n_rollouts, policy, seed, prefix_dev, prefix_stride, max_plies, out_dev, return_out_dev,
+                        hash_out_dev, order_out_dev, k_cap, weights_dev, weights_k_cap, stream);
 }
 
 // ---- tree search -------------------------------------------------------------------------------------------------------------------
@@ -1973,32 +2014,37 @@ int32_t xr_tree_exploration_table(double c_init, double c_base, int32_t n, doubl
     return XR_OK;
 }
 
-int32_t xr_batch_tree_search(xr_batch* b, int32_t group, int32_t n_waves, int32_t n_par, uint64_t seed, const float* prior_dev, int32_t node_cap,
-                             double c_init, double c_base, int32_t* visits_out_dev, double* value_out_dev, int32_t k_cap, int32_t* info_out_dev,
-                             int32_t* best_order_out_dev, double* best_return_out_dev, int32_t* paths_out_dev, double* returns_out_dev, void* stream) {
-    if (!b || !visits_out_dev || !value_out_dev || !info_out_dev) return fail(XR_ERR_INVALID, "xr_batch_tree_search: null argument");
-    if (!b->loaded) return fail(XR_ERR_STATE, "xr_batch_tree_search: load regions first");
+namespace {
+// xr_batch_tree_search (sim_weights_dev null) and xr_batch_tree_search_weighted: Evaluate runs XR_ROLLOUT_RANDOM, or XR_ROLLOUT_WEIGHTED
+// with the row's sim weights ([rows][k_cap]); every refusal names the entry point (fn)
+int32_t tree_search_impl(const char* fn, xr_batch* b, int32_t group, int32_t n_waves, int32_t n_par, uint64_t seed, const float* prior_dev, int32_t node_cap,
+                         double c_init, double c_base, int32_t* visits_out_dev, double* value_out_dev, int32_t k_cap, int32_t* info_out_dev,
+                         int32_t* best_order_out_dev, double* best_return_out_dev, int32_t* paths_out_dev, double* returns_out_dev,
+                         const int32_t* sim_weights_dev, void* stream) {
+    if (!b || !visits_out_dev || !value_out_dev || !info_out_dev) return fail(XR_ERR_INVALID, "%s: null argument", fn);
+    if (!b->loaded) return fail(XR_ERR_STATE, "%s: load regions first", fn);
     int lo, rows;
-    if (const int32_t rc = group_rows(b, group, "xr_batch_tree_search", lo, rows)) return rc;
-    if (n_waves < 1) return fail(XR_ERR_INVALID, "xr_batch_tree_search: n_waves %d < 1", n_waves);
-    if (n_par < 1) return fail(XR_ERR_INVALID, "xr_batch_tree_search: n_par %d < 1", n_par);
-    if (!std::isfinite(c_init)) return fail(XR_ERR_INVALID, "xr_batch_tree_search: c_init is not finite");
-    if (!tree_knobs_ok(c_init, c_base)) return fail(XR_ERR_INVALID, "xr_batch_tree_search: c_base must be finite and > 0");
-    if (n_par > XR_ROLLOUT_MAX) return fail(XR_ERR_RANGE, "xr_batch_tree_search: n_par %d above %d", n_par, XR_ROLLOUT_MAX);
+    if (const int32_t rc = group_rows(b, group, fn, lo, rows)) return rc;
+    if (n_waves < 1) return fail(XR_ERR_INVALID, "%s: n_waves %d < 1", fn, n_waves);
+    if (n_par < 1) return fail(XR_ERR_INVALID, "%s: n_par %d < 1", fn, n_par);
+    if (!std::isfinite(c_init)) return fail(XR_ERR_INVALID, "%s: c_init is not finite", fn);
+    if (!tree_knobs_ok(c_init, c_base)) return fail(XR_ERR_INVALID, "%s: c_base must be finite and > 0", fn);
+    if (n_par > XR_ROLLOUT_MAX) return fail(XR_ERR_RANGE, "%s: n_par %d above %d", fn, n_par, XR_ROLLOUT_MAX);
     if ((int64_t)n_waves * n_par > XR_TREE_MAX_SIMS)
-        return fail(XR_ERR_RANGE, "xr_batch_tree_search: n_waves x n_par = %lld simulations above %d", (long long)n_waves * n_par, XR_TREE_MAX_SIMS);
-    if (node_cap < 1) return fail(XR_ERR_RANGE, "xr_batch_tree_search: node_cap %d < 1", node_cap);
-    if (k_cap < b->k_max) return fail(XR_ERR_RANGE, "xr_batch_tree_search: k_cap %d < k_max %d", k_cap, b->k_max);
-    if (const int32_t rc = lds_field_check(b, "xr_batch_tree_search")) return rc;
+        return fail(XR_ERR_RANGE, "%s: n_waves x n_par = %lld simulations above %d", fn, (long long)n_waves * n_par, XR_TREE_MAX_SIMS);
+    if (node_cap < 1) return fail(XR_ERR_RANGE, "%s: node_cap %d < 1", fn, node_cap);
+    if (k_cap < b->k_max) return fail(XR_ERR_RANGE, "%s: k_cap %d < k_max %d", fn, k_cap, b->k_max);
+    if (const int32_t rc = lds_field_check(b, fn)) return rc;
     const int64_t tasks = (int64_t)rows * n_par;
-    if (tasks >= ((int64_t)1 << 31)) return fail(XR_ERR_RANGE, "xr_batch_tree_search: rows x n_par does not fit 31 bits");
-    if (!xr_lookahead_occupancy || !xr_launch_rollout || !xr_launch_tree_reset || !xr_launch_tree_select || !xr_launch_tree_backup)
-        return fail(XR_ERR_STATE, "xr_batch_tree_search: tree search kernels not linked");
+    if (tasks >= ((int64_t)1 << 31)) return fail(XR_ERR_RANGE, "%s: rows x n_par does not fit 31 bits", fn);
+    if (!xr_lookahead_occupancy || !xr_launch_rollout || !xr_launch_tree_reset || !xr_launch_tree_select || !xr_launch_tree_backup ||
+        (sim_weights_dev && !xr_launch_rollout_weighted))
+        return fail(XR_ERR_STATE, "%s: tree search kernels not linked", fn);
     if (k_cap < 1) k_cap = 1;
     const int n_sims = n_waves * n_par;
     // the private memory: six arrays in one allocation, each starting on a 16-byte boundary
     if ((double)rows * ((double)node_cap * sizeof(XrTreeNode) + (double)n_par * (8.0 * k_cap + 40.0) + 64.0) > 1e15)
-        return fail(XR_ERR_NOMEM, "xr_batch_tree_search: %d rows x %d nodes do not fit any device", rows, node_cap);
+        return fail(XR_ERR_NOMEM, "%s: %d rows x %d nodes do not fit any device", fn, rows, node_cap);
     Carver c;
     const size_t R = (size_t)rows, P = (size_t)n_par, K = (size_t)k_cap;
     const size_t o_nodes = c.take(R * (size_t)node_cap * sizeof(XrTreeNode)), o_rs = c.take(R * sizeof(XrTreeRow));
@@ -2008,23 +2054,23 @@ int32_t xr_batch_tree_search(xr_batch* b, int32_t group, int32_t n_waves, int32_
     hipStream_t st = static_cast<hipStream_t>(stream);
     const XrRouteVariant v = route_variant(b);
     xr_batch::LookPool& lp = b->look[group + 1];
-    if (const int32_t rc = shadow_pool(b, lp, v, st, "xr_batch_tree_search", true)) return rc;
+    if (const int32_t rc = shadow_pool(b, lp, v, st, fn, true)) return rc;
     const XrBatchDev sh = shadow_view(b, lp);
     xr_batch::TreePool& tp = b->tree[group + 1];
     if (tp.mem.n < c.off && tp.mem.alloc(c.off) != hipSuccess) {
         tp.mem.release();
-        return fail(XR_ERR_NOMEM, "xr_batch_tree_search: hipMalloc of %zu bytes of trees failed", c.off);
+        return fail(XR_ERR_NOMEM, "%s: hipMalloc of %zu bytes of trees failed", fn, c.off);
     }
     xr_batch::TreeTable* tab = nullptr;
     for (auto& t : tp.tables)
         if (t->c_init == c_init && t->c_base == c_base && t->host.size() >= (size_t)n_sims + 1) tab = t.get();
     if (!tab) {
         std::unique_ptr<xr_batch::TreeTable> t(new (std::nothrow) xr_batch::TreeTable);
-        if (!t) return fail(XR_ERR_NOMEM, "xr_batch_tree_search: no host memory for the exploration table");
+        if (!t) return fail(XR_ERR_NOMEM, "%s: no host memory for the exploration table", fn);
         t->c_init = c_init; t->c_base = c_base;
         t->host.resize((size_t)n_sims + 1);
         tree_table_fill(c_init, c_base, 0, n_sims, t->host.data());
-        if (t->dev.alloc(t->host.size()) != hipSuccess) return fail(XR_ERR_NOMEM, "xr_batch_tree_search: hipMalloc of the exploration table failed");
+        if (t->dev.alloc(t->host.size()) != hipSuccess) return fail(XR_ERR_NOMEM, "%s: hipMalloc of the exploration table failed", fn);
         XR_HIP(hipMemcpyAsync(t->dev.p, t->host.data(), t->host.size() * sizeof(double), hipMemcpyHostToDevice, st));
         tab = t.get();          // (a shorter table of the same knobs stays: a launch in flight may read it)
         tp.tables.push_back(std::move(t));
@@ -2044,11 +2090,32 @@ int32_t xr_batch_tree_search(xr_batch* b, int32_t group, int32_t n_waves, int32_
     for (int w = 0; w < n_waves; w++) {
         XR_HIP(xr_launch_tree_select(&b->dev, &t, rows, w, st));
         const Banks ctr = flip_banks(lp.roll_ctr.p, lp.roll_bank, 1);
-        XR_HIP(xr_launch_rollout(&b->dev, &sh, lo, (int)tasks, n_par, XR_ROLLOUT_RANDOM, seed + (uint64_t)w * 0xD1B54A32D192ED03ULL, t.prefix, k_cap, 0, ctr.cur,
-                                 ctr.next, rec, t.ret, nullptr, t.order, k_cap, v, blocks, st));
+        const uint64_t seed_w = seed + (uint64_t)w * 0xD1B54A32D192ED03ULL;
+        if (sim_weights_dev)
+            XR_HIP(xr_launch_rollout_weighted(&b->dev, &sh, lo, (int)tasks, n_par, seed_w, t.prefix, k_cap, 0, ctr.cur, ctr.next, rec, t.ret, nullptr, t.order,
+                                              k_cap, sim_weights_dev, k_cap, v, blocks, st));
+        else
+            XR_HIP(xr_launch_rollout(&b->dev, &sh, lo, (int)tasks, n_par, XR_ROLLOUT_RANDOM, seed_w, t.prefix, k_cap, 0, ctr.cur, ctr.next, rec, t.ret, nullptr,
+                                     t.order, k_cap, v, blocks, st));
         XR_HIP(xr_launch_tree_backup(&b->dev, &t, rows, w, w == n_waves - 1 ? 1 : 0, st));
     }
     return XR_OK;
+}
+}  // namespace
+
+int32_t xr_batch_tree_search(xr_batch* b, int32_t group, int32_t n_waves, int32_t n_par, uint64_t seed, const float* prior_dev, int32_t node_cap,
+                             double c_init, double c_base, int32_t* visits_out_dev, double* value_out_dev, int32_t k_cap, int32_t* info_out_dev,
+                             int32_t* best_order_out_dev, double* best_return_out_dev, int32_t* paths_out_dev, double* returns_out_dev, void* stream) {
+    return tree_search_impl("xr_batch_tree_search", b, group, n_waves, n_par, seed, prior_dev, node_cap, c_init, c_base, visits_out_dev, value_out_dev, k_cap,
+                            info_out_dev, best_order_out_dev, best_return_out_dev, paths_out_dev, returns_out_dev, nullptr, stream);
+}
+
+int32_t xr_batch_tree_search_weighted(xr_batch* b, int32_t group, int32_t n_waves, int32_t n_par, uint64_t seed, const float* prior_dev, int32_t node_cap,
+                                      double c_init, double c_base, int32_t* visits_out_dev, double* value_out_dev, int32_t k_cap, int32_t* info_out_dev,
+                                      int32_t* best_order_out_dev, double* best_return_out_dev, int32_t* paths_out_dev, double* returns_out_dev,
+                                      const int32_t* sim_weights_dev, void* stream) {
+    return tree_search_impl("xr_batch_tree_search_weighted", b, group, n_waves, n_par, seed, prior_dev, node_cap, c_init, c_base, visits_out_dev, value_out_dev,
+                            k_cap, info_out_dev, best_order_out_dev, best_return_out_dev, paths_out_dev, returns_out_dev, sim_weights_dev, stream);
 }
 
 // ---- branch ------------------------------------------------------------------------------------------------------------------------

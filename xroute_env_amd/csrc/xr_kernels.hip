@@ -16,6 +16,8 @@
 //   xr_branch_kernel<0 / 1>      (xr_branch.h) env slots take other slots' state: parents of overwritten parents to staging, then every moved slot
 //   xr_tree_reset / select / backup_kernel   (xr_tree.h) pUCT over net orderings with the tree in device memory, one wavefront per row
 //   xr_random_action_kernel
+//   xr_weighted_action_kernel    (xr_weighted.h) XR-Pick v1: a legal net drawn in proportion to caller-supplied integer weights, one wave per env
+//   xr_rollout_weighted_kernel   (xr_weighted.h) the rollout whose policy is that pick
 //
 // Integer / index work throughout: no MFMA.  What matters here is coalescing (every sweep is
 // unit-stride in the reference's own flat order f=(x*Y+y)*Z+z), LDS residency of the distance
@@ -2197,6 +2199,7 @@ __global__ void __launch_bounds__(256) xr_expand_state_kernel(XrBatchDev b, cons
 
 #include "xr_lookahead.h"
 #include "xr_rollout.h"
+#include "xr_weighted.h"
 #include "xr_tree.h"
 #include "xr_branch.h"
 
@@ -2330,6 +2333,32 @@ hipError_t xr_launch_rollout(const XrBatchDev* src, const XrBatchDev* shadow, in
                            prefix_stride, max_plies, ctr, next_ctr, out, return_out, hash_out, order_out, k_cap);
     });
     return hipGetLastError();
+}
+
+// weighted net sampling (xr_weighted.h): one wave per env, four per workgroup; rows of `weights` / `actions` start at env_base
+hipError_t xr_launch_weighted_actions(const XrBatchDev* b, const int32_t* weights, int k_cap, int32_t* actions, uint64_t seed, hipStream_t st) {
+    const int n = XR_ENV_END(*b) - b->env_base;
+    hipLaunchKernelGGL(xr_weighted_action_kernel, dim3((n + 3) / 4), dim3(256), 0, st, *b, weights, k_cap, actions, seed);
+    return hipGetLastError();
+}
+
+// the rollout launch with the policy XR_ROLLOUT_WEIGHTED: xr_launch_rollout's shape.  A launch above 64 KB of dynamic LDS raises the
+// kernel's limit itself (xr_route_set_max_lds covers the kernels that were there before it)
+hipError_t xr_launch_rollout_weighted(const XrBatchDev* src, const XrBatchDev* shadow, int env_lo, int n_tasks, int n_rollouts, uint64_t seed,
+                                      const int32_t* prefix, int prefix_stride, int max_plies, uint32_t* ctr, uint32_t* next_ctr, int32_t* out,
+                                      double* return_out, uint64_t* hash_out, int32_t* order_out, int k_cap, const int32_t* weights, int weights_k_cap,
+                                      XrRouteVariant v, int blocks, hipStream_t st) {
+    const dim3 g(blocks), t(v.threads);
+    return xr_with_variant(v.lds_dist, v.zch, [&](auto L, auto Z) {
+        if (v.lds_bytes > 64 * 1024) {
+            const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&xr_rollout_weighted_kernel<L.value, Z.value>),
+                                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)v.lds_bytes);
+            if (e != hipSuccess) return e;
+        }
+        hipLaunchKernelGGL((xr_rollout_weighted_kernel<L.value, Z.value>), g, t, v.lds_bytes, st, *src, *shadow, env_lo, n_tasks, n_rollouts, seed, prefix,
+                           prefix_stride, max_plies, ctr, next_ctr, out, return_out, hash_out, order_out, k_cap, weights, weights_k_cap);
+        return hipGetLastError();
+    });
 }
 
 // branch (xr_branch.h): workgroup (i, c) = chunk c of row i; the stream orders the staging pass before the writing pass

@@ -6,6 +6,9 @@
 `beam`        beam search over net orderings: lookahead -> select -> branch -> step (`from xroute_env_amd.envs.beam import beam_search`)
 `tree`        tree search episodes: one device-side MCTS (RegionBatch.tree_search) per ply, the most visited net stepped
               (`from xroute_env_amd.envs.tree import tree_episodes`)
+`weighted`    weights for the weighted net sampling (XR-Pick v1: RegionBatch.weighted_actions, rollout(policy="weighted"),
+              tree_search(sim_weights=...)) and a cross-entropy search over orderings on top of it
+              (`from xroute_env_amd.envs.weighted import cem_search, lookahead_weights`)
 """
 from .facade import OrderingEvaluationEnv, OrderingTrainingEnv, StaticRegionEnv, XRouteEnv
 from .vector_env import XRouteVectorEnv

@@ -29,12 +29,14 @@ def lookahead_prior(batch: RegionBatch, temperature: float) -> torch.Tensor:
 
 def tree_episodes(regions: Sequence, n_waves: int, n_par: int, seed: int = 0, device="cuda:0", prior: Optional[Callable] = None,
                   node_cap: Optional[int] = None, c_init: float = 1.25, c_base: float = 19652.0, stats: Optional[dict] = None,
-                  **batch_kw) -> List[dict]:
+                  sim_weights: Optional[Callable] = None, **batch_kw) -> List[dict]:
     """Play every region's episode by tree search, all regions at once.  Returns per region {"order": the nets played, "ret": the
     episode's return (the step rewards summed in step order in double), "best_order": the best complete ordering any simulation of any
     ply saw, "best_ret": its return, "simulations": the simulations run}.  prior: None, or a callable (batch) -> float32 [n_envs,
     k_max] weights asked before every search (lookahead_prior is one).  The seed of ply p is seed + p.  batch_kw goes to RegionBatch
-    (router knobs, costs); auto_reset is off.  stats: an optional dict that receives "routed_nets", the nets the searches routed."""
+    (router knobs, costs); auto_reset is off.  stats: an optional dict that receives "routed_nets", the nets the searches routed.
+    sim_weights: None (random simulations), or a callable (batch) -> int32 [n_envs, k_max] weights asked before every search: the
+    simulations follow the weighted policy (envs.weighted.lookahead_weights is one)."""
     R = len(regions)
     if R < 1:
         raise ValueError("tree_episodes needs at least one region")
@@ -57,7 +59,8 @@ def tree_episodes(regions: Sequence, n_waves: int, n_par: int, seed: int = 0, de
                 break
             if ply >= K:
                 raise RuntimeError("tree_episodes: nets left after k_max plies")
-            res = b.tree_search(n_waves, n_par, seed + ply, prior(b) if prior is not None else None, node_cap, c_init, c_base)
+            res = b.tree_search(n_waves, n_par, seed + ply, prior(b) if prior is not None else None, node_cap, c_init, c_base,
+                                sim_weights=sim_weights(b) if sim_weights is not None else None)
             act = XRouteVectorEnv._most_visited(res)
             # the best line of this search, as a whole episode: what was played so far, then the line
             line = res["best_return"] + ret

@@ -119,6 +119,21 @@ class XRouteVectorEnv:
     def random_actions(self, seed: int, out: Optional[torch.Tensor] = None):
         return self.batch.random_actions(seed, out)
 
+    def weighted_actions(self, weights: torch.Tensor, seed: int, out: Optional[torch.Tensor] = None, group: Optional[int] = None):
+        """RegionBatch.weighted_actions: a legal net per env drawn in proportion to weights (int32 [rows, k_max]); unit weights are
+        random_actions(seed).  group None: the whole batch, after every group's outstanding work.  A group: on that group's stream,
+        ordered like lookahead(group); the group's event then covers it."""
+        if group is None:
+            self._join_groups()
+            return self.batch.weighted_actions(weights, seed, out)
+        (g,) = self._groups_of(group)
+        s = self.group_streams[g]
+        s.wait_stream(torch.cuda.current_stream(self.device))
+        with torch.cuda.stream(s):
+            res = self.batch.weighted_actions(weights, seed, out, group=g, stream=s)
+            self.group_events[g].record(s)
+        return res
+
     # ---- lookahead: every candidate net priced from the current state, the env untouched ------------------------------------------
     def lookahead(self, group: Optional[int] = None):
         """(delta_status int32 [rows, k_max, 4], reward float64 [rows, k_max]) of RegionBatch.lookahead: what step() would publish for
@@ -160,17 +175,18 @@ class XRouteVectorEnv:
 
     # ---- rollouts: every env's episode played to its end from the current state, the env untouched ---------------------------------
     def rollout(self, n_rollouts: int, seed: int = 0, policy="random", prefix: Optional[torch.Tensor] = None, max_plies: int = 0,
-                group: Optional[int] = None):
+                group: Optional[int] = None, weights: Optional[torch.Tensor] = None):
         """RegionBatch.rollout's dict {out, ret, hash, order}.  group None: the whole batch, after every group's outstanding work.  A
-        group: on that group's stream, ordered like lookahead(group); the group's event then covers it."""
+        group: on that group's stream, ordered like lookahead(group); the group's event then covers it.  weights: with
+        policy="weighted", int32 [rows, k_max]."""
         if group is None:
             self._join_groups()
-            return self.batch.rollout(n_rollouts, seed, policy, prefix, max_plies)
+            return self.batch.rollout(n_rollouts, seed, policy, prefix, max_plies, weights=weights)
         (g,) = self._groups_of(group)
         s = self.group_streams[g]
         s.wait_stream(torch.cuda.current_stream(self.device))
         with torch.cuda.stream(s):
-            res = self.batch.rollout(n_rollouts, seed, policy, prefix, max_plies, group=g, stream=s)
+            res = self.batch.rollout(n_rollouts, seed, policy, prefix, max_plies, group=g, stream=s, weights=weights)
             self.group_events[g].record(s)
         return res
 
@@ -228,18 +244,20 @@ class XRouteVectorEnv:
 
     # ---- tree search: MCTS over net orderings from the current state, the env untouched ------------------------------------------
     def tree_search(self, n_waves: int, n_par: int, seed: int = 0, prior: Optional[torch.Tensor] = None, node_cap: Optional[int] = None,
-                    c_init: float = 1.25, c_base: float = 19652.0, group: Optional[int] = None, trace: bool = False):
+                    c_init: float = 1.25, c_base: float = 19652.0, group: Optional[int] = None, trace: bool = False,
+                    sim_weights: Optional[torch.Tensor] = None):
         """RegionBatch.tree_search's dict {visits, value, info, best_order, best_return[, paths, returns]}.  group None: the whole batch,
         after every group's outstanding work.  A group: on that group's stream, ordered like rollout(group); the group's event then
-        covers it."""
+        covers it.  sim_weights: None, or int32 [rows, k_max]: the simulations follow the weighted policy."""
         if group is None:
             self._join_groups()
-            return self.batch.tree_search(n_waves, n_par, seed, prior, node_cap, c_init, c_base, trace=trace)
+            return self.batch.tree_search(n_waves, n_par, seed, prior, node_cap, c_init, c_base, trace=trace, sim_weights=sim_weights)
         (g,) = self._groups_of(group)
         s = self.group_streams[g]
         s.wait_stream(torch.cuda.current_stream(self.device))
         with torch.cuda.stream(s):
-            res = self.batch.tree_search(n_waves, n_par, seed, prior, node_cap, c_init, c_base, group=g, stream=s, trace=trace)
+            res = self.batch.tree_search(n_waves, n_par, seed, prior, node_cap, c_init, c_base, group=g, stream=s, trace=trace,
+                                         sim_weights=sim_weights)
             self.group_events[g].record(s)
         return res
 
