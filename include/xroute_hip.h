@@ -653,6 +653,56 @@ int32_t xr_batch_tree_search_weighted(xr_batch* b, int32_t group, int32_t n_wave
                                       int32_t* paths_out_dev, double* returns_out_dev,
                                       const int32_t* sim_weights_dev, void* stream);
 
+/* ---- kept trees: a search that continues from the played net's subtree ---- */
+/* The standard MCTS saving (the reference's play loop keeps none: baseline/xroute/self_route.py:341-371 builds a new root at every
+ * move): after the env has really played net a, the root's child of a and everything below it is a valid tree for the new state.
+ * xr_batch_tree_search_keep is xr_batch_tree_search_weighted in every argument it shares with it (sim_weights_dev NULL: the random
+ * simulations; the errors, the no-trace contract, the enqueue-only contract and the refusal of the HBM-scratch forms and
+ * stream_per_region are the same, every refusal names xr_batch_tree_search_keep), except for what follows.  "XR-Tree v1, kept":
+ *   Own memory. Every caller (the whole batch, or one env group) has a kept-tree pool of its own, apart from the pool of the plain
+ *            searches: xr_batch_tree_search and xr_batch_tree_search_weighted never disturb a kept tree, and a kept call never disturbs
+ *            them.  The pool holds two halves of rows x node_cap nodes (a call re-roots from the half the last call searched in into the
+ *            other one), the row states, a key per row, and the wave arrays of the plain search:
+ *            rows x (80 node_cap + 40 + 24 + 8 legal_words) bytes for the trees, each of its five arrays rounded up to 16, allocated
+ *            when the shape below changes, and rows x n_par x (8 k_cap + 40) bytes of wave arrays that only grow, plus
+ *            8 x (XR_TREE_MAX_SIMS + 1) bytes per distinct (c_init, c_base) for the table.
+ *   Key.     The key of a row is written at the end of the call's first kernel: the env's env_steps, region, replay and legal words as
+ *            they are at that moment, and a valid bit.
+ *   played_dev.  NULL: every row is rebuilt (a fresh search that leaves a kept tree behind).  Otherwise int32 [rows]:
+ *            played[row] == 0: the env has not moved since the kept tree's call.  The row is kept whole if the key is valid and equals
+ *            the env's current env_steps, region, replay and legal words exactly, and the kept root's N plus n_waves * n_par does not
+ *            exceed XR_TREE_MAX_SIMS.
+ *            played[row] == a > 0: the env has since made exactly one real route, of net a.  The row is re-rooted if all of these
+ *            hold: the key is valid; region and replay are equal; env_steps == key.env_steps + 1; bit a is set in the key's legal words;
+ *            the env's legal words equal the key's with bit a cleared; the kept root is expanded and has a child of net a; that child's
+ *            N plus n_waves * n_par does not exceed XR_TREE_MAX_SIMS.
+ *            Otherwise, and for any negative entry, the row is rebuilt exactly as the plain search builds it.  A rebuild is never an
+ *            error.  The host rebuilds all rows when rows, the group's first slot, node_cap, k_cap or legal_words differ from the
+ *            pool's last call; n_par, n_waves, the knobs and the seed may differ.
+ *   Re-rooting (normative, node numbering included).  New node 0 is the old child of a, with net = 0 and P = 1.0.  The new nodes are
+ *            then taken in index order, and the children block of every expanded one is appended in its old (ascending net) order: a
+ *            breadth-first compaction.  nodes_used is the count; it always fits.  Let r be the slot's reward row (the reward of the step
+ *            that played a).  Every copied node gets W' = W - (double)N * r: one multiplication, then one subtraction, each rounded on
+ *            its own; N, P, net and count are kept, V is 0.  The row state gets min' = min - r and max' = max - r (infinities stay).
+ *            With played == 0 nothing is shifted or renumbered.  In both cases best restarts at -inf, max_depth at 0, and the flags
+ *            become XR_TREE_KEPT alone.  A new root that is unexpanded is expanded at the start with this call's prior, as the plain
+ *            search does.  A row whose env has no legal net (the played net was the last) is a done row: the empty result, kept {0, 0}.
+ *            Kept nodes keep the P they were given: prior_dev of this call serves new expansions only.
+ *   Table.   A kept root meets visit counts above n_waves * n_par: kept calls index E[n] for n = 0 .. XR_TREE_MAX_SIMS, computed once
+ *            per (c_init, c_base) by the same formula.
+ *   Outputs. info = {simulations of this call, nodes_used, max_depth of this call, flags}; visits_out and value_out show the root's
+ *            children with the carried visits included, in the current frame.  kept_out_dev: NULL, or int32 [rows][2] = {N of the new
+ *            root before this call's simulations, nodes carried}; {0, 0} for a rebuilt row.
+ * Cuts: the best line does not carry (best_order and best_return are this call's simulations' alone); one real route per call at
+ * most (a row whose env made two is rebuilt); a tree does not follow a branch to another slot. */
+#define XR_TREE_KEPT 2
+int32_t xr_batch_tree_search_keep(xr_batch* b, int32_t group, const int32_t* played_dev,
+                                  int32_t n_waves, int32_t n_par, uint64_t seed, const float* prior_dev, int32_t node_cap,
+                                  double c_init, double c_base, int32_t* visits_out_dev, double* value_out_dev, int32_t k_cap,
+                                  int32_t* info_out_dev, int32_t* best_order_out_dev, double* best_return_out_dev,
+                                  int32_t* paths_out_dev, double* returns_out_dev, const int32_t* sim_weights_dev,
+                                  int32_t* kept_out_dev, void* stream);
+
 /* ---- XR-Maze v2: global-route guides (optional) ---------------------------------------------- */
 /* The reference's simulator runs with `-follow_guide 1` (ispd/ispd18_test1/run-net-ordering-training.tcl:3) on the guide file
  * it ships (ispd/ispd18_test1/ispd18_test1.input.guide: per net, rectangles per metal layer).  With xr_config.guide_cost > 0 a

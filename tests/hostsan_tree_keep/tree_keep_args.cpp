@@ -1,0 +1,242 @@
+// tests/hostsan_tree_keep/tree_keep_args.cpp — TEST INFRASTRUCTURE (see ../hostsan/hip/hip_runtime.h).
+//
+// Drives xr_batch_tree_search_keep of the product's host side (csrc/xr_batch.cpp, built with ASan + UBSan against the host-memory HIP
+// stand-in) through every refusal include/xroute_hip.h documents — on batches with and without env groups, of the HBM-scratch forms and
+// with stream_per_region, with fixed and with randomised arguments, with and without played_dev, kept_out_dev and sim_weights_dev — and
+// checks the code AND the message of each.  The stand-in links no tree launcher, so a valid call must answer XR_ERR_STATE ("not linked")
+// after validating, without allocating or launching, and without taking a kept-tree pool: the stand-in's live-allocation and launch
+// counters must not move on any call of this program, in any order of callers and shapes, and the plain search's refusals between the kept
+// calls stay what they are.  Runs as a program of its own (no preload); ends with TREE_KEEP_ARGS_OK, no leak and nothing on stderr.
+#include <hip/hip_runtime.h>
+
+#include <cmath>
+#include <cstdio>
+#include <cstring>
+#include <limits>
+#include <string>
+#include <vector>
+
+#include "../../include/xroute_hip.h"
+
+extern "C" int64_t xr_stub_launches;
+
+namespace {
+
+struct Lcg {
+    uint64_t s;
+    uint32_t next() { s = s * 6364136223846793005ULL + 1442695040888963407ULL; return (uint32_t)(s >> 33); }
+    int below(int n) { return (int)(next() % (uint32_t)n); }
+    int between(int lo, int hi) { return lo + below(hi - lo + 1); }
+};
+
+int g_failures = 0, g_calls = 0;
+
+void check(bool ok, const std::string& what) {
+    if (ok) return;
+    printf("FAILURE: %s\n", what.c_str());
+    g_failures++;
+}
+
+// a small region: X x Y x 2 nodes, K nets of two access points each
+struct Reg {
+    int X, Y, Z = 2, K;
+    std::vector<int32_t> xs, ys;
+    std::vector<uint8_t> dir{0, 1};
+    std::vector<uint32_t> nodes;
+    Reg(int X_, int Y_, int K_) : X(X_), Y(Y_), K(K_) {
+        for (int i = 0; i < X; i++) xs.push_back(1000 + 400 * i);
+        for (int i = 0; i < Y; i++) ys.push_back(-500 + 380 * i);
+        nodes.assign((size_t)X * Y * Z, XR_TYPE_NORMAL);
+        for (int n = 1; n <= K; n++)
+            for (int p = 1; p <= 2; p++) nodes[(size_t)((n * 7 + p * 3) % (X * Y)) * Z + (p - 1)] = XR_TYPE_ACCESS | ((uint32_t)n << 3) | ((uint32_t)p << 17);
+    }
+    xr_region_desc desc() const {
+        xr_region_desc d{};
+        d.dim_x = X; d.dim_y = Y; d.dim_z = Z;
+        d.xs_host = xs.data(); d.ys_host = ys.data(); d.layer_dir_host = dir.data(); d.nodes_host = nodes.data();
+        d.n_nets = K;
+        return d;
+    }
+};
+
+const double kNan = std::numeric_limits<double>::quiet_NaN(), kInf = std::numeric_limits<double>::infinity();
+
+struct Args {
+    int32_t group = -1, n_waves = 2, n_par = 2, node_cap = 64, k_cap = 64;
+    double c_init = 1.25, c_base = 19652.0;
+    bool prior = false, visits = true, value = true, info = true, best = true, trace = false, played = false, kept = false, weights = false;
+};
+
+struct Expect { int32_t code; const char* msg; };
+
+// what include/xroute_hip.h documents, in the order the entry point checks
+Expect expected(const Args& a, bool loaded, int n_groups, int rows, int k_max, bool scratch_form) {
+    if (!a.visits || !a.value || !a.info) return {XR_ERR_INVALID, "null argument"};
+    if (!loaded) return {XR_ERR_STATE, "load regions first"};
+    if (a.group < -1 || a.group >= n_groups) return {XR_ERR_INVALID, "group"};
+    if (a.n_waves < 1) return {XR_ERR_INVALID, "n_waves"};
+    if (a.n_par < 1) return {XR_ERR_INVALID, "n_par"};
+    if (!std::isfinite(a.c_init)) return {XR_ERR_INVALID, "c_init"};
+    if (!(std::isfinite(a.c_base) && a.c_base > 0.0)) return {XR_ERR_INVALID, "c_base"};
+    if (a.n_par > XR_ROLLOUT_MAX) return {XR_ERR_RANGE, "n_par"};
+    if ((int64_t)a.n_waves * a.n_par > XR_TREE_MAX_SIMS) return {XR_ERR_RANGE, "simulations"};
+    if (a.node_cap < 1) return {XR_ERR_RANGE, "node_cap"};
+    if (a.k_cap < k_max) return {XR_ERR_RANGE, "k_cap"};
+    if (scratch_form) return {XR_ERR_RANGE, "HBM scratch"};
+    if ((int64_t)rows * a.n_par >= ((int64_t)1 << 31)) return {XR_ERR_RANGE, "31 bits"};
+    return {XR_ERR_STATE, "not linked"};
+}
+
+// stand-ins for the device buffers: never touched (nothing launches), but real memory
+std::vector<int32_t> g_visits(64), g_info(64), g_order(64), g_paths(64), g_played(64), g_kept(64), g_weights(64);
+std::vector<double> g_value(64), g_best(8), g_returns(8);
+std::vector<float> g_prior(64);
+
+void call(xr_batch* b, const Args& a, const Expect& want, const std::string& what) {
+    const int64_t live = xr_stub_alloc_live, launches = xr_stub_launches;
+    const int32_t rc = xr_batch_tree_search_keep(b, a.group, a.played ? g_played.data() : nullptr, a.n_waves, a.n_par, 0x1234567ULL * (uint64_t)(g_calls + 1),
+                                                 a.prior ? g_prior.data() : nullptr, a.node_cap, a.c_init, a.c_base, a.visits ? g_visits.data() : nullptr,
+                                                 a.value ? g_value.data() : nullptr, a.k_cap, a.info ? g_info.data() : nullptr,
+                                                 a.best ? g_order.data() : nullptr, a.best ? g_best.data() : nullptr, a.trace ? g_paths.data() : nullptr,
+                                                 a.trace ? g_returns.data() : nullptr, a.weights ? g_weights.data() : nullptr,
+                                                 a.kept ? g_kept.data() : nullptr, nullptr);
+    g_calls++;
+    const char* msg = xr_last_error();
+    char buf[512];
+    snprintf(buf, sizeof buf, "%s: group %d played %d waves %d par %d cap %d k_cap %d c %g/%g -> rc %d \"%s\", expected %d \"...%s...\"", what.c_str(), a.group,
+             (int)a.played, a.n_waves, a.n_par, a.node_cap, a.k_cap, a.c_init, a.c_base, rc, msg, want.code, want.msg);
+    check(rc == want.code && strstr(msg, "xr_batch_tree_search_keep") && strstr(msg, want.msg), buf);
+    check(xr_stub_alloc_live == live && xr_stub_launches == launches, std::string("allocated or launched: ") + buf);
+}
+
+struct Batch {
+    xr_batch* h = nullptr;
+    int n_envs = 0, n_groups = 1, k_max = 0;
+    bool scratch_form = false;
+    std::vector<int32_t> bounds;
+    int rows(int g) const { return g < 0 ? n_envs : bounds[g + 1] - bounds[g]; }
+};
+
+Batch make(const char* name, int n_envs, const std::vector<const Reg*>& regs, int force_scratch, int per_region, const std::vector<int32_t>& bounds) {
+    Batch B;
+    xr_config c;
+    xr_config_default(&c);
+    c.n_envs = n_envs; c.force_scratch_field = force_scratch; c.stream_per_region = per_region;
+    check(xr_batch_create(&c, &B.h) == XR_OK, std::string(name) + ": create");
+    Args a;
+    call(B.h, a, expected(a, false, 1, n_envs, 0, false), std::string(name) + " before the load");
+    std::vector<xr_region_desc> d;
+    for (const Reg* r : regs) d.push_back(r->desc());
+    const int32_t rc = xr_batch_load_regions(B.h, d.data(), (int32_t)d.size(), nullptr);
+    check(rc == XR_OK, std::string(name) + ": load: " + xr_last_error());
+    int32_t s[6] = {0, 0, 0, 0, 0, 0};
+    int64_t stride = 0;
+    check(xr_batch_sizes(B.h, &s[0], &s[1], &s[2], &s[3], &s[4], &s[5], &stride) == XR_OK, "sizes");
+    B.n_envs = n_envs; B.k_max = s[3]; B.scratch_form = force_scratch || per_region;
+    B.bounds = {0, n_envs};
+    if (!bounds.empty()) {
+        check(xr_batch_set_groups(B.h, bounds.data(), (int32_t)bounds.size() - 1) == XR_OK, std::string(name) + ": set_groups: " + xr_last_error());
+        B.bounds = bounds; B.n_groups = (int)bounds.size() - 1;
+    }
+    return B;
+}
+
+// every refusal once, by name, then randomised arguments
+void drive(const char* name, Batch& B, Lcg& rng, int random_calls) {
+    auto run = [&](Args a, const char* what) { call(B.h, a, expected(a, true, B.n_groups, B.rows(a.group < -1 || a.group >= B.n_groups ? -1 : a.group), B.k_max, B.scratch_form),
+                                                     std::string(name) + " " + what); };
+    Args a;
+    run(a, "valid, defaults");
+    a = Args{}; a.visits = false; run(a, "null visits_out_dev");
+    a = Args{}; a.value = false; run(a, "null value_out_dev");
+    a = Args{}; a.info = false; run(a, "null info_out_dev");
+    a = Args{}; a.group = -2; run(a, "group -2");
+    a = Args{}; a.group = B.n_groups; run(a, "group n_groups");
+    a = Args{}; a.group = B.n_groups - 1; run(a, "last group");
+    a = Args{}; a.n_waves = 0; run(a, "n_waves 0");
+    a = Args{}; a.n_par = 0; run(a, "n_par 0");
+    a = Args{}; a.n_par = -3; run(a, "n_par -3");
+    a = Args{}; a.c_init = kNan; run(a, "c_init NaN");
+    a = Args{}; a.c_init = kInf; run(a, "c_init inf");
+    a = Args{}; a.c_init = -2.0; run(a, "c_init negative is a number");
+    a = Args{}; a.c_base = 0.0; run(a, "c_base 0");
+    a = Args{}; a.c_base = -1.0; run(a, "c_base -1");
+    a = Args{}; a.c_base = kNan; run(a, "c_base NaN");
+    a = Args{}; a.n_par = XR_ROLLOUT_MAX + 1; run(a, "n_par above the limit");
+    a = Args{}; a.n_par = XR_ROLLOUT_MAX; a.n_waves = 16; run(a, "65536 simulations");
+    a = Args{}; a.n_par = XR_ROLLOUT_MAX; a.n_waves = 17; run(a, "above 65536 simulations");
+    a = Args{}; a.n_par = 1; a.n_waves = XR_TREE_MAX_SIMS + 1; run(a, "65537 waves of one");
+    a = Args{}; a.node_cap = 0; run(a, "node_cap 0");
+    a = Args{}; a.node_cap = 1; run(a, "node_cap 1");
+    a = Args{}; a.k_cap = B.k_max - 1; run(a, "k_cap below k_max");
+    a = Args{}; a.k_cap = B.k_max; run(a, "k_cap = k_max");
+    a = Args{}; a.best = false; a.trace = true; a.prior = true; run(a, "optional outputs the other way round");
+    a = Args{}; a.played = true; run(a, "played_dev given");
+    a = Args{}; a.played = true; a.kept = true; a.weights = true; run(a, "played_dev, kept_out_dev and sim_weights_dev given");
+    a = Args{}; a.played = true; a.node_cap = 65; run(a, "another shape with played_dev");
+    a = Args{}; a.played = true; a.info = false; run(a, "null info_out_dev with played_dev");
+    a = Args{}; a.played = true; a.n_par = XR_ROLLOUT_MAX; a.n_waves = 17; run(a, "above 65536 simulations with played_dev");
+    {              // the plain search between the kept calls keeps its own name and its own refusals
+        const int64_t live = xr_stub_alloc_live, launches = xr_stub_launches;
+        const int32_t rc = xr_batch_tree_search(B.h, -1, 2, 2, 1, nullptr, 64, 1.25, 19652.0, g_visits.data(), g_value.data(), 64, g_info.data(), nullptr, nullptr,
+                                                nullptr, nullptr, nullptr);
+        const bool named = strstr(xr_last_error(), "xr_batch_tree_search:") != nullptr;
+        check(rc == (B.scratch_form ? XR_ERR_RANGE : XR_ERR_STATE) && named, std::string(name) + " the plain search between kept calls: " + xr_last_error());
+        check(xr_stub_alloc_live == live && xr_stub_launches == launches, std::string(name) + " the plain search allocated or launched");
+    }
+    for (int i = 0; i < random_calls; i++) {
+        Args r;
+        r.group = rng.between(-3, B.n_groups + 1);
+        r.n_waves = rng.below(4) ? rng.between(1, 9) : rng.between(-2, 0);
+        r.n_par = rng.below(4) ? rng.between(1, 9) : (rng.below(2) ? rng.between(-3, 0) : rng.between(XR_ROLLOUT_MAX - 1, XR_ROLLOUT_MAX + 2));
+        if (!rng.below(8)) r.n_waves = rng.between(15, 18);
+        r.node_cap = rng.below(4) ? rng.between(1, 500) : rng.between(-2, 0);
+        r.k_cap = rng.between(B.k_max - 2, B.k_max + 2);
+        const double ci[] = {1.25, 0.0, -1.0, kNan, kInf, -kInf}, cb[] = {19652.0, 1.0, 1e-9, 0.0, -5.0, kNan, kInf};
+        r.c_init = ci[rng.below(3) ? 0 : rng.below(6)];
+        r.c_base = cb[rng.below(3) ? 0 : rng.below(7)];
+        r.prior = rng.below(2); r.best = rng.below(2); r.trace = rng.below(2);
+        r.played = rng.below(2); r.kept = rng.below(2); r.weights = rng.below(2);
+        r.visits = rng.below(16) != 0; r.value = rng.below(16) != 0; r.info = rng.below(16) != 0;
+        run(r, "random");
+    }
+}
+
+}  // namespace
+
+int main() {
+    const Reg a(6, 6, 3), b(7, 5, 5);
+    Lcg rng{0x4EE9};
+    {
+        Args n;          // a null batch, with and without the rest
+        call(nullptr, n, {XR_ERR_INVALID, "null argument"}, "null batch");
+        n.info = false;
+        call(nullptr, n, {XR_ERR_INVALID, "null argument"}, "null batch and info_out_dev");
+    }
+    struct Case { const char* name; int n_envs, scratch, per_region; std::vector<int32_t> bounds; };
+    const Case cases[] = {{"whole batch", 6, 0, 0, {}}, {"three groups", 9, 0, 0, {0, 2, 5, 9}}, {"one group set", 4, 0, 0, {0, 4}},
+                          {"force_scratch_field", 6, 1, 0, {}}, {"force_scratch_field, groups", 6, 1, 0, {0, 3, 6}}, {"stream_per_region", 5, 0, 1, {}}};
+    for (const Case& c : cases) {
+        Batch B = make(c.name, c.n_envs, {&a, &b}, c.scratch, c.per_region, c.bounds);
+        drive(c.name, B, rng, 400);
+        xr_batch_destroy(B.h);
+        check(xr_stub_alloc_live == 0, std::string(c.name) + ": no device buffer outlives the batch");
+    }
+    {
+        // rows x n_par beyond 31 bits: 2^19 slots x 4096 lanes (one group of the two is small enough)
+        const Reg tiny(2, 2, 1);
+        const int n = 1 << 19;
+        Batch B = make("2^19 slots", n, {&tiny}, 0, 0, {0, n - 1, n});
+        Args r;
+        r.n_par = XR_ROLLOUT_MAX; r.n_waves = 1;
+        call(B.h, r, {XR_ERR_RANGE, "31 bits"}, "2^19 rows x 4096");
+        r.group = 0;
+        call(B.h, r, {XR_ERR_STATE, "not linked"}, "2^19 - 1 rows x 4096");
+        xr_batch_destroy(B.h);
+        check(xr_stub_alloc_live == 0, "2^19 slots: no device buffer outlives the batch");
+    }
+    check(xr_stub_launches > 0, "the loads launched their kernels through the stand-in (the counters are live)");
+    if (g_failures) printf("TREE_KEEP_ARGS_FAILED %d of %d calls\n", g_failures, g_calls);
+    else printf("TREE_KEEP_ARGS_OK %d calls\n", g_calls);
+    return g_failures ? 1 : 0;
+}

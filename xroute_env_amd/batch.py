@@ -434,7 +434,7 @@ class RegionBatch:
     # ---- tree search: MCTS over net orderings, the tree on the device (xr_batch_tree_search) ------------------------------------------
     def tree_search(self, n_waves: int, n_par: int, seed: int = 0, prior: Optional[torch.Tensor] = None, node_cap: Optional[int] = None,
                     c_init: float = 1.25, c_base: float = 19652.0, group: Optional[int] = None, stream=None, trace: bool = False,
-                    sim_weights: Optional[torch.Tensor] = None):
+                    sim_weights: Optional[torch.Tensor] = None, keep: bool = False, played: Optional[torch.Tensor] = None):
         """XR-Tree v1 (include/xroute_hip.h) from the state every env is in now: n_waves waves of n_par simulations per row, each a pUCT
         descent of the row's tree, a random rollout below the selected node and a backup — one enqueue-only call; the batch is left
         exactly as it was.  prior: None (uniform) or float32 [rows, k_max] weights per net (not finite or < 0 counts as 0; softmax is the
@@ -445,7 +445,15 @@ class RegionBatch:
         n_waves * n_par, k_max] and `returns` float64 [rows, n_waves * n_par], every simulation in (wave, lane) order.  A done env holds
         the empty result.  group: an env group (rows = its slots, enqueued on `stream`); None: the whole batch.  sim_weights: None, or
         int32 [rows, k_max]: the simulations below a selected node follow rollout(policy="weighted", weights=sim_weights) instead of the
-        random policy (xr_batch_tree_search_weighted)."""
+        random policy (xr_batch_tree_search_weighted).  keep=True: the search of "XR-Tree v1, kept" (xr_batch_tree_search_keep), on the
+        caller's kept-tree pool: it leaves its tree behind, and continues from the tree the caller's last kept call left where `played`
+        says how the env has moved since — None: every row starts over; int32 [rows]: 0 the env has not moved, a > 0 the env has made
+        exactly one step, of net a; a row whose key does not agree (and any negative entry) starts over.  The dict then also holds
+        `kept` int32 [rows, 2] = {visits of the new root carried in, nodes carried}, and `info`'s flags carry XR_TREE_KEPT.  node_cap
+        is part of the pool's shape (a call with another one starts every row over); its default is 1 + 4 * n_waves * n_par * k_max for
+        a kept call, room for what a tree carries along."""
+        if played is not None and not keep:
+            raise ValueError("played needs keep=True")
         if group is None:
             g, rows = -1, self.n_envs
         else:
@@ -464,7 +472,7 @@ class RegionBatch:
         if not (math.isfinite(cb) and cb > 0):
             raise ValueError(f"c_base must be finite and > 0, got {c_base}")
         k = max(int(self.k_max), 1)
-        cap = 1 + W * P * k if node_cap is None else int(node_cap)
+        cap = 1 + (4 if keep else 1) * W * P * k if node_cap is None else int(node_cap)
         if not 1 <= cap < 2 ** 31:
             raise ValueError(f"node_cap must be in 1..2^31 - 1, got {node_cap}")
         pp = None
@@ -474,15 +482,27 @@ class RegionBatch:
                 raise ValueError(f"prior must be a contiguous float32 [{rows}, {k}] tensor on the batch device")
             pp = C.c_void_p(prior.data_ptr())
         wp = self._check_weights(sim_weights, rows, "sim_weights") if sim_weights is not None else None
+        pl = None
+        if played is not None:
+            if not isinstance(played, torch.Tensor) or played.device != self.device or played.dtype != torch.int32 or not played.is_contiguous() \
+                    or tuple(played.shape) != (rows,):
+                raise ValueError(f"played must be a contiguous int32 [{rows}] tensor on the batch device")
+            pl = C.c_void_p(played.data_ptr())
         shapes = {"visits": (torch.int32, (rows, k)), "value": (torch.float64, (rows, k)), "info": (torch.int32, (rows, 4)),
                   "best_order": (torch.int32, (rows, k)), "best_return": (torch.float64, (rows,))}
         if trace:
             shapes.update(paths=(torch.int32, (rows, W * P, k)), returns=(torch.float64, (rows, W * P)))
+        if keep:
+            shapes.update(kept=(torch.int32, (rows, 2)))
         with torch.cuda.stream(stream if stream is not None else torch.cuda.current_stream(self.device)):
             res = {n: torch.empty(shp, dtype=dt, device=self.device) for n, (dt, shp) in shapes.items()}
         ptr = {n: C.c_void_p(t.data_ptr()) for n, t in res.items()}
         with torch.cuda.device(self.device):
-            if wp is not None:
+            if keep:
+                _lib.check(self.L.xr_batch_tree_search_keep(self._h, g, pl, W, P, C.c_uint64(int(seed) & (2 ** 64 - 1)), pp, cap, ci, cb, ptr["visits"],
+                                                            ptr["value"], k, ptr["info"], ptr["best_order"], ptr["best_return"], ptr.get("paths"),
+                                                            ptr.get("returns"), wp, ptr["kept"], self._stream_arg(stream)))
+            elif wp is not None:
                 _lib.check(self.L.xr_batch_tree_search_weighted(self._h, g, W, P, C.c_uint64(int(seed) & (2 ** 64 - 1)), pp, cap, ci, cb, ptr["visits"],
                                                                 ptr["value"], k, ptr["info"], ptr["best_order"], ptr["best_return"],
                                                                 ptr.get("paths"), ptr.get("returns"), wp, self._stream_arg(stream)))

@@ -191,7 +191,17 @@ struct xr_batch {
         std::vector<std::unique_ptr<TreeTable>> tables;
         void release() { mem.release(); tables.clear(); }
     } tree[1 + XR_MAX_GROUPS];
-    int look_grid = 0;                          // workgroups of the persistent lookahead launch the chip holds at once (0: not asked yet)
+    // kept trees (xr_batch_tree_search_keep): a pool of its own per caller, indexed like tree[].  `trees` holds what outlives a call — two
+    // halves of rows x node_cap nodes (a call re-roots from the half the last call searched in, `half`, into the other one), the row
+    // states, the keys and their legal words — and depends on the shape below alone; `scratch` holds one wave's arrays and only ever
+    // grows, so a call with more lanes keeps the trees.  A call whose shape differs from the last one's rebuilds every row
+    struct KeepPool {
+        DevBuf<uint8_t> trees, scratch;
+        std::vector<std::unique_ptr<TreeTable>> tables;          // E[0 .. XR_TREE_MAX_SIMS] per (c_init, c_base)
+        int rows = 0, lo = -1, node_cap = 0, k_cap = 0, legal_words = 0, half = 0;
+        void release() { trees.release(); scratch.release(); tables.clear(); rows = 0; lo = -1; node_cap = 0; k_cap = 0; legal_words = 0; half = 0; }
+    } keep[1 + XR_MAX_GROUPS];
+    int look_grid = 0;                         // workgroups of the persistent lookahead launch the chip holds at once (0: not asked yet)
     XrBatchDev dev{};
     ~xr_batch() {
         if (ev_fork) (void)hipEventDestroy(ev_fork);
@@ -1046,6 +1056,7 @@ int32_t xr_batch_load_regions(xr_batch* b, const xr_region_desc* regs, int32_t n
     for (xr_batch::LookPool& lp : b->look) lp.release();         // shadow slots are sized for the regions they were allocated under
     for (xr_batch::BranchPool& bp : b->branch) bp.release();     // and so are the staging rows of xr_batch_branch
     for (xr_batch::TreePool& tp : b->tree) tp.release();
+    for (xr_batch::KeepPool& kp : b->keep) kp.release();
     b->look_grid = 0;
     b->guide_csr.release(); b->guide_box.release(); b->guide_mask.release(); b->guide_mask_bytes = 0;        // guides belong to the regions they were loaded for
     memset(&b->dev, 0, sizeof(b->dev));
@@ -2016,8 +2027,9 @@ int32_t xr_tree_exploration_table(double c_init, double c_base, int32_t n, doubl
 
 namespace {
 // xr_batch_tree_search (sim_weights_dev null) and xr_batch_tree_search_weighted: Evaluate runs XR_ROLLOUT_RANDOM, or XR_ROLLOUT_WEIGHTED
-// with the row's sim weights ([rows][k_cap]); every refusal names the entry point (fn)
-int32_t tree_search_impl(const char* fn, xr_batch* b, int32_t group, int32_t n_waves, int32_t n_par, uint64_t seed, const float* prior_dev, int32_t node_cap,
+// with the row's sim weights ([rows][k_cap]); every refusal names the entry point (fn).  keep: xr_batch_tree_search_keep — the same
+// checks and the same waves, on the caller's kept-tree pool, after xr_tree_keep_begin_kernel in place of the reset
+int32_t tree_search_impl(const char* fn, bool keep, const int32_t* played_dev, int32_t* kept_out_dev, xr_batch* b, int32_t group, int32_t n_waves, int32_t n_par, uint64_t seed, const float* prior_dev, int32_t node_cap,
                          double c_init, double c_base, int32_t* visits_out_dev, double* value_out_dev, int32_t k_cap, int32_t* info_out_dev,
                          int32_t* best_order_out_dev, double* best_return_out_dev, int32_t* paths_out_dev, double* returns_out_dev,
                          const int32_t* sim_weights_dev, void* stream) {
@@ -2038,16 +2050,17 @@ int32_t tree_search_impl(const char* fn, xr_batch* b, int32_t group, int32_t n_w
     const int64_t tasks = (int64_t)rows * n_par;
     if (tasks >= ((int64_t)1 << 31)) return fail(XR_ERR_RANGE, "%s: rows x n_par does not fit 31 bits", fn);
     if (!xr_lookahead_occupancy || !xr_launch_rollout || !xr_launch_tree_reset || !xr_launch_tree_select || !xr_launch_tree_backup ||
-        (sim_weights_dev && !xr_launch_rollout_weighted))
+        (sim_weights_dev && !xr_launch_rollout_weighted) || (keep && !xr_launch_tree_keep_begin))
         return fail(XR_ERR_STATE, "%s: tree search kernels not linked", fn);
     if (k_cap < 1) k_cap = 1;
     const int n_sims = n_waves * n_par;
     // the private memory: six arrays in one allocation, each starting on a 16-byte boundary
-    if ((double)rows * ((double)node_cap * sizeof(XrTreeNode) + (double)n_par * (8.0 * k_cap + 40.0) + 64.0) > 1e15)
+    if ((double)rows * ((keep ? 2.0 : 1.0) * (double)node_cap * sizeof(XrTreeNode) + (keep ? 8.0 * b->legal_words + 24.0 : 0.0) + (double)n_par * (8.0 * k_cap + 40.0) + 64.0) > 1e15)
         return fail(XR_ERR_NOMEM, "%s: %d rows x %d nodes do not fit any device", fn, rows, node_cap);
     Carver c;
     const size_t R = (size_t)rows, P = (size_t)n_par, K = (size_t)k_cap;
-    const size_t o_nodes = c.take(R * (size_t)node_cap * sizeof(XrTreeNode)), o_rs = c.take(R * sizeof(XrTreeRow));
+    // (a kept call: the nodes, the row states and the keys live in the pool's other allocation, carved below)
+    const size_t o_nodes = keep ? 0 : c.take(R * (size_t)node_cap * sizeof(XrTreeNode)), o_rs = keep ? 0 : c.take(R * sizeof(XrTreeRow));
     const size_t o_prefix = c.take(R * P * K * sizeof(int32_t)), o_order = c.take(R * P * K * sizeof(int32_t));
     const size_t o_rec = c.take(R * P * 8 * sizeof(int32_t)), o_ret = c.take(R * P * sizeof(double));
     XR_HIP(hipSetDevice(b->cfg.device));
@@ -2057,36 +2070,70 @@ int32_t tree_search_impl(const char* fn, xr_batch* b, int32_t group, int32_t n_w
     if (const int32_t rc = shadow_pool(b, lp, v, st, fn, true)) return rc;
     const XrBatchDev sh = shadow_view(b, lp);
     xr_batch::TreePool& tp = b->tree[group + 1];
-    if (tp.mem.n < c.off && tp.mem.alloc(c.off) != hipSuccess) {
-        tp.mem.release();
+    xr_batch::KeepPool& kp = b->keep[group + 1];
+    DevBuf<uint8_t>& wave_mem = keep ? kp.scratch : tp.mem;
+    if (wave_mem.n < c.off && wave_mem.alloc(c.off) != hipSuccess) {
+        wave_mem.release();
         return fail(XR_ERR_NOMEM, "%s: hipMalloc of %zu bytes of trees failed", fn, c.off);
     }
+    Carver ck;          // the kept trees: two halves of nodes, the row states, the keys, their legal words
+    const size_t half_bytes = R * (size_t)node_cap * sizeof(XrTreeNode);
+    const size_t k_half0 = ck.take(half_bytes), k_half1 = ck.take(half_bytes), k_rs = ck.take(R * sizeof(XrTreeRow));
+    const size_t k_key = ck.take(R * sizeof(XrTreeKey)), k_legal = ck.take(R * (size_t)b->legal_words * sizeof(uint64_t));
+    bool rebuild_all = !played_dev;
+    if (keep) {
+        if (kp.rows != rows || kp.lo != lo || kp.node_cap != node_cap || kp.k_cap != k_cap || kp.legal_words != b->legal_words || kp.trees.n < ck.off) {
+            rebuild_all = true;          // another shape (or the first call): no row of the pool is a tree of this call's rows
+            if (kp.trees.n < ck.off && kp.trees.alloc(ck.off) != hipSuccess) {
+                kp.release();
+                return fail(XR_ERR_NOMEM, "%s: hipMalloc of %zu bytes of kept trees failed", fn, ck.off);
+            }
+        }
+        kp.rows = 0;          // (the pool holds this call's trees once its first kernel is enqueued, not before)
+    }
+    auto& tables = keep ? kp.tables : tp.tables;
+    const int e_max = keep ? XR_TREE_MAX_SIMS : n_sims;          // a kept root meets visit counts above this call's simulations
     xr_batch::TreeTable* tab = nullptr;
-    for (auto& t : tp.tables)
-        if (t->c_init == c_init && t->c_base == c_base && t->host.size() >= (size_t)n_sims + 1) tab = t.get();
+    for (auto& t : tables)
+        if (t->c_init == c_init && t->c_base == c_base && t->host.size() >= (size_t)e_max + 1) tab = t.get();
     if (!tab) {
         std::unique_ptr<xr_batch::TreeTable> t(new (std::nothrow) xr_batch::TreeTable);
         if (!t) return fail(XR_ERR_NOMEM, "%s: no host memory for the exploration table", fn);
         t->c_init = c_init; t->c_base = c_base;
-        t->host.resize((size_t)n_sims + 1);
-        tree_table_fill(c_init, c_base, 0, n_sims, t->host.data());
+        t->host.resize((size_t)e_max + 1);
+        tree_table_fill(c_init, c_base, 0, e_max, t->host.data());
         if (t->dev.alloc(t->host.size()) != hipSuccess) return fail(XR_ERR_NOMEM, "%s: hipMalloc of the exploration table failed", fn);
         XR_HIP(hipMemcpyAsync(t->dev.p, t->host.data(), t->host.size() * sizeof(double), hipMemcpyHostToDevice, st));
         tab = t.get();          // (a shorter table of the same knobs stays: a launch in flight may read it)
-        tp.tables.push_back(std::move(t));
+        tables.push_back(std::move(t));
     }
-    uint8_t* const m = tp.mem.p;
+    uint8_t* const m = wave_mem.p;
     XrTreeDev t{};
-    t.nodes = reinterpret_cast<XrTreeNode*>(m + o_nodes); t.rs = reinterpret_cast<XrTreeRow*>(m + o_rs);
+    XrTreeKeepDev kd{};
+    if (keep) {          // the half flip: this call searches in the other half, and reads the last call's
+        uint8_t* const km = kp.trees.p;
+        kd.old_nodes = reinterpret_cast<const XrTreeNode*>(km + (kp.half ? k_half1 : k_half0));
+        kp.half ^= 1;
+        t.nodes = reinterpret_cast<XrTreeNode*>(km + (kp.half ? k_half1 : k_half0)); t.rs = reinterpret_cast<XrTreeRow*>(km + k_rs);
+        kd.key = reinterpret_cast<XrTreeKey*>(km + k_key); kd.key_legal = reinterpret_cast<uint64_t*>(km + k_legal);
+        kd.played = rebuild_all ? nullptr : played_dev; kd.kept_out = kept_out_dev; kd.n_add = n_sims;
+    } else {
+        t.nodes = reinterpret_cast<XrTreeNode*>(m + o_nodes); t.rs = reinterpret_cast<XrTreeRow*>(m + o_rs);
+    }
     t.prefix = reinterpret_cast<int32_t*>(m + o_prefix); t.order = reinterpret_cast<int32_t*>(m + o_order);
     t.ret = reinterpret_cast<double*>(m + o_ret);
     int32_t* const rec = reinterpret_cast<int32_t*>(m + o_rec);
     t.E = tab->dev.p; t.prior = prior_dev;
-    t.node_cap = node_cap; t.n_par = n_par; t.k_cap = k_cap; t.n_sims = n_sims; t.env_lo = lo;
+    t.node_cap = node_cap; t.n_par = n_par; t.k_cap = k_cap; t.n_sims = n_sims; t.env_lo = lo; t.e_max = e_max;
     t.visits_out = visits_out_dev; t.value_out = value_out_dev; t.info_out = info_out_dev; t.best_order_out = best_order_out_dev;
     t.best_return_out = best_return_out_dev; t.paths_out = paths_out_dev; t.returns_out = returns_out_dev;
     const int blocks = (int)std::min<int64_t>(b->look_grid, tasks);
-    XR_HIP(xr_launch_tree_reset(&b->dev, &t, rows, st));
+    if (keep) {
+        XR_HIP(xr_launch_tree_keep_begin(&b->dev, &t, &kd, rows, st));
+        kp.rows = rows; kp.lo = lo; kp.node_cap = node_cap; kp.k_cap = k_cap; kp.legal_words = b->legal_words;
+    } else {
+        XR_HIP(xr_launch_tree_reset(&b->dev, &t, rows, st));
+    }
     for (int w = 0; w < n_waves; w++) {
         XR_HIP(xr_launch_tree_select(&b->dev, &t, rows, w, st));
         const Banks ctr = flip_banks(lp.roll_ctr.p, lp.roll_bank, 1);
@@ -2106,7 +2153,7 @@ int32_t tree_search_impl(const char* fn, xr_batch* b, int32_t group, int32_t n_w
 int32_t xr_batch_tree_search(xr_batch* b, int32_t group, int32_t n_waves, int32_t n_par, uint64_t seed, const float* prior_dev, int32_t node_cap,
                              double c_init, double c_base, int32_t* visits_out_dev, double* value_out_dev, int32_t k_cap, int32_t* info_out_dev,
                              int32_t* best_order_out_dev, double* best_return_out_dev, int32_t* paths_out_dev, double* returns_out_dev, void* stream) {
-    return tree_search_impl("xr_batch_tree_search", b, group, n_waves, n_par, seed, prior_dev, node_cap, c_init, c_base, visits_out_dev, value_out_dev, k_cap,
+    return tree_search_impl("xr_batch_tree_search", false, nullptr, nullptr, b, group, n_waves, n_par, seed, prior_dev, node_cap, c_init, c_base, visits_out_dev, value_out_dev, k_cap,
                             info_out_dev, best_order_out_dev, best_return_out_dev, paths_out_dev, returns_out_dev, nullptr, stream);
 }
 
@@ -2114,8 +2161,17 @@ int32_t xr_batch_tree_search_weighted(xr_batch* b, int32_t group, int32_t n_wave
                                       double c_init, double c_base, int32_t* visits_out_dev, double* value_out_dev, int32_t k_cap, int32_t* info_out_dev,
                                       int32_t* best_order_out_dev, double* best_return_out_dev, int32_t* paths_out_dev, double* returns_out_dev,
                                       const int32_t* sim_weights_dev, void* stream) {
-    return tree_search_impl("xr_batch_tree_search_weighted", b, group, n_waves, n_par, seed, prior_dev, node_cap, c_init, c_base, visits_out_dev, value_out_dev,
+    return tree_search_impl("xr_batch_tree_search_weighted", false, nullptr, nullptr, b, group, n_waves, n_par, seed, prior_dev, node_cap, c_init, c_base, visits_out_dev, value_out_dev,
                             k_cap, info_out_dev, best_order_out_dev, best_return_out_dev, paths_out_dev, returns_out_dev, sim_weights_dev, stream);
+}
+
+int32_t xr_batch_tree_search_keep(xr_batch* b, int32_t group, const int32_t* played_dev, int32_t n_waves, int32_t n_par, uint64_t seed, const float* prior_dev,
+                                  int32_t node_cap, double c_init, double c_base, int32_t* visits_out_dev, double* value_out_dev, int32_t k_cap,
+                                  int32_t* info_out_dev, int32_t* best_order_out_dev, double* best_return_out_dev, int32_t* paths_out_dev,
+                                  double* returns_out_dev, const int32_t* sim_weights_dev, int32_t* kept_out_dev, void* stream) {
+    return tree_search_impl("xr_batch_tree_search_keep", true, played_dev, kept_out_dev, b, group, n_waves, n_par, seed, prior_dev, node_cap, c_init, c_base,
+                            visits_out_dev, value_out_dev, k_cap, info_out_dev, best_order_out_dev, best_return_out_dev, paths_out_dev, returns_out_dev,
+                            sim_weights_dev, stream);
 }
 
 // ---- branch ------------------------------------------------------------------------------------------------------------------------

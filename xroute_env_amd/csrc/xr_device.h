@@ -231,9 +231,10 @@ struct XrTreeDev {
     int32_t* prefix;         // [rows][n_par][k_cap] the paths of the current wave, each ended by 0: the rollout launch's prefix
     int32_t* order;          // [rows][n_par][k_cap] the rollout launch's order rows
     double* ret;             // [rows][n_par] its returns
-    const double* E;         // [n_sims + 1] exploration table
+    const double* E;         // [e_max + 1] exploration table
     const float* prior;      // null, or [rows][k_cap]
-    int32_t node_cap, n_par, k_cap, n_sims, env_lo;
+    int32_t node_cap, n_par, k_cap, n_sims, env_lo;   // n_sims: the call's simulations, the stride of paths_out / returns_out
+    int32_t e_max;           // the last entry of E (select clamps there): n_sims for the plain search, XR_TREE_MAX_SIMS for a kept one
     int32_t* visits_out;
     double* value_out;
     int32_t* info_out;
@@ -241,6 +242,24 @@ struct XrTreeDev {
     double* best_return_out;
     int32_t* paths_out;
     double* returns_out;
+};
+
+// Kept trees (xr_tree_keep.h, xr_batch_tree_search_keep): what says which state of its env a kept tree belongs to, and what the first
+// kernel of a kept call gets besides XrTreeDev (whose nodes are the half the call searches in)
+struct XrTreeKey {
+    int64_t env_steps;
+    int32_t region, replay;
+    int32_t valid, pad;
+};
+static_assert(sizeof(XrTreeKey) == 24, "XrTreeKey layout");
+struct XrTreeKeepDev {
+    const XrTreeNode* old_nodes;   // [rows][node_cap] the half the last call searched in
+    XrTreeKey* key;                // [rows]
+    uint64_t* key_legal;           // [rows][legal_words]
+    const int32_t* played;         // null (every row is rebuilt), or [rows]
+    int32_t* kept_out;             // null, or [rows][2]
+    int32_t n_add;                 // the simulations this call adds: n_waves x n_par
+    int32_t pad;
 };
 
 // Which instantiation of the route / order / step-queue kernels a launch takes, and its launch shape (xr_kernels.hip maps
@@ -298,6 +317,8 @@ hipError_t xr_launch_branch(const XrSlotRows* env, const XrSlotRows* stg, int en
 hipError_t xr_launch_tree_reset(const XrBatchDev* src, const XrTreeDev* t, int rows, hipStream_t st) __attribute__((weak));
 hipError_t xr_launch_tree_select(const XrBatchDev* src, const XrTreeDev* t, int rows, int wave, hipStream_t st) __attribute__((weak));
 hipError_t xr_launch_tree_backup(const XrBatchDev* src, const XrTreeDev* t, int rows, int wave, int last, hipStream_t st) __attribute__((weak));
+// kept trees (xr_tree_keep.h).  Weak for the same reason: xr_batch_tree_search_keep answers XR_ERR_STATE where it is not linked
+hipError_t xr_launch_tree_keep_begin(const XrBatchDev* src, const XrTreeDev* t, const XrTreeKeepDev* k, int rows, hipStream_t st) __attribute__((weak));
 hipError_t xr_launch_guide_masks(const XrBatchDev* b, uint8_t* masks, int k_max, hipStream_t st);
 hipError_t xr_launch_ingest_state(const XrBatchDev* b, const int16_t* owner_in, const uint64_t* legal_in, const int32_t* cum_in, hipStream_t st);
 hipError_t xr_launch_pack_state(const XrBatchDev* b, uint8_t* rows, int64_t row_bytes, int region_base, hipStream_t st);

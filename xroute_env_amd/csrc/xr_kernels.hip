@@ -14,6 +14,7 @@
 //   xr_lookahead_plan_kernel + xr_lookahead_kernel   (xr_lookahead.h) every candidate net of every env routed in a throw-away copy of its slot
 //   xr_rollout_kernel            (xr_rollout.h) every env's episode played to its end, R times, in throw-away copies of its slot
 //   xr_branch_kernel<0 / 1>      (xr_branch.h) env slots take other slots' state: parents of overwritten parents to staging, then every moved slot
+//   xr_tree_keep_begin_kernel      (xr_tree_keep.h) the first kernel of a search that continues from the played net's subtree
 //   xr_tree_reset / select / backup_kernel   (xr_tree.h) pUCT over net orderings with the tree in device memory, one wavefront per row
 //   xr_random_action_kernel
 //   xr_weighted_action_kernel    (xr_weighted.h) XR-Pick v1: a legal net drawn in proportion to caller-supplied integer weights, one wave per env
@@ -2201,6 +2202,7 @@ __global__ void __launch_bounds__(256) xr_expand_state_kernel(XrBatchDev b, cons
 #include "xr_rollout.h"
 #include "xr_weighted.h"
 #include "xr_tree.h"
+#include "xr_tree_keep.h"
 #include "xr_branch.h"
 
 // ------------------------------------------------------------------------------------------------
@@ -2384,6 +2386,12 @@ hipError_t xr_launch_tree_select(const XrBatchDev* src, const XrTreeDev* t, int 
 
 hipError_t xr_launch_tree_backup(const XrBatchDev* src, const XrTreeDev* t, int rows, int wave, int last, hipStream_t st) {
     hipLaunchKernelGGL(xr_tree_backup_kernel, dim3(rows), dim3(64), 0, st, *src, *t, wave, last);
+    return hipGetLastError();
+}
+
+// kept trees (xr_tree_keep.h): the first kernel of xr_batch_tree_search_keep, one wavefront per row
+hipError_t xr_launch_tree_keep_begin(const XrBatchDev* src, const XrTreeDev* t, const XrTreeKeepDev* k, int rows, hipStream_t st) {
+    hipLaunchKernelGGL(xr_tree_keep_begin_kernel, dim3(rows), dim3(64), 0, st, *src, *t, *k);
     return hipGetLastError();
 }
 

@@ -125,7 +125,7 @@ __global__ void __launch_bounds__(64) xr_tree_select_kernel(XrBatchDev src, XrTr
             if (first < 0 || depth >= k_cap) break;
             const int cnt = __builtin_amdgcn_readfirstlane(nodes[node].count);
             const int n_p = __builtin_amdgcn_readfirstlane(nodes[node].N + nodes[node].V);
-            const double Ep = t.E[n_p < t.n_sims ? n_p : t.n_sims];
+            const double Ep = t.E[n_p < t.e_max ? n_p : t.e_max];
             double bs = 0.0;
             int bi = 0x7FFFFFFF;
             for (int c = lane; c < cnt; c += 64) {

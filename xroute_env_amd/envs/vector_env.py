@@ -245,30 +245,36 @@ class XRouteVectorEnv:
     # ---- tree search: MCTS over net orderings from the current state, the env untouched ------------------------------------------
     def tree_search(self, n_waves: int, n_par: int, seed: int = 0, prior: Optional[torch.Tensor] = None, node_cap: Optional[int] = None,
                     c_init: float = 1.25, c_base: float = 19652.0, group: Optional[int] = None, trace: bool = False,
-                    sim_weights: Optional[torch.Tensor] = None):
-        """RegionBatch.tree_search's dict {visits, value, info, best_order, best_return[, paths, returns]}.  group None: the whole batch,
+                    sim_weights: Optional[torch.Tensor] = None, keep: bool = False, played: Optional[torch.Tensor] = None):
+        """RegionBatch.tree_search's dict {visits, value, info, best_order, best_return[, paths, returns][, kept]}.  group None: the whole batch,
         after every group's outstanding work.  A group: on that group's stream, ordered like rollout(group); the group's event then
-        covers it.  sim_weights: None, or int32 [rows, k_max]: the simulations follow the weighted policy."""
+        covers it.  sim_weights: None, or int32 [rows, k_max]: the simulations follow the weighted policy.  keep, played: the kept search
+        (RegionBatch.tree_search): the caller's tree stays, and continues where `played` says how its envs have moved."""
         if group is None:
             self._join_groups()
-            return self.batch.tree_search(n_waves, n_par, seed, prior, node_cap, c_init, c_base, trace=trace, sim_weights=sim_weights)
+            return self.batch.tree_search(n_waves, n_par, seed, prior, node_cap, c_init, c_base, trace=trace, sim_weights=sim_weights, keep=keep,
+                                          played=played)
         (g,) = self._groups_of(group)
         s = self.group_streams[g]
         s.wait_stream(torch.cuda.current_stream(self.device))
         with torch.cuda.stream(s):
             res = self.batch.tree_search(n_waves, n_par, seed, prior, node_cap, c_init, c_base, group=g, stream=s, trace=trace,
-                                         sim_weights=sim_weights)
+                                         sim_weights=sim_weights, keep=keep, played=played)
             self.group_events[g].record(s)
+        if isinstance(played, torch.Tensor):
+            played.record_stream(s)
         return res
 
     def tree_actions(self, n_waves: int, n_par: int, seed: int = 0, prior: Optional[torch.Tensor] = None, node_cap: Optional[int] = None,
-                     c_init: float = 1.25, c_base: float = 19652.0, group: Optional[int] = None) -> torch.Tensor:
+                     c_init: float = 1.25, c_base: float = 19652.0, group: Optional[int] = None, keep: bool = False,
+                     played: Optional[torch.Tensor] = None) -> torch.Tensor:
         """int32 actions [rows]: per env the most visited child of its search's root; ties go to the higher value, then to the lower
-        net; 0 for a done env, like random_actions.  (A root that did not fit node_cap has no child: the first net of the best line.)"""
+        net; 0 for a done env, like random_actions.  (A root that did not fit node_cap has no child: the first net of the best line.)
+        keep, played: the kept search; the actions returned, once stepped, are the next call's `played`."""
         if group is None:
-            return self._most_visited(self.tree_search(n_waves, n_par, seed, prior, node_cap, c_init, c_base))
+            return self._most_visited(self.tree_search(n_waves, n_par, seed, prior, node_cap, c_init, c_base, keep=keep, played=played))
         (g,) = self._groups_of(group)
-        res = self.tree_search(n_waves, n_par, seed, prior, node_cap, c_init, c_base, group=g)
+        res = self.tree_search(n_waves, n_par, seed, prior, node_cap, c_init, c_base, group=g, keep=keep, played=played)
         s = self.group_streams[g]
         with torch.cuda.stream(s):
             act = self._most_visited(res)
