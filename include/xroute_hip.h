@@ -504,6 +504,51 @@ int32_t xr_batch_rollout(xr_batch* b, int32_t group, int32_t n_rollouts, int32_t
                          int32_t* out_dev, double* return_out_dev, uint64_t* hash_out_dev,
                          int32_t* order_out_dev, int32_t k_cap, void* stream);
 
+/* ---- peek: the state after a line of play, packed, without stepping ---- */
+/* From the state every env is in now: the STATE the env would be in after a given line of play, n_lines lines per env, as the packed
+ * state row of xr_batch_pack_state — what xr_batch_expand_state turns into the head rows xr_batch_step_compact writes and into the nlegal /
+ * region arrays xr_agent_actor takes, so that a network can be asked about a state the env is not in (a critic value for every successor,
+ * a learned tree prior).  For every row (an env of the whole batch or of one env group, exactly as in xr_batch_rollout) and every line l
+ * in [0, n_lines): copy the env's state into a throw-away shadow slot and route the line's prefix there under xr_batch_rollout's prefix
+ * rules — every route by the same router the step takes.  Nothing continues after the prefix: the policy is always "stop".
+ *   group            -1: the whole batch, rows [0, n_envs).  >= 0: that env group; rows start at the group's first slot, and the work is
+ *                    enqueued on `stream` only.
+ *   n_lines          1 .. XR_PEEK_MAX lines per env.
+ *   prefix_dev       NULL, or int32 [rows][n_lines][prefix_stride] of 1-based net ids, a value <= 0 ends a list.  An entry that is not
+ *                    legal at that point is skipped and flagged XR_ENV_BAD_ACTION in the line's status; a skipped entry costs no ply.
+ *                    Once no net is left the rest of a list is ignored.
+ *   max_plies        0: the whole list.  > 0: stop after that many real routes.
+ *   rows_out_dev     uint8 [rows][n_lines][row_bytes], 8-byte aligned, row_bytes a multiple of 8 and >= xr_batch_state_row_bytes: row
+ *                    (row * n_lines + l) is the packed state row of the shadow slot after the line, in xr_batch_pack_state's format
+ *                    (int32 region + region_base | nlegal | legal_words | occ_words, uint64 legal[legal_words], uint64
+ *                    occ[occ_words]) — byte-identical to what xr_batch_pack_state(region_base) writes for a twin env that really stepped
+ *                    the line's legal nets in order.  Bytes of a row beyond 16 + 8 * (legal_words + occ_words) are not written.
+ *   region_base      added to the env's region index in the row's header, as in xr_batch_pack_state.
+ *   out_dev, return_out_dev, hash_out_dev, order_out_dev, k_cap
+ *                    [rows][n_lines]...: bit for bit what xr_batch_rollout(..., XR_ROLLOUT_STOP, ...) writes for the same arguments
+ *                    (return / hash / order may be NULL; k_cap >= k_max is required only with order_out_dev).
+ * A line that makes no real route (prefix_dev == NULL, an empty list, a list of illegal entries only, a done env) writes the row of the
+ * env's current state and the empty rollout record — peek never looks through an auto-reset.  Every output entry is written exactly once
+ * per call.
+ * Errors (the batch is untouched after any of them): XR_ERR_INVALID null b / rows_out_dev / out_dev, rows_out_dev not 8-byte aligned or
+ * row_bytes % 8 != 0, a group outside -1 .. n_groups - 1, prefix_dev with prefix_stride < 1, a negative max_plies; XR_ERR_STATE before
+ * xr_batch_load_regions; XR_ERR_RANGE n_lines outside 1 .. XR_PEEK_MAX, row_bytes < xr_batch_state_row_bytes, k_cap < k_max with
+ * order_out_dev, rows x n_lines beyond 31 bits; XR_ERR_RANGE for the HBM-scratch router forms (force_scratch_field included) and for
+ * stream_per_region, for lookahead's reason.
+ * Contract, rollout's word for word.  A peek never synchronises: it only enqueues on `stream` (one persistent launch; tasks are claimed
+ * from a counter that the previous launch on the pool zeroed).  It may allocate its private memory on the first call, per batch and per
+ * group: it plays in lookahead's shadow slots and claims from the rollout's claim counters (two alternating banks, no memset per call;
+ * peeks and rollouts on one pool are ordered by the caller anyway).  It leaves NO TRACE in the batch: every array xr_batch_fetch returns
+ * is only read, and the validity of the in-place observation buffers (fp32 and uint8, batch-wide and per group) is kept.  Peeks of
+ * DIFFERENT groups may be in flight at once on different streams; within one group (or for the whole batch) peeks, rollouts, lookaheads
+ * and steps are ordered by the caller. */
+#define XR_PEEK_MAX 4096   /* = XR_ROLLOUT_MAX */
+int32_t xr_batch_peek(xr_batch* b, int32_t group, int32_t n_lines,
+                      const int32_t* prefix_dev, int32_t prefix_stride, int32_t max_plies,
+                      uint8_t* rows_out_dev, int64_t row_bytes, int32_t region_base,
+                      int32_t* out_dev, double* return_out_dev, uint64_t* hash_out_dev,
+                      int32_t* order_out_dev, int32_t k_cap, void* stream);
+
 /* ---- branch: env slots take other slots' state, on the device ---- */
 /* The primitive of every search that keeps more than one line of play (beam search, the tree expansion of the reference's MCTS trainer,
  * baseline/xroute/trainer4/dispatcher.py:113-118): slot i continues from the state slot parent[i] is in now.  A permuted copy of the

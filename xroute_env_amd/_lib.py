@@ -34,6 +34,7 @@ SYMBOLS = [
     "xr_batch_step_observe_u8", "xr_batch_observation_u8",
     "xr_batch_lookahead",
     "xr_batch_rollout",
+    "xr_batch_peek",
     "xr_batch_branch",
     "xr_tree_exploration_table", "xr_batch_tree_search",
     "xr_batch_weighted_actions", "xr_batch_rollout_weighted", "xr_batch_tree_search_weighted",
@@ -65,6 +66,7 @@ XR_MAX_GROUPS, XR_GROUP_INPLACE = 64, 1
 XR_OBS_U8_INPLACE = 1
 XR_ROUTER_SWEEP, XR_ROUTER_DIAL = 1, 2
 XR_ROLLOUT_STOP, XR_ROLLOUT_RANDOM, XR_ROLLOUT_MAX = 0, 1, 4096
+XR_PEEK_MAX = 4096
 XR_TREE_POOL_FULL, XR_TREE_MAX_SIMS = 1, 65536
 XR_ROLLOUT_WEIGHTED, XR_WEIGHT_MAX = 2, 1 << 24
 XR_TREE_KEPT = 2
@@ -150,6 +152,7 @@ def lib():
     L.xr_batch_observation_u8.argtypes = [vp, vp, C.c_int64, C.c_int32, C.c_int32, vp]
     L.xr_batch_lookahead.argtypes = [vp, C.c_int32, vp, vp, C.c_int32, vp, vp]
     L.xr_batch_rollout.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32, C.c_uint64, vp, C.c_int32, C.c_int32, vp, vp, vp, vp, C.c_int32, vp]
+    L.xr_batch_peek.argtypes = [vp, C.c_int32, C.c_int32, vp, C.c_int32, C.c_int32, vp, C.c_int64, C.c_int32, vp, vp, vp, vp, C.c_int32, vp]
     L.xr_batch_branch.argtypes = [vp, C.c_int32, vp, vp]
     L.xr_tree_exploration_table.argtypes = [C.c_double, C.c_double, C.c_int32, vp]
     L.xr_batch_tree_search.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32, C.c_uint64, vp, C.c_int32, C.c_double, C.c_double,

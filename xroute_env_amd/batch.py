@@ -412,6 +412,68 @@ class RegionBatch:
                                                    ptr["out"], ptr["return_out"], ptr["hash_out"], ptr["order_out"], k, self._stream_arg(stream)))
         return {"out": bufs["out"][0], "ret": bufs["return_out"][0], "hash": bufs["hash_out"][0], "order": bufs["order_out"][0]}
 
+    # ---- peek: the state after a line of play, packed, without stepping (xr_batch_peek) ------------------------------------------
+    def peek(self, prefix: Optional[torch.Tensor], n_lines: Optional[int] = None, max_plies: int = 0, region_base: int = 0,
+             row_bytes: Optional[int] = None, group: Optional[int] = None, stream=None, rows_out: Optional[torch.Tensor] = None,
+             out: Optional[torch.Tensor] = None, return_out: Optional[torch.Tensor] = None, hash_out: Optional[torch.Tensor] = None,
+             order_out: Optional[torch.Tensor] = None):
+        """From the state every env is in now, the state it WOULD be in after each of L lines of play; the batch is left exactly as it
+        was.  Line l of a row routes prefix[row, l] (int32 [rows, L, stride] of 1-based net ids, <= 0 ends a list; entries that are not
+        legal are skipped and flagged BAD_ACTION) in a throw-away copy of the slot and stops.  prefix=None needs n_lines: every line is
+        the env's current state.  Returns a dict of device tensors: `rows` uint8 [rows, L, row_bytes], the packed state row after each
+        line in pack_state's format (expand_state(rows.view(-1, row_bytes)) gives the head rows step_compact would write, nlegal and
+        region; bytes past state_row_bytes() are not written), and `out`, `ret`, `hash`, `order` exactly as rollout(policy="stop")
+        returns them for the same prefix.  row_bytes: a multiple of 8, default state_row_bytes().  group: an env group (rows = its
+        slots, enqueued on `stream`, default the current stream); None: the whole batch."""
+        if group is None:
+            g, rows = -1, self.n_envs
+        else:
+            lo, hi = self.group_bounds(group)
+            g, rows = int(group), hi - lo
+        if prefix is None:
+            if n_lines is None:
+                raise ValueError("peek(prefix=None) needs n_lines")
+            L = int(n_lines)
+        else:
+            if not isinstance(prefix, torch.Tensor) or prefix.dim() != 3:
+                raise ValueError(f"prefix must be a contiguous int32 [{rows}, n_lines, stride >= 1] tensor on the batch device")
+            L = int(prefix.shape[1]) if n_lines is None else int(n_lines)
+        if not 1 <= L <= _lib.XR_PEEK_MAX:
+            raise ValueError(f"n_lines must be in 1..{_lib.XR_PEEK_MAX}, got {L}")
+        if rows * L >= 2 ** 31:
+            raise ValueError("rows x n_lines does not fit 31 bits")
+        if int(max_plies) < 0:
+            raise ValueError(f"max_plies must be >= 0, got {max_plies}")
+        pp, stride = None, 0
+        if prefix is not None:
+            if prefix.device != self.device or prefix.dtype != torch.int32 or not prefix.is_contiguous() \
+                    or tuple(prefix.shape[:2]) != (rows, L) or prefix.shape[2] < 1:
+                raise ValueError(f"prefix must be a contiguous int32 [{rows}, {L}, stride >= 1] tensor on the batch device")
+            pp, stride = C.c_void_p(prefix.data_ptr()), int(prefix.shape[2])
+        need = 16 + 8 * (int(self.legal_words) + (int(self.n_max) + 63) // 64)
+        rb = int(row_bytes) if row_bytes is not None else (int(rows_out.shape[-1]) if isinstance(rows_out, torch.Tensor) and rows_out.dim() == 3
+                                                           else need)
+        if rb % 8 != 0 or rb < need:
+            raise ValueError(f"row_bytes must be a multiple of 8 and >= state_row_bytes() = {need}, got {rb}")
+        k = max(int(self.k_max), 1)
+        bufs = {"rows_out": (rows_out, torch.uint8, (rows, L, rb)), "out": (out, torch.int32, (rows, L, 8)),
+                "return_out": (return_out, torch.float64, (rows, L)), "hash_out": (hash_out, torch.int64, (rows, L)),
+                "order_out": (order_out, torch.int32, (rows, L, k))}
+        if any(t is None for t, _, _ in bufs.values()):
+            with torch.cuda.stream(stream if stream is not None else torch.cuda.current_stream(self.device)):
+                bufs = {n: (torch.empty(shp, dtype=dt, device=self.device) if t is None else t, dt, shp) for n, (t, dt, shp) in bufs.items()}
+        for name, (t, dt, shp) in bufs.items():
+            if not isinstance(t, torch.Tensor) or t.device != self.device or t.dtype != dt or not t.is_contiguous() or tuple(t.shape) != shp:
+                raise ValueError(f"{name} must be a contiguous {str(dt).replace('torch.', '')} {list(shp)} tensor on the batch device")
+        if bufs["rows_out"][0].data_ptr() % 8 != 0:
+            raise ValueError("rows_out must be 8-byte aligned")
+        ptr = {n: C.c_void_p(t.data_ptr()) for n, (t, _, _) in bufs.items()}
+        with torch.cuda.device(self.device):
+            _lib.check(self.L.xr_batch_peek(self._h, g, L, pp, stride, int(max_plies), ptr["rows_out"], rb, int(region_base), ptr["out"],
+                                            ptr["return_out"], ptr["hash_out"], ptr["order_out"], k, self._stream_arg(stream)))
+        return {"rows": bufs["rows_out"][0], "out": bufs["out"][0], "ret": bufs["return_out"][0], "hash": bufs["hash_out"][0],
+                "order": bufs["order_out"][0]}
+
     # ---- branch: env slots take other slots' state, on the device (xr_batch_branch) ----------------------------------------------
     def branch(self, parent: torch.Tensor, group: Optional[int] = None, stream=None) -> None:
         """Row i continues from the state row parent[i] is in now (int32 [rows] on the device; rows and indices relative to the group's

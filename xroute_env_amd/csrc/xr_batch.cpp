@@ -2005,6 +2005,42 @@ int32_t xr_batch_rollout_weighted(xr_batch* b, int32_t group, int32_t n_rollouts
                         hash_out_dev, order_out_dev, k_cap, weights_dev, weights_k_cap, stream);
 }
 
+// ---- peek --------------------------------------------------------------------------------------------------------------------------
+// xr_batch_rollout's checks in xr_batch_rollout's order, with the row arguments where the policy's were; the pool and the claim counters
+// are the rollout's (calls on one pool are ordered by the caller)
+int32_t xr_batch_peek(xr_batch* b, int32_t group, int32_t n_lines, const int32_t* prefix_dev, int32_t prefix_stride, int32_t max_plies,
+                      uint8_t* rows_out_dev, int64_t row_bytes, int32_t region_base, int32_t* out_dev, double* return_out_dev, uint64_t* hash_out_dev,
+                      int32_t* order_out_dev, int32_t k_cap, void* stream) {
+    const char* fn = "xr_batch_peek";
+    if (!b || !rows_out_dev || !out_dev) return fail(XR_ERR_INVALID, "%s: null argument", fn);
+    if ((reinterpret_cast<uintptr_t>(rows_out_dev) & 7) || row_bytes % 8 != 0)
+        return fail(XR_ERR_INVALID, "%s: rows_out_dev %p / row_bytes %lld are not 8-byte aligned", fn, (void*)rows_out_dev, (long long)row_bytes);
+    if (!b->loaded) return fail(XR_ERR_STATE, "%s: load regions first", fn);
+    int lo, rows;
+    if (const int32_t rc = group_rows(b, group, fn, lo, rows)) return rc;
+    if (prefix_dev && prefix_stride < 1) return fail(XR_ERR_INVALID, "%s: prefix_stride %d < 1 with a prefix", fn, prefix_stride);
+    if (max_plies < 0) return fail(XR_ERR_INVALID, "%s: max_plies %d is negative", fn, max_plies);
+    if (n_lines < 1 || n_lines > XR_PEEK_MAX) return fail(XR_ERR_RANGE, "%s: n_lines %d outside 1..%d", fn, n_lines, XR_PEEK_MAX);
+    const int64_t need = 16 + 8 * ((int64_t)b->legal_words + ((b->n_max + 63) >> 6));
+    if (row_bytes < need) return fail(XR_ERR_RANGE, "%s: row_bytes %lld < %lld (xr_batch_state_row_bytes)", fn, (long long)row_bytes, (long long)need);
+    if (order_out_dev && k_cap < b->k_max) return fail(XR_ERR_RANGE, "%s: k_cap %d < k_max %d", fn, k_cap, b->k_max);
+    if (const int32_t rc = lds_field_check(b, fn)) return rc;
+    const int64_t tasks = (int64_t)rows * n_lines;
+    if (tasks >= ((int64_t)1 << 31)) return fail(XR_ERR_RANGE, "%s: rows x n_lines does not fit 31 bits", fn);
+    if (!xr_lookahead_occupancy || !xr_launch_peek) return fail(XR_ERR_STATE, "%s: peek kernels not linked", fn);
+    XR_HIP(hipSetDevice(b->cfg.device));
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const XrRouteVariant v = route_variant(b);
+    xr_batch::LookPool& lp = b->look[group + 1];
+    if (const int32_t rc = shadow_pool(b, lp, v, st, fn, true)) return rc;
+    const XrBatchDev sh = shadow_view(b, lp);
+    const Banks ctr = flip_banks(lp.roll_ctr.p, lp.roll_bank, 1);
+    const int blocks = (int)std::min<int64_t>(b->look_grid, tasks);
+    XR_HIP(xr_launch_peek(&b->dev, &sh, lo, (int)tasks, n_lines, prefix_dev, prefix_dev ? prefix_stride : 0, max_plies, ctr.cur, ctr.next, rows_out_dev,
+                          row_bytes, region_base, out_dev, return_out_dev, hash_out_dev, order_out_dev, order_out_dev ? k_cap : 0, v, blocks, st));
+    return XR_OK;
+}
+
 // ---- tree search -------------------------------------------------------------------------------------------------------------------
 namespace {
 bool tree_knobs_ok(double c_init, double c_base) { return std::isfinite(c_init) && std::isfinite(c_base) && c_base > 0.0; }

@@ -302,6 +302,11 @@ hipError_t xr_launch_lookahead(const XrBatchDev* src, const XrBatchDev* shadow, 
 hipError_t xr_launch_rollout(const XrBatchDev* src, const XrBatchDev* shadow, int env_lo, int n_tasks, int n_rollouts, int policy, uint64_t seed,
                              const int32_t* prefix, int prefix_stride, int max_plies, uint32_t* ctr, uint32_t* next_ctr, int32_t* out, double* return_out,
                              uint64_t* hash_out, int32_t* order_out, int k_cap, XrRouteVariant v, int blocks, hipStream_t st) __attribute__((weak));
+// peek (xr_peek.h).  Weak for the same reason: xr_batch_peek answers XR_ERR_STATE where it is not linked
+hipError_t xr_launch_peek(const XrBatchDev* src, const XrBatchDev* shadow, int env_lo, int n_tasks, int n_lines, const int32_t* prefix, int prefix_stride,
+                          int max_plies, uint32_t* ctr, uint32_t* next_ctr, uint8_t* rows, int64_t row_bytes, int region_base, int32_t* out,
+                          double* return_out, uint64_t* hash_out, int32_t* order_out, int k_cap, XrRouteVariant v, int blocks, hipStream_t st)
+    __attribute__((weak));
 // weighted net sampling (xr_weighted.h).  Weak for the same reason: xr_batch_weighted_actions, xr_batch_rollout_weighted and
 // xr_batch_tree_search_weighted answer XR_ERR_STATE where they are not linked
 hipError_t xr_launch_weighted_actions(const XrBatchDev* b, const int32_t* weights, int k_cap, int32_t* actions, uint64_t seed, hipStream_t st)

@@ -13,6 +13,7 @@
 //   xr_netplane_kernel, xr_netplane_stream_kernel   the writer of the split form (XR_OBS_SPLIT)
 //   xr_lookahead_plan_kernel + xr_lookahead_kernel   (xr_lookahead.h) every candidate net of every env routed in a throw-away copy of its slot
 //   xr_rollout_kernel            (xr_rollout.h) every env's episode played to its end, R times, in throw-away copies of its slot
+//   xr_peek_kernel               (xr_peek.h) the state after a line of play as a packed state row: the rollout's loops, then xr_pack_state_kernel's packing
 //   xr_branch_kernel<0 / 1>      (xr_branch.h) env slots take other slots' state: parents of overwritten parents to staging, then every moved slot
 //   xr_tree_keep_begin_kernel      (xr_tree_keep.h) the first kernel of a search that continues from the played net's subtree
 //   xr_tree_reset / select / backup_kernel   (xr_tree.h) pUCT over net orderings with the tree in device memory, one wavefront per row
@@ -2200,6 +2201,7 @@ __global__ void __launch_bounds__(256) xr_expand_state_kernel(XrBatchDev b, cons
 
 #include "xr_lookahead.h"
 #include "xr_rollout.h"
+#include "xr_peek.h"
 #include "xr_weighted.h"
 #include "xr_tree.h"
 #include "xr_tree_keep.h"
@@ -2335,6 +2337,24 @@ hipError_t xr_launch_rollout(const XrBatchDev* src, const XrBatchDev* shadow, in
                            prefix_stride, max_plies, ctr, next_ctr, out, return_out, hash_out, order_out, k_cap);
     });
     return hipGetLastError();
+}
+
+// peek (xr_peek.h): the persistent launch; task t = (row t / n_lines, line t % n_lines).  A launch above 64 KB of dynamic LDS raises the
+// kernel's limit itself, as xr_launch_rollout_weighted does
+hipError_t xr_launch_peek(const XrBatchDev* src, const XrBatchDev* shadow, int env_lo, int n_tasks, int n_lines, const int32_t* prefix, int prefix_stride,
+                          int max_plies, uint32_t* ctr, uint32_t* next_ctr, uint8_t* rows, int64_t row_bytes, int region_base, int32_t* out,
+                          double* return_out, uint64_t* hash_out, int32_t* order_out, int k_cap, XrRouteVariant v, int blocks, hipStream_t st) {
+    const dim3 g(blocks), t(v.threads);
+    return xr_with_variant(v.lds_dist, v.zch, [&](auto L, auto Z) {
+        if (v.lds_bytes > 64 * 1024) {
+            const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&xr_peek_kernel<L.value, Z.value>),
+                                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)v.lds_bytes);
+            if (e != hipSuccess) return e;
+        }
+        hipLaunchKernelGGL((xr_peek_kernel<L.value, Z.value>), g, t, v.lds_bytes, st, *src, *shadow, env_lo, n_tasks, n_lines, prefix, prefix_stride,
+                           max_plies, ctr, next_ctr, rows, row_bytes, region_base, out, return_out, hash_out, order_out, k_cap);
+        return hipGetLastError();
+    });
 }
 
 // weighted net sampling (xr_weighted.h): one wave per env, four per workgroup; rows of `weights` / `actions` start at env_base

@@ -9,6 +9,9 @@
 `weighted`    weights for the weighted net sampling (XR-Pick v1: RegionBatch.weighted_actions, rollout(policy="weighted"),
               tree_search(sim_weights=...)) and a cross-entropy search over orderings on top of it
               (`from xroute_env_amd.envs.weighted import cem_search, lookahead_weights`)
+`peek`        successor states and their values on RegionBatch.peek: every candidate net's successor as head rows, a critic value per
+              successor, the value-greedy action and the value prior of a tree search
+              (`from xroute_env_amd.envs.peek import successor_values, value_actions, value_prior`)
 """
 from .facade import OrderingEvaluationEnv, OrderingTrainingEnv, StaticRegionEnv, XRouteEnv
 from .vector_env import XRouteVectorEnv

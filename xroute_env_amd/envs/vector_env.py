@@ -190,6 +190,22 @@ class XRouteVectorEnv:
             self.group_events[g].record(s)
         return res
 
+    def peek(self, prefix: Optional[torch.Tensor], n_lines: Optional[int] = None, max_plies: int = 0, region_base: int = 0,
+             row_bytes: Optional[int] = None, group: Optional[int] = None):
+        """RegionBatch.peek's dict {rows, out, ret, hash, order}: the packed state after each line of play, without stepping.  group
+        None: the whole batch, after every group's outstanding work.  A group: on that group's stream, ordered like rollout(group); the
+        group's event then covers it."""
+        if group is None:
+            self._join_groups()
+            return self.batch.peek(prefix, n_lines, max_plies, region_base, row_bytes)
+        (g,) = self._groups_of(group)
+        s = self.group_streams[g]
+        s.wait_stream(torch.cuda.current_stream(self.device))
+        with torch.cuda.stream(s):
+            res = self.batch.peek(prefix, n_lines, max_plies, region_base, row_bytes, group=g, stream=s)
+            self.group_events[g].record(s)
+        return res
+
     def rollout_actions(self, n_rollouts: int, seed: int, group: Optional[int] = None) -> torch.Tensor:
         """int32 actions [rows]: per env the first net of its best random rollout (the highest return of n_rollouts; the first maximum
         on a tie); 0 for a done env, like random_actions."""
