@@ -748,6 +748,90 @@ int32_t xr_batch_tree_search_keep(xr_batch* b, int32_t group, const int32_t* pla
                                   int32_t* paths_out_dev, double* returns_out_dev, const int32_t* sim_weights_dev,
                                   int32_t* kept_out_dev, void* stream);
 
+/* ---- evaluated tree search: leaves valued by the caller's network ---- */
+/* The search of the reference's MuZero agent with the network where the reference has it (baseline/xroute/self_route.py:341-371, 482-568):
+ * a simulation stops at the selected leaf, the leaf's STATE goes to the caller's evaluator as a packed state row (xr_batch_peek's), and
+ * the evaluator's value — plus, optionally, a prior for the leaf's own children — goes back into the tree.  A simulation routes only the
+ * nets on its path; nothing is rolled out to the end of the episode.  Three enqueue-only entry points, called in the order
+ * open, {leaves, [the caller's evaluator, on the same stream], backup} x waves; no host round trip anywhere.  A row is an env of the whole
+ * batch (group -1) or of one env group, as in xr_batch_lookahead.  "XR-Tree v2, evaluated" (build-defined); Nodes, Prior, Table, Select
+ * and Backup are XR-Tree v1's (the tree search section above) except for what follows:
+ *   Own memory. Every caller (the whole batch, or one env group) has an evaluated-tree pool of its own, apart from the pool of the plain
+ *            searches and from the kept-tree pool: none of the three searches disturbs another.  The pool holds one session:
+ *            rows x (40 node_cap + 40 + n_par x (4 k_cap + 16) + 8 k_cap + 8 legal_words + 4) bytes, each of its nine arrays (nodes, row
+ *            states, paths, line returns, leaf records, best order, legal words, nlegal, prior) rounded up to 16, allocated again when
+ *            an open call needs more than any before it, plus 8 x (max_sims + 1) bytes per distinct (c_init, c_base, max_sims) for the
+ *            table, plus lookahead's shadow slots and the rollout's claim counters where the caller has not used them yet (the peek
+ *            launch plays there).
+ * xr_batch_tree_open     starts a session (and ends the pool's last one, whatever state it was in).  It uploads E[0 .. max_sims] (v1's
+ *            Table, computed on the host; xr_tree_exploration_table returns the same numbers) and runs one kernel: per row it copies the
+ *            env's nlegal and legal words — the SNAPSHOT — and the row of root_prior_dev into the pool, resets the row state exactly as
+ *            the plain search does (min / max / best = +inf / -inf / -inf, no node, depth 0, flags 0), and builds the root and expands it
+ *            under v1's Prior rule from root_prior_dev (fp32 [rows][k_cap], or NULL: uniform).  Every later kernel of the session reads
+ *            the snapshot, never the env's live words, and root_prior_dev is not read again after this call.  A caller who steps the env
+ *            (or resets it, or branches into it) between open and the last backup gets unspecified numbers — every access stays in bounds
+ *            — and must re-open.  Done rows (no legal net at the open call) get v1's empty result from every backup and take part in
+ *            nothing.
+ *   n_par            1 .. XR_PEEK_MAX lanes per wave.
+ *   max_sims         n_par .. XR_TREE_MAX_SIMS: the simulations the session may run, the last entry of its table.
+ *   node_cap         >= 1 nodes per row, the root included (1 + (max_sims + 1) * k_max always suffices).
+ *   k_cap            >= k_max: the row length of every per-net array of the session.
+ * xr_batch_tree_leaves   one wave, two enqueues (and a device-to-device copy of rows x n_par doubles when return_out_dev is given).
+ *   Select.  v1's Select rule word for word: the lanes j = 0 .. n_par - 1 descend one after the other, pending visits V included, the
+ *            best child is the maximum under >, a tie goes to the lowest net.  A lane stops at an unexpanded or terminal node.  An
+ *            unexpanded non-terminal node — a FRESH leaf — is expanded at select time if the pool has room, its block's P taken from the
+ *            open call's row prior under v1's rule.  Select writes paths_out_dev (NULL, or int32 [rows][n_par][k_cap], each list ended
+ *            by 0 unless it has k_cap nets) and leaf_out_dev (NULL, or int32 [rows][n_par][2] = {node index, flags}); the flags are
+ *            XR_TREE_LEAF_TERMINAL (the path holds every legal net of the snapshot), XR_TREE_LEAF_FRESH (this lane expanded the node
+ *            in this wave) or 0 (an unexpanded node a full pool has no room for); a done row has {-1, XR_TREE_LEAF_NONE} and empty paths.
+ *   Peek.    One peek launch — xr_batch_peek's kernel through its launcher — with n_lines = n_par, the prefix = the wave's paths,
+ *            max_plies 0: rows_out_dev (uint8 [rows][n_par][row_bytes]), out_dev (int32 [rows][n_par][8]) and return_out_dev (NULL, or
+ *            double [rows][n_par]) are bit for bit what xr_batch_peek writes for that prefix; row_bytes and region_base are its
+ *            arguments.  The tree keeps the line returns for the backup.
+ * xr_batch_tree_backup   one enqueue.  value_dev: double [rows][n_par], the evaluator's value of each leaf's state: the return it expects
+ *            from that state to the end of the episode.  leaf_prior_dev: NULL, or fp32 [rows][n_par][k_cap], weights per net for the
+ *            children of each lane's leaf.
+ *   Return.  Per row, in lane order: G = the line's return for a TERMINAL leaf (its value entry is not read); otherwise G = ret + v, one
+ *            IEEE addition, v the lane's value entry, or 0.0 where that entry is not finite.
+ *   Backup.  v1's Backup rule: on every node of the path N += 1, V -= 1, W += G; then min = fmin(min, G), max = fmax(max, G).
+ *   Best line.  From TERMINAL simulations only (only there is G an exact episode return): if G > best (strictly: the first wins) best = G
+ *            and the best order becomes the path.  A session without a terminal simulation has best return -inf and best order all 0.
+ *   Leaf priors.  After the lane's backup, if leaf_prior_dev is given and the lane's leaf is FRESH: the P of its children block is
+ *            overwritten by v1's Prior rule from that lane's row — S summed in double over the block's nets in ascending net order,
+ *            entries that are not finite or are < 0 count as 0, P = w[net] / S; S == 0 leaves the block as it is.  A leaf that is not
+ *            FRESH (terminal, unexpanded, or expanded by an earlier wave) is never given a new prior.
+ *   Outputs. Every backup writes visits_out_dev (int32 [rows][k_cap]) and value_out_dev (double [rows][k_cap]) of the root's children
+ *            as v1 does, info_out_dev int32 [rows][4] = {simulations so far, nodes_used, max_depth, flags (XR_TREE_POOL_FULL)}, and,
+ *            where given, best_order_out_dev (int32 [rows][k_cap]), best_return_out_dev (double [rows]) and returns_out_dev (double
+ *            [rows][n_par], the wave's G; 0.0 for a done row): the caller may stop after any wave.
+ * Call order.  XR_ERR_STATE for xr_batch_tree_leaves before a successful open of that pool, or twice without a backup between; for
+ * xr_batch_tree_backup without pending leaves; for any of the three where the kernels are not linked.  XR_ERR_RANGE for a wave that
+ * would pass max_sims (the tree is unchanged).  After xr_batch_set_groups or xr_batch_load_regions the caller must re-open.
+ * Errors (the batch and the session are untouched after any of them): XR_ERR_INVALID null b, a group outside -1 .. n_groups - 1, a c_init
+ * that is not finite, a c_base that is not > 0 and finite (open); null rows_out_dev / out_dev, rows_out_dev not 8-byte aligned or
+ * row_bytes % 8 != 0 (leaves); null value_dev / visits_out_dev / value_out_dev / info_out_dev (backup); XR_ERR_STATE before
+ * xr_batch_load_regions; XR_ERR_RANGE n_par outside 1 .. XR_PEEK_MAX, max_sims outside n_par .. XR_TREE_MAX_SIMS, node_cap < 1,
+ * k_cap < k_max, rows x n_par beyond 31 bits (open), row_bytes < xr_batch_state_row_bytes (leaves), and for the HBM-scratch router forms
+ * (force_scratch_field included) and stream_per_region, for the rollout's reason; XR_ERR_NOMEM when the pool cannot be allocated.  Every
+ * message names the entry point.
+ * Contract, v1's and peek's.  None of the three ever synchronises: each only enqueues on `stream` (open: the table's copy and one launch;
+ * leaves: select and the persistent peek launch; backup: one launch; no workgroup waits for another one).  They leave NO TRACE in the
+ * batch: the peek launch plays in lookahead's shadow slots, every array xr_batch_fetch returns is only read, and the validity of the
+ * in-place observation buffers is kept.  Sessions of DIFFERENT groups may be in flight at once on different streams; within one group
+ * (or for the whole batch) the calls of a session, other searches, peeks, rollouts, lookaheads, branches and steps are ordered by the
+ * caller, and so is the evaluator: it runs on `stream`, or is ordered against it by the caller.
+ * Cuts: no Dirichlet noise, no discounting, no kept tree for this form (a session starts from an empty tree), no HBM-scratch forms. */
+#define XR_TREE_LEAF_TERMINAL 1
+#define XR_TREE_LEAF_FRESH 2
+#define XR_TREE_LEAF_NONE 4
+int32_t xr_batch_tree_open(xr_batch* b, int32_t group, int32_t n_par, int32_t node_cap, double c_init, double c_base,
+                           int32_t max_sims, const float* root_prior_dev, int32_t k_cap, void* stream);
+int32_t xr_batch_tree_leaves(xr_batch* b, int32_t group, uint8_t* rows_out_dev, int64_t row_bytes, int32_t region_base,
+                             int32_t* out_dev, double* return_out_dev, int32_t* paths_out_dev, int32_t* leaf_out_dev, void* stream);
+int32_t xr_batch_tree_backup(xr_batch* b, int32_t group, const double* value_dev, const float* leaf_prior_dev,
+                             int32_t* visits_out_dev, double* value_out_dev, int32_t* info_out_dev,
+                             int32_t* best_order_out_dev, double* best_return_out_dev, double* returns_out_dev, void* stream);
+
 /* ---- XR-Maze v2: global-route guides (optional) ---------------------------------------------- */
 /* The reference's simulator runs with `-follow_guide 1` (ispd/ispd18_test1/run-net-ordering-training.tcl:3) on the guide file
  * it ships (ispd/ispd18_test1/ispd18_test1.input.guide: per net, rectangles per metal layer).  With xr_config.guide_cost > 0 a

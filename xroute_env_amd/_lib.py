@@ -39,6 +39,7 @@ SYMBOLS = [
     "xr_tree_exploration_table", "xr_batch_tree_search",
     "xr_batch_weighted_actions", "xr_batch_rollout_weighted", "xr_batch_tree_search_weighted",
     "xr_batch_tree_search_keep",
+    "xr_batch_tree_open", "xr_batch_tree_leaves", "xr_batch_tree_backup",
     "xr_observation_from_records", "xr_proto_decode", "xr_proto_encode_response", "xr_proto_encode_request",
 ]
 
@@ -70,6 +71,7 @@ XR_PEEK_MAX = 4096
 XR_TREE_POOL_FULL, XR_TREE_MAX_SIMS = 1, 65536
 XR_ROLLOUT_WEIGHTED, XR_WEIGHT_MAX = 2, 1 << 24
 XR_TREE_KEPT = 2
+XR_TREE_LEAF_TERMINAL, XR_TREE_LEAF_FRESH, XR_TREE_LEAF_NONE = 1, 2, 4
 
 
 def tree_seed(seed: int, w: int) -> int:
@@ -164,6 +166,9 @@ def lib():
                                                 vp, vp, C.c_int32, vp, vp, vp, vp, vp, vp, vp]
     L.xr_batch_tree_search_keep.argtypes = [vp, C.c_int32, vp, C.c_int32, C.c_int32, C.c_uint64, vp, C.c_int32, C.c_double, C.c_double,
                                             vp, vp, C.c_int32, vp, vp, vp, vp, vp, vp, vp, vp]
+    L.xr_batch_tree_open.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32, C.c_double, C.c_double, C.c_int32, vp, C.c_int32, vp]
+    L.xr_batch_tree_leaves.argtypes = [vp, C.c_int32, vp, C.c_int64, C.c_int32, vp, vp, vp, vp, vp]
+    L.xr_batch_tree_backup.argtypes = [vp, C.c_int32, vp, vp, vp, vp, vp, vp, vp, vp, vp]
     L.xr_batch_random_actions_group.argtypes = [vp, C.c_int32, vp, C.c_uint64, vp]
     L.xr_batch_fetch_group.argtypes = [vp, C.c_int32, C.c_int32, vp, C.c_size_t, vp]
     L.xr_agent_obstacle_tower_weights.argtypes = []

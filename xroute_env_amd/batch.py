@@ -207,6 +207,7 @@ class RegionBatch:
         with torch.cuda.device(self.device):
             _lib.check(self.L.xr_batch_set_groups(self._h, b.ctypes.data, b.size - 1))
         self._group_bounds = [int(v) for v in b]
+        self._tree_sessions = {}          # (an evaluated-tree session belongs to the rows it was opened for)
 
     @property
     def n_groups(self) -> int:
@@ -572,6 +573,110 @@ class RegionBatch:
                 _lib.check(self.L.xr_batch_tree_search(self._h, g, W, P, C.c_uint64(int(seed) & (2 ** 64 - 1)), pp, cap, ci, cb, ptr["visits"],
                                                        ptr["value"], k, ptr["info"], ptr["best_order"], ptr["best_return"], ptr.get("paths"),
                                                        ptr.get("returns"), self._stream_arg(stream)))
+        return res
+
+    # ---- evaluated tree search: leaves valued by the caller's network (xr_batch_tree_open / _leaves / _backup) -------------------------
+    def _tree_rows(self, group):
+        if group is None:
+            return -1, self.n_envs
+        lo, hi = self.group_bounds(group)
+        return int(group), hi - lo
+
+    def _tree_tensor(self, t, name: str, dtype, shape):
+        if not isinstance(t, torch.Tensor) or t.device != self.device or t.dtype != dtype or not t.is_contiguous() or tuple(t.shape) != tuple(shape):
+            raise ValueError(f"{name} must be a contiguous {str(dtype).replace('torch.', '')} {list(shape)} tensor on the batch device")
+        return C.c_void_p(t.data_ptr())
+
+    def tree_open(self, n_par: int, max_sims: int, root_prior: Optional[torch.Tensor] = None, node_cap: Optional[int] = None,
+                  c_init: float = 1.25, c_base: float = 19652.0, group: Optional[int] = None, stream=None) -> None:
+        """Start a session of "XR-Tree v2, evaluated" (include/xroute_hip.h) from the state every env is in now: a tree per row whose
+        simulations stop at the selected leaf; tree_leaves() hands out a wave's leaves as packed state rows, the caller's evaluator values
+        them, tree_backup() takes the values.  n_par: lanes per wave (1..XR_PEEK_MAX); max_sims: the simulations the session may run
+        (n_par..XR_TREE_MAX_SIMS); root_prior: None (uniform) or float32 [rows, k_max] weights per net, the prior of every block the
+        search expands until an evaluator's leaf prior replaces it; node_cap: nodes per row, default 1 + (max_sims + 1) * k_max (always
+        enough).  The env's legal set is copied: a caller who steps the env before the last tree_backup must open again.  Enqueue-only;
+        the batch is left exactly as it was.  group: an env group (rows = its slots, enqueued on `stream`); None: the whole batch."""
+        g, rows = self._tree_rows(group)
+        P, M = int(n_par), int(max_sims)
+        if not 1 <= P <= _lib.XR_PEEK_MAX:
+            raise ValueError(f"n_par must be in 1..{_lib.XR_PEEK_MAX}, got {n_par}")
+        if not P <= M <= _lib.XR_TREE_MAX_SIMS:
+            raise ValueError(f"max_sims must be in n_par..{_lib.XR_TREE_MAX_SIMS}, got {max_sims}")
+        if rows * P >= 2 ** 31:
+            raise ValueError("rows x n_par does not fit 31 bits")
+        ci, cb = float(c_init), float(c_base)
+        if not math.isfinite(ci):
+            raise ValueError(f"c_init must be finite, got {c_init}")
+        if not (math.isfinite(cb) and cb > 0):
+            raise ValueError(f"c_base must be finite and > 0, got {c_base}")
+        k = max(int(self.k_max), 1)
+        cap = 1 + (M + 1) * k if node_cap is None else int(node_cap)
+        if not 1 <= cap < 2 ** 31:
+            raise ValueError(f"node_cap must be in 1..2^31 - 1, got {node_cap}")
+        pp = self._tree_tensor(root_prior, "root_prior", torch.float32, (rows, k)) if root_prior is not None else None
+        with torch.cuda.device(self.device):
+            _lib.check(self.L.xr_batch_tree_open(self._h, g, P, cap, ci, cb, M, pp, k, self._stream_arg(stream)))
+        if not hasattr(self, "_tree_sessions"):
+            self._tree_sessions = {}
+        self._tree_sessions[g] = P
+
+    def _tree_session(self, group, fn: str):
+        g, rows = self._tree_rows(group)
+        P = getattr(self, "_tree_sessions", {}).get(g)
+        if P is None:
+            raise _lib.XRouteError(_lib.XR_ERR_STATE, f"{fn}: no open session of this caller (tree_open first)")
+        return g, rows, P
+
+    def tree_leaves(self, region_base: int = 0, row_bytes: Optional[int] = None, group: Optional[int] = None, stream=None,
+                    rows_out: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None, return_out: Optional[torch.Tensor] = None,
+                    paths_out: Optional[torch.Tensor] = None, leaf_out: Optional[torch.Tensor] = None):
+        """One wave of the open session: n_par pUCT descents per row (XR-Tree v1's Select), then one peek launch along the paths.  Returns a
+        dict of device tensors: `rows` uint8 [rows, n_par, row_bytes], `out` int32 [rows, n_par, 8] and `ret` float64 [rows, n_par] —
+        exactly what peek(paths) returns — `paths` int32 [rows, n_par, k_max] (each ended by 0) and `leaf` int32 [rows, n_par, 2] =
+        {node, flags: XR_TREE_LEAF_TERMINAL | XR_TREE_LEAF_FRESH | XR_TREE_LEAF_NONE}.  Every wave is followed by tree_backup()."""
+        g, rows, P = self._tree_session(group, "tree_leaves")
+        need = 16 + 8 * (int(self.legal_words) + (int(self.n_max) + 63) // 64)
+        rb = int(row_bytes) if row_bytes is not None else (int(rows_out.shape[-1]) if isinstance(rows_out, torch.Tensor) and rows_out.dim() == 3
+                                                           else need)
+        if rb % 8 != 0 or rb < need:
+            raise ValueError(f"row_bytes must be a multiple of 8 and >= state_row_bytes() = {need}, got {rb}")
+        k = max(int(self.k_max), 1)
+        bufs = {"rows_out": (rows_out, torch.uint8, (rows, P, rb)), "out": (out, torch.int32, (rows, P, 8)),
+                "return_out": (return_out, torch.float64, (rows, P)), "paths_out": (paths_out, torch.int32, (rows, P, k)),
+                "leaf_out": (leaf_out, torch.int32, (rows, P, 2))}
+        for n, (t, dt, shp) in bufs.items():          # the caller's buffers first: a bad one is refused before anything is allocated
+            if t is not None:
+                self._tree_tensor(t, n, dt, shp)
+        if any(t is None for t, _, _ in bufs.values()):
+            with torch.cuda.stream(stream if stream is not None else torch.cuda.current_stream(self.device)):
+                bufs = {n: (torch.empty(shp, dtype=dt, device=self.device) if t is None else t, dt, shp) for n, (t, dt, shp) in bufs.items()}
+        ptr = {n: self._tree_tensor(t, n, dt, shp) for n, (t, dt, shp) in bufs.items()}
+        if bufs["rows_out"][0].data_ptr() % 8 != 0:
+            raise ValueError("rows_out must be 8-byte aligned")
+        with torch.cuda.device(self.device):
+            _lib.check(self.L.xr_batch_tree_leaves(self._h, g, ptr["rows_out"], rb, int(region_base), ptr["out"], ptr["return_out"], ptr["paths_out"],
+                                                   ptr["leaf_out"], self._stream_arg(stream)))
+        return {"rows": bufs["rows_out"][0], "out": bufs["out"][0], "ret": bufs["return_out"][0], "paths": bufs["paths_out"][0],
+                "leaf": bufs["leaf_out"][0]}
+
+    def tree_backup(self, value: torch.Tensor, leaf_prior: Optional[torch.Tensor] = None, group: Optional[int] = None, stream=None):
+        """The evaluator's answer to the last tree_leaves(): value float64 [rows, n_par] (the return expected from each leaf's state to the
+        end of its episode; not finite counts as 0, a terminal leaf's is not read) and leaf_prior None or float32 [rows, n_par, k_max]
+        (weights over the children of each lane's leaf; applied to leaves that lane has just expanded).  Returns a dict of device tensors
+        as tree_search() does — `visits`, `value`, `info` = {simulations so far, nodes_used, max_depth, flags}, `best_order`,
+        `best_return` (from terminal simulations only) — and `returns` float64 [rows, n_par], the wave's G."""
+        g, rows, P = self._tree_session(group, "tree_backup")
+        k = max(int(self.k_max), 1)
+        vp = self._tree_tensor(value, "value", torch.float64, (rows, P))
+        lp = self._tree_tensor(leaf_prior, "leaf_prior", torch.float32, (rows, P, k)) if leaf_prior is not None else None
+        shapes = {"visits": (torch.int32, (rows, k)), "value": (torch.float64, (rows, k)), "info": (torch.int32, (rows, 4)),
+                  "best_order": (torch.int32, (rows, k)), "best_return": (torch.float64, (rows,)), "returns": (torch.float64, (rows, P))}
+        with torch.cuda.stream(stream if stream is not None else torch.cuda.current_stream(self.device)):
+            res = {n: torch.empty(shp, dtype=dt, device=self.device) for n, (dt, shp) in shapes.items()}
+        ptr = {n: C.c_void_p(t.data_ptr()) for n, t in res.items()}
+        with torch.cuda.device(self.device):
+            _lib.check(self.L.xr_batch_tree_backup(self._h, g, vp, lp, ptr["visits"], ptr["value"], ptr["info"], ptr["best_order"], ptr["best_return"],
+                                                   ptr["returns"], self._stream_arg(stream)))
         return res
 
     def alloc_head(self) -> torch.Tensor:

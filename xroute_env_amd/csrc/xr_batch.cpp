@@ -201,6 +201,17 @@ struct xr_batch {
         int rows = 0, lo = -1, node_cap = 0, k_cap = 0, legal_words = 0, half = 0;
         void release() { trees.release(); scratch.release(); tables.clear(); rows = 0; lo = -1; node_cap = 0; k_cap = 0; legal_words = 0; half = 0; }
     } keep[1 + XR_MAX_GROUPS];
+    // evaluated tree search (xr_batch_tree_open / _leaves / _backup): a pool of its own per caller, indexed like tree[].  One session lives
+    // here from its open call on: the trees, the snapshot of the legal words, one wave's paths, line returns and leaf records (`d` is the
+    // view the kernels get), and on the host the session's shape, its simulations so far and whether a wave waits for its backup
+    struct EvalPool {
+        DevBuf<uint8_t> mem;
+        std::vector<std::unique_ptr<TreeTable>> tables;          // E[0 .. max_sims] per (c_init, c_base, max_sims)
+        XrTreeEvalDev d{};
+        int rows = 0, lo = -1, max_sims = 0, sims = 0;
+        bool open = false, pending = false;
+        void release() { mem.release(); tables.clear(); d = XrTreeEvalDev{}; rows = 0; lo = -1; max_sims = 0; sims = 0; open = false; pending = false; }
+    } eval[1 + XR_MAX_GROUPS];
     int look_grid = 0;                         // workgroups of the persistent lookahead launch the chip holds at once (0: not asked yet)
     XrBatchDev dev{};
     ~xr_batch() {
@@ -1057,6 +1068,7 @@ int32_t xr_batch_load_regions(xr_batch* b, const xr_region_desc* regs, int32_t n
     for (xr_batch::BranchPool& bp : b->branch) bp.release();     // and so are the staging rows of xr_batch_branch
     for (xr_batch::TreePool& tp : b->tree) tp.release();
     for (xr_batch::KeepPool& kp : b->keep) kp.release();
+    for (xr_batch::EvalPool& ep : b->eval) ep.release();
     b->look_grid = 0;
     b->guide_csr.release(); b->guide_box.release(); b->guide_mask.release(); b->guide_mask_bytes = 0;        // guides belong to the regions they were loaded for
     memset(&b->dev, 0, sizeof(b->dev));
@@ -2208,6 +2220,134 @@ int32_t xr_batch_tree_search_keep(xr_batch* b, int32_t group, const int32_t* pla
     return tree_search_impl("xr_batch_tree_search_keep", true, played_dev, kept_out_dev, b, group, n_waves, n_par, seed, prior_dev, node_cap, c_init, c_base,
                             visits_out_dev, value_out_dev, k_cap, info_out_dev, best_order_out_dev, best_return_out_dev, paths_out_dev, returns_out_dev,
                             sim_weights_dev, stream);
+}
+
+// ---- evaluated tree search ---------------------------------------------------------------------------------------------------------
+// "XR-Tree v2, evaluated": open starts a session on the caller's pool, leaves runs one wave's select and its peek launch, backup takes
+// the evaluator's values.  The host keeps the session's shape and its place in the call order; every refusal names its entry point
+int32_t xr_batch_tree_open(xr_batch* b, int32_t group, int32_t n_par, int32_t node_cap, double c_init, double c_base, int32_t max_sims,
+                           const float* root_prior_dev, int32_t k_cap, void* stream) {
+    const char* fn = "xr_batch_tree_open";
+    if (!b) return fail(XR_ERR_INVALID, "%s: null argument", fn);
+    if (!b->loaded) return fail(XR_ERR_STATE, "%s: load regions first", fn);
+    int lo, rows;
+    if (const int32_t rc = group_rows(b, group, fn, lo, rows)) return rc;
+    if (!std::isfinite(c_init)) return fail(XR_ERR_INVALID, "%s: c_init is not finite", fn);
+    if (!tree_knobs_ok(c_init, c_base)) return fail(XR_ERR_INVALID, "%s: c_base must be finite and > 0", fn);
+    if (n_par < 1 || n_par > XR_PEEK_MAX) return fail(XR_ERR_RANGE, "%s: n_par %d outside 1..%d", fn, n_par, XR_PEEK_MAX);
+    if (max_sims < n_par || max_sims > XR_TREE_MAX_SIMS)
+        return fail(XR_ERR_RANGE, "%s: max_sims %d outside n_par %d..%d", fn, max_sims, n_par, XR_TREE_MAX_SIMS);
+    if (node_cap < 1) return fail(XR_ERR_RANGE, "%s: node_cap %d < 1", fn, node_cap);
+    if (k_cap < b->k_max) return fail(XR_ERR_RANGE, "%s: k_cap %d < k_max %d", fn, k_cap, b->k_max);
+    if (const int32_t rc = lds_field_check(b, fn)) return rc;
+    const int64_t tasks = (int64_t)rows * n_par;
+    if (tasks >= ((int64_t)1 << 31)) return fail(XR_ERR_RANGE, "%s: rows x n_par does not fit 31 bits", fn);
+    if (!xr_lookahead_occupancy || !xr_launch_peek || !xr_launch_tree_eval_open || !xr_launch_tree_eval_select || !xr_launch_tree_eval_backup)
+        return fail(XR_ERR_STATE, "%s: evaluated tree search kernels not linked", fn);
+    if (k_cap < 1) k_cap = 1;
+    if ((double)rows * ((double)node_cap * sizeof(XrTreeNode) + (double)n_par * (4.0 * k_cap + 16.0) + 8.0 * k_cap + 8.0 * b->legal_words + 44.0 + 160.0) > 1e15)
+        return fail(XR_ERR_NOMEM, "%s: %d rows x %d nodes do not fit any device", fn, rows, node_cap);
+    Carver c;          // nine arrays in one allocation, each starting on a 16-byte boundary
+    const size_t R = (size_t)rows, P = (size_t)n_par, K = (size_t)k_cap;
+    const size_t o_nodes = c.take(R * (size_t)node_cap * sizeof(XrTreeNode)), o_rs = c.take(R * sizeof(XrTreeRow));
+    const size_t o_prefix = c.take(R * P * K * sizeof(int32_t)), o_ret = c.take(R * P * sizeof(double)), o_leaf = c.take(R * P * 2 * sizeof(int32_t));
+    const size_t o_best = c.take(R * K * sizeof(int32_t)), o_legal = c.take(R * (size_t)b->legal_words * sizeof(uint64_t));
+    const size_t o_nlegal = c.take(R * sizeof(int32_t)), o_prior = c.take(R * K * sizeof(float));
+    XR_HIP(hipSetDevice(b->cfg.device));
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const XrRouteVariant v = route_variant(b);
+    xr_batch::LookPool& lp = b->look[group + 1];
+    if (const int32_t rc = shadow_pool(b, lp, v, st, fn, true)) return rc;          // (the peek launches of the session play there)
+    xr_batch::EvalPool& ep = b->eval[group + 1];
+    ep.open = false; ep.pending = false;          // the last session ends here, whatever becomes of this call
+    if (ep.mem.n < c.off && ep.mem.alloc(c.off) != hipSuccess) {
+        ep.mem.release();
+        return fail(XR_ERR_NOMEM, "%s: hipMalloc of %zu bytes of trees failed", fn, c.off);
+    }
+    xr_batch::TreeTable* tab = nullptr;
+    for (auto& t : ep.tables)
+        if (t->c_init == c_init && t->c_base == c_base && t->host.size() == (size_t)max_sims + 1) tab = t.get();
+    if (!tab) {
+        std::unique_ptr<xr_batch::TreeTable> t(new (std::nothrow) xr_batch::TreeTable);
+        if (!t) return fail(XR_ERR_NOMEM, "%s: no host memory for the exploration table", fn);
+        t->c_init = c_init; t->c_base = c_base;
+        t->host.resize((size_t)max_sims + 1);
+        tree_table_fill(c_init, c_base, 0, max_sims, t->host.data());
+        if (t->dev.alloc(t->host.size()) != hipSuccess) return fail(XR_ERR_NOMEM, "%s: hipMalloc of the exploration table failed", fn);
+        XR_HIP(hipMemcpyAsync(t->dev.p, t->host.data(), t->host.size() * sizeof(double), hipMemcpyHostToDevice, st));
+        tab = t.get();          // (the host copy stays: the asynchronous upload reads it)
+        ep.tables.push_back(std::move(t));
+    }
+    uint8_t* const m = ep.mem.p;
+    XrTreeEvalDev d{};
+    d.nodes = reinterpret_cast<XrTreeNode*>(m + o_nodes); d.rs = reinterpret_cast<XrTreeRow*>(m + o_rs);
+    d.prefix = reinterpret_cast<int32_t*>(m + o_prefix); d.ret = reinterpret_cast<double*>(m + o_ret);
+    d.leaf = reinterpret_cast<int32_t*>(m + o_leaf); d.best_order = reinterpret_cast<int32_t*>(m + o_best);
+    d.legal = reinterpret_cast<uint64_t*>(m + o_legal); d.nlegal = reinterpret_cast<int32_t*>(m + o_nlegal);
+    d.prior = reinterpret_cast<float*>(m + o_prior);
+    d.E = tab->dev.p;
+    d.node_cap = node_cap; d.n_par = n_par; d.k_cap = k_cap; d.e_max = max_sims; d.env_lo = lo; d.legal_words = b->legal_words;
+    d.has_prior = root_prior_dev ? 1 : 0;
+    XR_HIP(xr_launch_tree_eval_open(&b->dev, &d, root_prior_dev, rows, st));
+    ep.d = d; ep.rows = rows; ep.lo = lo; ep.max_sims = max_sims; ep.sims = 0; ep.open = true;
+    return XR_OK;
+}
+
+int32_t xr_batch_tree_leaves(xr_batch* b, int32_t group, uint8_t* rows_out_dev, int64_t row_bytes, int32_t region_base, int32_t* out_dev,
+                             double* return_out_dev, int32_t* paths_out_dev, int32_t* leaf_out_dev, void* stream) {
+    const char* fn = "xr_batch_tree_leaves";
+    if (!b || !rows_out_dev || !out_dev) return fail(XR_ERR_INVALID, "%s: null argument", fn);
+    if ((reinterpret_cast<uintptr_t>(rows_out_dev) & 7) || row_bytes % 8 != 0)
+        return fail(XR_ERR_INVALID, "%s: rows_out_dev %p / row_bytes %lld are not 8-byte aligned", fn, (void*)rows_out_dev, (long long)row_bytes);
+    if (!b->loaded) return fail(XR_ERR_STATE, "%s: load regions first", fn);
+    int lo, rows;
+    if (const int32_t rc = group_rows(b, group, fn, lo, rows)) return rc;
+    const int64_t need = 16 + 8 * ((int64_t)b->legal_words + ((b->n_max + 63) >> 6));
+    if (row_bytes < need) return fail(XR_ERR_RANGE, "%s: row_bytes %lld < %lld (xr_batch_state_row_bytes)", fn, (long long)row_bytes, (long long)need);
+    if (const int32_t rc = lds_field_check(b, fn)) return rc;
+    xr_batch::EvalPool& ep = b->eval[group + 1];
+    if (!ep.open || ep.rows != rows || ep.lo != lo || ep.d.legal_words != b->legal_words)
+        return fail(XR_ERR_STATE, "%s: no open session of this caller (xr_batch_tree_open first)", fn);
+    if (ep.pending) return fail(XR_ERR_STATE, "%s: the last wave's leaves still wait for xr_batch_tree_backup", fn);
+    if (ep.sims + ep.d.n_par > ep.max_sims)
+        return fail(XR_ERR_RANGE, "%s: %d simulations so far, a wave of %d would pass max_sims %d", fn, ep.sims, ep.d.n_par, ep.max_sims);
+    if (!xr_lookahead_occupancy || !xr_launch_peek || !xr_launch_tree_eval_select) return fail(XR_ERR_STATE, "%s: evaluated tree search kernels not linked", fn);
+    XR_HIP(hipSetDevice(b->cfg.device));
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const XrRouteVariant v = route_variant(b);
+    xr_batch::LookPool& lp = b->look[group + 1];
+    if (const int32_t rc = shadow_pool(b, lp, v, st, fn, true)) return rc;
+    const XrBatchDev sh = shadow_view(b, lp);
+    const int64_t tasks = (int64_t)rows * ep.d.n_par;
+    XR_HIP(xr_launch_tree_eval_select(&ep.d, paths_out_dev, leaf_out_dev, rows, st));
+    ep.pending = true;          // (the paths carry pending visits from here on: only a backup, or a new open, clears them)
+    const Banks ctr = flip_banks(lp.roll_ctr.p, lp.roll_bank, 1);
+    const int blocks = (int)std::min<int64_t>(b->look_grid, tasks);
+    XR_HIP(xr_launch_peek(&b->dev, &sh, lo, (int)tasks, ep.d.n_par, ep.d.prefix, ep.d.k_cap, 0, ctr.cur, ctr.next, rows_out_dev, row_bytes, region_base, out_dev,
+                          ep.d.ret, nullptr, nullptr, 0, v, blocks, st));
+    if (return_out_dev) XR_HIP(hipMemcpyAsync(return_out_dev, ep.d.ret, (size_t)tasks * sizeof(double), hipMemcpyDeviceToDevice, st));
+    return XR_OK;
+}
+
+int32_t xr_batch_tree_backup(xr_batch* b, int32_t group, const double* value_dev, const float* leaf_prior_dev, int32_t* visits_out_dev,
+                             double* value_out_dev, int32_t* info_out_dev, int32_t* best_order_out_dev, double* best_return_out_dev,
+                             double* returns_out_dev, void* stream) {
+    const char* fn = "xr_batch_tree_backup";
+    if (!b || !value_dev || !visits_out_dev || !value_out_dev || !info_out_dev) return fail(XR_ERR_INVALID, "%s: null argument", fn);
+    if (!b->loaded) return fail(XR_ERR_STATE, "%s: load regions first", fn);
+    int lo, rows;
+    if (const int32_t rc = group_rows(b, group, fn, lo, rows)) return rc;
+    xr_batch::EvalPool& ep = b->eval[group + 1];
+    if (!ep.open || !ep.pending || ep.rows != rows || ep.lo != lo)
+        return fail(XR_ERR_STATE, "%s: no pending leaves of this caller (xr_batch_tree_leaves first)", fn);
+    if (!xr_launch_tree_eval_backup) return fail(XR_ERR_STATE, "%s: evaluated tree search kernels not linked", fn);
+    XR_HIP(hipSetDevice(b->cfg.device));
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    XR_HIP(xr_launch_tree_eval_backup(&ep.d, value_dev, leaf_prior_dev, ep.sims + ep.d.n_par, visits_out_dev, value_out_dev, info_out_dev, best_order_out_dev,
+                                      best_return_out_dev, returns_out_dev, rows, st));
+    ep.sims += ep.d.n_par;
+    ep.pending = false;
+    return XR_OK;
 }
 
 // ---- branch ------------------------------------------------------------------------------------------------------------------------

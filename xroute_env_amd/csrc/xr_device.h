@@ -262,6 +262,22 @@ struct XrTreeKeepDev {
     int32_t pad;
 };
 
+// Evaluated tree search (xr_tree_eval.h, xr_batch_tree_open / _leaves / _backup): the pool of a session, passed by value to its three
+// kernels.  Everything here is the pool's own memory: the env's rows are read by the open kernel alone
+struct XrTreeEvalDev {
+    XrTreeNode* nodes;       // [rows][node_cap]
+    XrTreeRow* rs;           // [rows]
+    int32_t* prefix;         // [rows][n_par][k_cap] the paths of the current wave, each ended by 0: the peek launch's prefix
+    double* ret;             // [rows][n_par] the peek launch's line returns
+    int32_t* leaf;           // [rows][n_par][2] {node, flags} of the current wave
+    int32_t* best_order;     // [rows][k_cap] the best terminal line so far
+    uint64_t* legal;         // [rows][legal_words] the env's legal words at the open call
+    int32_t* nlegal;         // [rows] and its nlegal
+    float* prior;            // [rows][k_cap] the open call's row prior (zeros without one)
+    const double* E;         // [e_max + 1] exploration table
+    int32_t node_cap, n_par, k_cap, e_max, env_lo, legal_words, has_prior, pad;
+};
+
 // Which instantiation of the route / order / step-queue kernels a launch takes, and its launch shape (xr_kernels.hip maps
 // (lds_dist, zch) to <LDS_DIST, ZCH> in one place: xr_with_variant)
 struct XrRouteVariant {
@@ -324,6 +340,12 @@ hipError_t xr_launch_tree_select(const XrBatchDev* src, const XrTreeDev* t, int 
 hipError_t xr_launch_tree_backup(const XrBatchDev* src, const XrTreeDev* t, int rows, int wave, int last, hipStream_t st) __attribute__((weak));
 // kept trees (xr_tree_keep.h).  Weak for the same reason: xr_batch_tree_search_keep answers XR_ERR_STATE where it is not linked
 hipError_t xr_launch_tree_keep_begin(const XrBatchDev* src, const XrTreeDev* t, const XrTreeKeepDev* k, int rows, hipStream_t st) __attribute__((weak));
+// evaluated tree search (xr_tree_eval.h).  Weak for the same reason: xr_batch_tree_open answers XR_ERR_STATE where they are not linked
+hipError_t xr_launch_tree_eval_open(const XrBatchDev* src, const XrTreeEvalDev* t, const float* root_prior, int rows, hipStream_t st) __attribute__((weak));
+hipError_t xr_launch_tree_eval_select(const XrTreeEvalDev* t, int32_t* paths_out, int32_t* leaf_out, int rows, hipStream_t st) __attribute__((weak));
+hipError_t xr_launch_tree_eval_backup(const XrTreeEvalDev* t, const double* value, const float* leaf_prior, int sims, int32_t* visits_out, double* value_out,
+                                      int32_t* info_out, int32_t* best_order_out, double* best_return_out, double* returns_out, int rows, hipStream_t st)
+    __attribute__((weak));
 hipError_t xr_launch_guide_masks(const XrBatchDev* b, uint8_t* masks, int k_max, hipStream_t st);
 hipError_t xr_launch_ingest_state(const XrBatchDev* b, const int16_t* owner_in, const uint64_t* legal_in, const int32_t* cum_in, hipStream_t st);
 hipError_t xr_launch_pack_state(const XrBatchDev* b, uint8_t* rows, int64_t row_bytes, int region_base, hipStream_t st);

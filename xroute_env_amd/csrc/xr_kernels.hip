@@ -16,6 +16,7 @@
 //   xr_peek_kernel               (xr_peek.h) the state after a line of play as a packed state row: the rollout's loops, then xr_pack_state_kernel's packing
 //   xr_branch_kernel<0 / 1>      (xr_branch.h) env slots take other slots' state: parents of overwritten parents to staging, then every moved slot
 //   xr_tree_keep_begin_kernel      (xr_tree_keep.h) the first kernel of a search that continues from the played net's subtree
+//   xr_tree_eval_open / select / backup_kernel   (xr_tree_eval.h) the search whose leaves the caller's evaluator values
 //   xr_tree_reset / select / backup_kernel   (xr_tree.h) pUCT over net orderings with the tree in device memory, one wavefront per row
 //   xr_random_action_kernel
 //   xr_weighted_action_kernel    (xr_weighted.h) XR-Pick v1: a legal net drawn in proportion to caller-supplied integer weights, one wave per env
@@ -2205,6 +2206,7 @@ __global__ void __launch_bounds__(256) xr_expand_state_kernel(XrBatchDev b, cons
 #include "xr_weighted.h"
 #include "xr_tree.h"
 #include "xr_tree_keep.h"
+#include "xr_tree_eval.h"
 #include "xr_branch.h"
 
 // ------------------------------------------------------------------------------------------------
@@ -2412,6 +2414,25 @@ hipError_t xr_launch_tree_backup(const XrBatchDev* src, const XrTreeDev* t, int 
 // kept trees (xr_tree_keep.h): the first kernel of xr_batch_tree_search_keep, one wavefront per row
 hipError_t xr_launch_tree_keep_begin(const XrBatchDev* src, const XrTreeDev* t, const XrTreeKeepDev* k, int rows, hipStream_t st) {
     hipLaunchKernelGGL(xr_tree_keep_begin_kernel, dim3(rows), dim3(64), 0, st, *src, *t, *k);
+    return hipGetLastError();
+}
+
+// evaluated tree search (xr_tree_eval.h): one wavefront per row.  select's dynamic LDS is the plain search's
+hipError_t xr_launch_tree_eval_open(const XrBatchDev* src, const XrTreeEvalDev* t, const float* root_prior, int rows, hipStream_t st) {
+    hipLaunchKernelGGL(xr_tree_eval_open_kernel, dim3(rows), dim3(64), 0, st, *src, *t, root_prior);
+    return hipGetLastError();
+}
+
+hipError_t xr_launch_tree_eval_select(const XrTreeEvalDev* t, int32_t* paths_out, int32_t* leaf_out, int rows, hipStream_t st) {
+    const size_t lds = (size_t)t->legal_words * sizeof(uint64_t) + (2 * (size_t)t->k_cap + 1) * sizeof(int32_t);
+    hipLaunchKernelGGL(xr_tree_eval_select_kernel, dim3(rows), dim3(64), lds, st, *t, paths_out, leaf_out);
+    return hipGetLastError();
+}
+
+hipError_t xr_launch_tree_eval_backup(const XrTreeEvalDev* t, const double* value, const float* leaf_prior, int sims, int32_t* visits_out, double* value_out,
+                                      int32_t* info_out, int32_t* best_order_out, double* best_return_out, double* returns_out, int rows, hipStream_t st) {
+    hipLaunchKernelGGL(xr_tree_eval_backup_kernel, dim3(rows), dim3(64), 0, st, *t, value, leaf_prior, sims, visits_out, value_out, info_out, best_order_out,
+                       best_return_out, returns_out);
     return hipGetLastError();
 }
 

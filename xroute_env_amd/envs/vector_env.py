@@ -297,6 +297,37 @@ class XRouteVectorEnv:
             self.group_events[g].record(s)
         return act
 
+    # ---- evaluated tree search (RegionBatch.tree_open / tree_leaves / tree_backup) --------------------------------------------------
+    def _tree_eval_call(self, name: str, group, *args, **kw):
+        """group None: the whole batch, after every group's outstanding work.  A group: on that group's stream, ordered like
+        rollout(group); the group's event then covers it."""
+        if group is None:
+            self._join_groups()
+            return getattr(self.batch, name)(*args, **kw)
+        (g,) = self._groups_of(group)
+        s = self.group_streams[g]
+        s.wait_stream(torch.cuda.current_stream(self.device))
+        with torch.cuda.stream(s):
+            res = getattr(self.batch, name)(*args, group=g, stream=s, **kw)
+            self.group_events[g].record(s)
+        for t in list(args) + list(kw.values()):
+            if isinstance(t, torch.Tensor):
+                t.record_stream(s)
+        return res
+
+    def tree_open(self, n_par: int, max_sims: int, root_prior: Optional[torch.Tensor] = None, node_cap: Optional[int] = None,
+                  c_init: float = 1.25, c_base: float = 19652.0, group: Optional[int] = None) -> None:
+        """RegionBatch.tree_open: start an evaluated-tree session from the state the envs (of the group) are in now."""
+        return self._tree_eval_call("tree_open", group, n_par, max_sims, root_prior, node_cap, c_init, c_base)
+
+    def tree_leaves(self, region_base: int = 0, row_bytes: Optional[int] = None, group: Optional[int] = None):
+        """RegionBatch.tree_leaves's dict {rows, out, ret, paths, leaf}: one wave's leaves as packed state rows."""
+        return self._tree_eval_call("tree_leaves", group, region_base, row_bytes)
+
+    def tree_backup(self, value: torch.Tensor, leaf_prior: Optional[torch.Tensor] = None, group: Optional[int] = None):
+        """RegionBatch.tree_backup's dict {visits, value, info, best_order, best_return, returns}: the evaluator's values go into the tree."""
+        return self._tree_eval_call("tree_backup", group, value, leaf_prior)
+
     @staticmethod
     def _most_visited(res) -> torch.Tensor:
         visits, value = res["visits"], res["value"]
