@@ -285,7 +285,10 @@ int32_t xr_batch_step_observe_inplace(xr_batch* b, const int32_t* actions_dev, f
  *                            of 4·N·(2+7K).
  *   xr_batch_net_planes    = the 7 planes [7, Z, Y, X] of n_pairs (region index, 1-based net id) pairs, pair i at
  *                            out_dev + i*pair_stride (floats, pair_stride >= 7*n_max) — byte-identical to planes 2+7i..8+7i
- *                            of xr_batch_observation for an env playing that region with that net at rank i. */
+ *                            of xr_batch_observation for an env playing that region with that net at rank i.  A net id that
+ *                            names no net of the region (<= 0, > n_nets) gives seven planes of zeros.  A pair whose region index
+ *                            is outside the table (< 0, >= n_regions) is passed over: its row of out_dev is NOT written, the
+ *                            other pairs are.  Of a pair's row only the first 7*N floats (N = nodes of ITS region) are written. */
 int32_t xr_batch_step_compact(xr_batch* b, const int32_t* actions_dev, float* head_out_dev, int64_t head_stride,
                               void* stream);
 int32_t xr_batch_net_planes(xr_batch* b, const int32_t* pair_region_dev, const int32_t* pair_net_dev, int32_t n_pairs,
@@ -301,6 +304,10 @@ int32_t xr_batch_net_planes(xr_batch* b, const int32_t* pair_region_dev, const i
  *                               int32 region + region_base | int32 nlegal | int32 legal_words | int32 occ_words |
  *                               uint64 legal[legal_words] | uint64 occ[occ_words]  (bit f%64 of word f/64 = node f, flat observation order)
  *                             region_base: what turns this batch's local region index into an index of the learner's region table.
+ *                             occ_words is ceil(n_max / 64) for every slot of the batch; bits at and beyond the N nodes of the slot's own
+ *                             region are zero, whatever the owner row holds behind N.  row_bytes may exceed xr_batch_state_row_bytes
+ *                             (ranks agree on the maximum): the bytes of a row beyond 16 + 8·(legal_words + occ_words) are NEVER
+ *                             written — they keep what the caller put there, and xr_batch_expand_state never reads them.
  *   xr_batch_expand_state     (learner side; `b` supplies the region table: it must hold every region the rows name) n_rows rows -> the
  *                             fp32 head rows xr_batch_step_compact writes for those envs, byte for byte (planes 0..1 at
  *                             head_out_dev + i*head_stride, each env in its own region's layout), plus nlegal / region of every row as

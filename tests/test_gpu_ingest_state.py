@@ -1,7 +1,9 @@
 """xr_batch_ingest_state (ABI 9): the client half of the reference's Game.step WITHOUT the route — a new state of every env slot, as an external
 simulator's Request carries it, becomes the batch's state (reference baseline/baseline_utils.py:420-438: metric deltas = new - previous cumulative
 values, done = no nets left; reward baseline/DQN/train_DQN.py:98-99) — BASELINE config 2 ("grid-build + reward only").  The states come from a twin
-batch that routes; what the ingesting batch then reports and the observation it builds are compared with the oracle."""
+batch that routes; the deltas, reward, done flag and nets-left count the ingesting batch then reports and the observation it builds are compared with
+the oracle, its legal SETS with the twin's (kernel against kernel).  States no router produces, and the mask cut at every word boundary, are in
+tests/test_gpu_state_rows.py."""
 import numpy as np
 import pytest
 import torch

@@ -1,7 +1,10 @@
 """Compact state for a central learner (BASELINE config 4): xr_batch_pack_state -> (one all_gather) ->
 xr_batch_expand_state must reproduce, byte for byte, the two observation planes xr_batch_step_compact writes — plane 0
 (obstacle: blockage or used, reference baseline/build_3Dgrid.py:19-36,94-103) and plane 1 (the remaining nets' ids ascending at
-flat positions 0..K-1, :144-161) — and the oracle's build_3Dgrid restatement of the same envs."""
+flat positions 0..K-1, :144-161).  Only the first test also holds the expanded planes against the oracle's build_3Dgrid restatement of the
+same envs, at one grid shape (12x10x5); every other comparison here is kernel against kernel (expand(pack) against the head the compact step
+wrote).  What a packed row must CONTAIN, and every shape class of the kernels' index arithmetic, is checked against a plain reference in
+tests/test_gpu_state_rows.py."""
 import os
 
 import numpy as np
