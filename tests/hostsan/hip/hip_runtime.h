@@ -25,6 +25,11 @@ struct hipDeviceProp_t { int multiProcessorCount; size_t sharedMemPerBlock; size
 extern "C" int64_t xr_stub_alloc_limit;
 extern "C" int64_t xr_stub_alloc_live;     // bytes currently allocated (leak check of the error paths)
 extern "C" void (*xr_stub_malloc_hook)(size_t bytes);     // optional (null: off): sees the byte count of every hipMalloc, refused ones included
+// optional (null: off), for a registry of the live allocations (search_trace.cpp names a device pointer by the allocation that holds it):
+// every allocation made (freed = 0) and every one freed (freed = 1)
+extern "C" void (*xr_stub_alloc_hook)(void* p, size_t bytes, int freed);
+// optional (null: off): every asynchronous fill and copy — its name, destination, hipMemcpyKind (-1 for a fill) and byte count
+extern "C" void (*xr_stub_async_hook)(const char* what, const void* dst, int kind, size_t bytes);
 
 static inline const char* hipGetErrorString(hipError_t e) { return e == hipSuccess ? "success" : e == hipErrorOutOfMemory ? "out of memory (stub)" : "invalid value (stub)"; }
 static inline hipError_t hipGetDeviceCount(int* n) { *n = 1; return hipSuccess; }
@@ -39,21 +44,32 @@ static inline hipError_t hipMalloc(void** p, size_t n) {
     *reinterpret_cast<uint64_t*>(q) = n;
     xr_stub_alloc_live += (int64_t)n;
     *p = q + 16;
+    if (xr_stub_alloc_hook) xr_stub_alloc_hook(*p, n, 0);
     return hipSuccess;
 }
 static inline hipError_t hipFree(void* p) {
     if (!p) return hipSuccess;
     uint8_t* q = static_cast<uint8_t*>(p) - 16;
+    if (xr_stub_alloc_hook) xr_stub_alloc_hook(p, (size_t)*reinterpret_cast<uint64_t*>(q), 1);
     xr_stub_alloc_live -= (int64_t)*reinterpret_cast<uint64_t*>(q);
     free(q);
     return hipSuccess;
 }
 static inline hipError_t hipMemcpy(void* d, const void* s, size_t n, hipMemcpyKind) { if (n) memcpy(d, s, n); return hipSuccess; }
-static inline hipError_t hipMemcpyAsync(void* d, const void* s, size_t n, hipMemcpyKind, hipStream_t = nullptr) { if (n) memmove(d, s, n); return hipSuccess; }
+static inline hipError_t hipMemcpyAsync(void* d, const void* s, size_t n, hipMemcpyKind k, hipStream_t = nullptr) {
+    if (xr_stub_async_hook) xr_stub_async_hook("hipMemcpyAsync", d, (int)k, n);
+    if (n) memmove(d, s, n);
+    return hipSuccess;
+}
 static inline hipError_t hipMemset(void* d, int v, size_t n) { if (n) memset(d, v, n); return hipSuccess; }
-static inline hipError_t hipMemsetAsync(void* d, int v, size_t n, hipStream_t = nullptr) { if (n) memset(d, v, n); return hipSuccess; }
+static inline hipError_t hipMemsetAsync(void* d, int v, size_t n, hipStream_t = nullptr) {
+    if (xr_stub_async_hook) xr_stub_async_hook("hipMemsetAsync", d, -1, n);
+    if (n) memset(d, v, n);
+    return hipSuccess;
+}
 typedef void* hipDeviceptr_t;
 static inline hipError_t hipMemsetD32Async(hipDeviceptr_t d, int v, size_t count, hipStream_t = nullptr) {
+    if (xr_stub_async_hook) xr_stub_async_hook("hipMemsetD32Async", d, -1, count * 4);
     uint32_t* q = static_cast<uint32_t*>(d);
     for (size_t i = 0; i < count; i++) q[i] = (uint32_t)v;
     return hipSuccess;

@@ -12,6 +12,8 @@ int64_t xr_stub_launches = 0;
 // variant it was handed (null where the launcher takes none) — load_trace.cpp prints what reaches a launch through it
 void (*xr_stub_launch_hook)(const char* name, const XrBatchDev* b, const XrRouteVariant* v) = nullptr;
 void (*xr_stub_malloc_hook)(size_t bytes) = nullptr;      // optional: the byte count of every hipMalloc (hip/hip_runtime.h)
+void (*xr_stub_alloc_hook)(void* p, size_t bytes, int freed) = nullptr;                                   // optional, both: hip/hip_runtime.h
+void (*xr_stub_async_hook)(const char* what, const void* dst, int kind, size_t bytes) = nullptr;
 }
 
 static hipError_t launched(const char* name, const XrBatchDev* b = nullptr, const XrRouteVariant* v = nullptr) {

@@ -7,57 +7,12 @@
 // allocating or launching: the stand-in's live-allocation and launch counters must not move on any call of this program.  The table
 // function is checked against its formula.  Runs as a program of its own (no preload); ends with TREE_ARGS_OK, no leak and nothing on
 // stderr.
-#include <hip/hip_runtime.h>
+#include "../hostsan/args_common.h"
 
 #include <cmath>
-#include <cstdio>
-#include <cstring>
 #include <limits>
-#include <string>
-#include <vector>
-
-#include "../../include/xroute_hip.h"
-
-extern "C" int64_t xr_stub_launches;
 
 namespace {
-
-struct Lcg {
-    uint64_t s;
-    uint32_t next() { s = s * 6364136223846793005ULL + 1442695040888963407ULL; return (uint32_t)(s >> 33); }
-    int below(int n) { return (int)(next() % (uint32_t)n); }
-    int between(int lo, int hi) { return lo + below(hi - lo + 1); }
-};
-
-int g_failures = 0, g_calls = 0;
-
-void check(bool ok, const std::string& what) {
-    if (ok) return;
-    printf("FAILURE: %s\n", what.c_str());
-    g_failures++;
-}
-
-// a small region: X x Y x 2 nodes, K nets of two access points each
-struct Reg {
-    int X, Y, Z = 2, K;
-    std::vector<int32_t> xs, ys;
-    std::vector<uint8_t> dir{0, 1};
-    std::vector<uint32_t> nodes;
-    Reg(int X_, int Y_, int K_) : X(X_), Y(Y_), K(K_) {
-        for (int i = 0; i < X; i++) xs.push_back(1000 + 400 * i);
-        for (int i = 0; i < Y; i++) ys.push_back(-500 + 380 * i);
-        nodes.assign((size_t)X * Y * Z, XR_TYPE_NORMAL);
-        for (int n = 1; n <= K; n++)
-            for (int p = 1; p <= 2; p++) nodes[(size_t)((n * 7 + p * 3) % (X * Y)) * Z + (p - 1)] = XR_TYPE_ACCESS | ((uint32_t)n << 3) | ((uint32_t)p << 17);
-    }
-    xr_region_desc desc() const {
-        xr_region_desc d{};
-        d.dim_x = X; d.dim_y = Y; d.dim_z = Z;
-        d.xs_host = xs.data(); d.ys_host = ys.data(); d.layer_dir_host = dir.data(); d.nodes_host = nodes.data();
-        d.n_nets = K;
-        return d;
-    }
-};
 
 const double kNan = std::numeric_limits<double>::quiet_NaN(), kInf = std::numeric_limits<double>::infinity();
 
@@ -66,8 +21,6 @@ struct Args {
     double c_init = 1.25, c_base = 19652.0;
     bool prior = false, visits = true, value = true, info = true, best = true, trace = false;
 };
-
-struct Expect { int32_t code; const char* msg; };
 
 // what include/xroute_hip.h documents, in the order the entry point checks
 Expect expected(const Args& a, bool loaded, int n_groups, int rows, int k_max, bool scratch_form) {
@@ -107,36 +60,11 @@ void call(xr_batch* b, const Args& a, const Expect& want, const std::string& wha
     check(xr_stub_alloc_live == live && xr_stub_launches == launches, std::string("allocated or launched: ") + buf);
 }
 
-struct Batch {
-    xr_batch* h = nullptr;
-    int n_envs = 0, n_groups = 1, k_max = 0;
-    bool scratch_form = false;
-    std::vector<int32_t> bounds;
-    int rows(int g) const { return g < 0 ? n_envs : bounds[g + 1] - bounds[g]; }
-};
-
 Batch make(const char* name, int n_envs, const std::vector<const Reg*>& regs, int force_scratch, int per_region, const std::vector<int32_t>& bounds) {
-    Batch B;
-    xr_config c;
-    xr_config_default(&c);
-    c.n_envs = n_envs; c.force_scratch_field = force_scratch; c.stream_per_region = per_region;
-    check(xr_batch_create(&c, &B.h) == XR_OK, std::string(name) + ": create");
-    Args a;
-    call(B.h, a, expected(a, false, 1, n_envs, 0, false), std::string(name) + " before the load");
-    std::vector<xr_region_desc> d;
-    for (const Reg* r : regs) d.push_back(r->desc());
-    const int32_t rc = xr_batch_load_regions(B.h, d.data(), (int32_t)d.size(), nullptr);
-    check(rc == XR_OK, std::string(name) + ": load: " + xr_last_error());
-    int32_t s[6] = {0, 0, 0, 0, 0, 0};
-    int64_t stride = 0;
-    check(xr_batch_sizes(B.h, &s[0], &s[1], &s[2], &s[3], &s[4], &s[5], &stride) == XR_OK, "sizes");
-    B.n_envs = n_envs; B.k_max = s[3]; B.scratch_form = force_scratch || per_region;
-    B.bounds = {0, n_envs};
-    if (!bounds.empty()) {
-        check(xr_batch_set_groups(B.h, bounds.data(), (int32_t)bounds.size() - 1) == XR_OK, std::string(name) + ": set_groups: " + xr_last_error());
-        B.bounds = bounds; B.n_groups = (int)bounds.size() - 1;
-    }
-    return B;
+    return make(name, n_envs, regs, force_scratch, per_region, bounds, [&](Batch& B) {
+        Args a;
+        call(B.h, a, expected(a, false, 1, n_envs, 0, false), std::string(name) + " before the load");
+    });
 }
 
 // every refusal once, by name, then randomised arguments
@@ -238,7 +166,5 @@ int main() {
         check(xr_stub_alloc_live == 0, "2^19 slots: no device buffer outlives the batch");
     }
     check(xr_stub_launches > 0, "the loads launched their kernels through the stand-in (the counters are live)");
-    if (g_failures) printf("TREE_ARGS_FAILED %d of %d calls\n", g_failures, g_calls);
-    else printf("TREE_ARGS_OK %d calls\n", g_calls);
-    return g_failures ? 1 : 0;
+    return finish("TREE_ARGS");
 }

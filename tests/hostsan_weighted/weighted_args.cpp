@@ -6,61 +6,15 @@
 // and checks the code AND the message of each.  The stand-in links none of the launchers, so a valid call must answer XR_ERR_STATE
 // ("not linked") after validating, without allocating or launching: the stand-in's live-allocation and launch counters must not move on
 // any call of this program.  Runs as a program of its own (no preload); ends with WEIGHTED_ARGS_OK, no leak and nothing on stderr.
-#include <hip/hip_runtime.h>
+#include "../hostsan/args_common.h"
 
 #include <cmath>
-#include <cstdio>
-#include <cstring>
 #include <limits>
-#include <string>
-#include <vector>
-
-#include "../../include/xroute_hip.h"
-
-extern "C" int64_t xr_stub_launches;
 
 namespace {
 
-struct Lcg {
-    uint64_t s;
-    uint32_t next() { s = s * 6364136223846793005ULL + 1442695040888963407ULL; return (uint32_t)(s >> 33); }
-    int below(int n) { return (int)(next() % (uint32_t)n); }
-    int between(int lo, int hi) { return lo + below(hi - lo + 1); }
-};
-
-int g_failures = 0, g_calls = 0;
-
-void check(bool ok, const std::string& what) {
-    if (ok) return;
-    printf("FAILURE: %s\n", what.c_str());
-    g_failures++;
-}
-
-// a small region: X x Y x 2 nodes, K nets of two access points each
-struct Reg {
-    int X, Y, Z = 2, K;
-    std::vector<int32_t> xs, ys;
-    std::vector<uint8_t> dir{0, 1};
-    std::vector<uint32_t> nodes;
-    Reg(int X_, int Y_, int K_) : X(X_), Y(Y_), K(K_) {
-        for (int i = 0; i < X; i++) xs.push_back(1000 + 400 * i);
-        for (int i = 0; i < Y; i++) ys.push_back(-500 + 380 * i);
-        nodes.assign((size_t)X * Y * Z, XR_TYPE_NORMAL);
-        for (int n = 1; n <= K; n++)
-            for (int p = 1; p <= 2; p++) nodes[(size_t)((n * 7 + p * 3) % (X * Y)) * Z + (p - 1)] = XR_TYPE_ACCESS | ((uint32_t)n << 3) | ((uint32_t)p << 17);
-    }
-    xr_region_desc desc() const {
-        xr_region_desc d{};
-        d.dim_x = X; d.dim_y = Y; d.dim_z = Z;
-        d.xs_host = xs.data(); d.ys_host = ys.data(); d.layer_dir_host = dir.data(); d.nodes_host = nodes.data();
-        d.n_nets = K;
-        return d;
-    }
-};
-
 const double kNan = std::numeric_limits<double>::quiet_NaN(), kInf = std::numeric_limits<double>::infinity();
 
-struct Expect { int32_t code; const char* msg; };
 struct Ctx { bool loaded; int n_groups, rows, k_max; bool scratch_form; };
 
 // stand-ins for the device buffers: never touched (nothing launches), but real memory
@@ -68,15 +22,6 @@ std::vector<int32_t> g_i32a(64), g_i32b(64), g_i32c(64), g_i32d(64), g_weights(6
 std::vector<double> g_f64a(64), g_f64b(8);
 std::vector<uint64_t> g_hash(8);
 std::vector<float> g_prior(64);
-
-void judge(const char* fn, int32_t rc, const Expect& want, const std::string& what, int64_t live, int64_t launches) {
-    g_calls++;
-    const char* msg = xr_last_error();
-    char buf[512];
-    snprintf(buf, sizeof buf, "%s %s -> rc %d \"%s\", expected %d \"...%s...\"", fn, what.c_str(), rc, msg, want.code, want.msg);
-    check(rc == want.code && strstr(msg, fn) && strstr(msg, want.msg), buf);
-    check(xr_stub_alloc_live == live && xr_stub_launches == launches, std::string("allocated or launched: ") + buf);
-}
 
 // ---- xr_batch_weighted_actions ------------------------------------------------------------------------------------------------------
 struct ActArgs {
@@ -94,7 +39,7 @@ void call(xr_batch* b, const ActArgs& a, const Expect& want, const std::string& 
     const int64_t live = xr_stub_alloc_live, launches = xr_stub_launches;
     const int32_t rc = xr_batch_weighted_actions(b, a.group, a.weights ? g_weights.data() : nullptr, a.k_cap, a.actions ? g_i32a.data() : nullptr,
                                                  0x1234567ULL * (uint64_t)(g_calls + 1), nullptr);
-    judge("xr_batch_weighted_actions", rc, want, what + " group " + std::to_string(a.group) + " k_cap " + std::to_string(a.k_cap), live, launches);
+    verdict("xr_batch_weighted_actions", rc, want, what + " group " + std::to_string(a.group) + " k_cap " + std::to_string(a.k_cap), live, launches);
 }
 
 // ---- xr_batch_rollout_weighted ------------------------------------------------------------------------------------------------------
@@ -127,7 +72,7 @@ void call(xr_batch* b, const RollArgs& a, const Expect& want, const std::string&
     char buf[256];
     snprintf(buf, sizeof buf, "%s group %d R %d policy %d prefix %d/%d max_plies %d order %d/%d weights %d/%d", what.c_str(), a.group, a.n_rollouts, a.policy,
              (int)a.prefix, a.prefix_stride, a.max_plies, (int)a.order, a.k_cap, (int)a.weights, a.weights_k_cap);
-    judge("xr_batch_rollout_weighted", rc, want, buf, live, launches);
+    verdict("xr_batch_rollout_weighted", rc, want, buf, live, launches);
 }
 
 // ---- xr_batch_tree_search_weighted --------------------------------------------------------------------------------------------------
@@ -162,49 +107,23 @@ void call(xr_batch* b, const TreeArgs& a, const Expect& want, const std::string&
     char buf[256];
     snprintf(buf, sizeof buf, "%s group %d waves %d par %d cap %d k_cap %d c %g/%g sim_weights %d", what.c_str(), a.group, a.n_waves, a.n_par, a.node_cap, a.k_cap,
              a.c_init, a.c_base, (int)a.sim_weights);
-    judge("xr_batch_tree_search_weighted", rc, want, buf, live, launches);
+    verdict("xr_batch_tree_search_weighted", rc, want, buf, live, launches);
 }
 
-struct Batch {
-    xr_batch* h = nullptr;
-    int n_envs = 0, n_groups = 1, k_max = 0;
-    bool scratch_form = false;
-    std::vector<int32_t> bounds;
-    Ctx ctx(int g) const {
-        const bool in = g >= 0 && g < n_groups;
-        return {true, n_groups, in ? bounds[g + 1] - bounds[g] : n_envs, k_max, scratch_form};
-    }
-};
+Ctx ctx(const Batch& B, int g) { return {true, B.n_groups, B.rows(g), B.k_max, B.scratch_form}; }
 
 Batch make(const char* name, int n_envs, const std::vector<const Reg*>& regs, int force_scratch, int per_region, const std::vector<int32_t>& bounds) {
-    Batch B;
-    xr_config c;
-    xr_config_default(&c);
-    c.n_envs = n_envs; c.force_scratch_field = force_scratch; c.stream_per_region = per_region;
-    check(xr_batch_create(&c, &B.h) == XR_OK, std::string(name) + ": create");
-    const Ctx before{false, 1, n_envs, 0, false};
-    call(B.h, ActArgs{}, expected(ActArgs{}, before), std::string(name) + " before the load");
-    call(B.h, RollArgs{}, expected(RollArgs{}, before), std::string(name) + " before the load");
-    call(B.h, TreeArgs{}, expected(TreeArgs{}, before), std::string(name) + " before the load");
-    std::vector<xr_region_desc> d;
-    for (const Reg* r : regs) d.push_back(r->desc());
-    const int32_t rc = xr_batch_load_regions(B.h, d.data(), (int32_t)d.size(), nullptr);
-    check(rc == XR_OK, std::string(name) + ": load: " + xr_last_error());
-    int32_t s[6] = {0, 0, 0, 0, 0, 0};
-    int64_t stride = 0;
-    check(xr_batch_sizes(B.h, &s[0], &s[1], &s[2], &s[3], &s[4], &s[5], &stride) == XR_OK, "sizes");
-    B.n_envs = n_envs; B.k_max = s[3]; B.scratch_form = force_scratch || per_region;
-    B.bounds = {0, n_envs};
-    if (!bounds.empty()) {
-        check(xr_batch_set_groups(B.h, bounds.data(), (int32_t)bounds.size() - 1) == XR_OK, std::string(name) + ": set_groups: " + xr_last_error());
-        B.bounds = bounds; B.n_groups = (int)bounds.size() - 1;
-    }
-    return B;
+    return make(name, n_envs, regs, force_scratch, per_region, bounds, [&](Batch& B) {
+        const Ctx before{false, 1, n_envs, 0, false};
+        call(B.h, ActArgs{}, expected(ActArgs{}, before), std::string(name) + " before the load");
+        call(B.h, RollArgs{}, expected(RollArgs{}, before), std::string(name) + " before the load");
+        call(B.h, TreeArgs{}, expected(TreeArgs{}, before), std::string(name) + " before the load");
+    });
 }
 
 // every refusal once, by name, then randomised arguments
 void drive(const char* name, Batch& B, Lcg& rng, int random_calls) {
-    auto run = [&](auto a, const char* what) { call(B.h, a, expected(a, B.ctx(a.group)), std::string(name) + " " + what); };
+    auto run = [&](auto a, const char* what) { call(B.h, a, expected(a, ctx(B, a.group)), std::string(name) + " " + what); };
     {
         ActArgs a;
         run(a, "valid, defaults");
@@ -318,7 +237,5 @@ int main() {
         check(xr_stub_alloc_live == 0, std::string(c.name) + ": no device buffer outlives the batch");
     }
     check(xr_stub_launches > 0, "the loads launched their kernels through the stand-in (the counters are live)");
-    if (g_failures) printf("WEIGHTED_ARGS_FAILED %d of %d calls\n", g_failures, g_calls);
-    else printf("WEIGHTED_ARGS_OK %d calls\n", g_calls);
-    return g_failures ? 1 : 0;
+    return finish("WEIGHTED_ARGS");
 }

@@ -56,11 +56,13 @@ def test_peek_null_arguments_without_gpu():
 
 
 def test_product_library_links_the_peek_kernel():
-    """The launcher is weak in csrc/xr_device.h (so that the host-only sanitizer build links): the product library must define it."""
-    assert hasattr(_lib.lib(), "xr_launch_peek")
+    """The line launcher (xr_launch_line, kind XR_LINE_PEEK) is weak in csrc/xr_device.h (so that the host-only sanitizer build links): the
+    product library must define it."""
+    assert hasattr(_lib.lib(), "xr_launch_line")
     dev = open(os.path.join(ROOT, "xroute_env_amd", "csrc", "xr_device.h")).read()
-    decl = dev[dev.index("hipError_t xr_launch_peek("):]
+    decl = dev[dev.index("hipError_t xr_launch_line("):]
     assert "__attribute__((weak))" in decl[:decl.index(";")]
+    assert "XR_LINE_PEEK" in dev[dev.index("enum XrLineKind"):dev.index("struct XrLineLaunch")]
 
 
 def _fake_batch():

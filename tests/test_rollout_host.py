@@ -52,7 +52,7 @@ def test_rollout_null_arguments_without_gpu():
 
 def test_product_library_links_the_rollout_kernel():
     """The launcher is weak in csrc/xr_device.h (so that the host-only sanitizer build links): the product library must define it."""
-    assert hasattr(_lib.lib(), "xr_launch_rollout")
+    assert hasattr(_lib.lib(), "xr_launch_line")          # (the rollout: kind XR_LINE_POLICY of the one line launcher)
 
 
 def test_region_batch_rollout_validates_before_the_library():

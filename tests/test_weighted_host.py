@@ -64,7 +64,9 @@ def test_weighted_null_arguments_without_gpu():
 def test_product_library_links_the_weighted_launchers():
     """The launchers are weak in csrc/xr_device.h (so that the host-only sanitizer build links): the product library must define them."""
     L = _lib.lib()
-    assert hasattr(L, "xr_launch_weighted_actions") and hasattr(L, "xr_launch_rollout_weighted")
+    assert hasattr(L, "xr_launch_weighted_actions") and hasattr(L, "xr_launch_line")          # (the rollout under weights: kind XR_LINE_WEIGHTED)
+    dev = open(os.path.join(ROOT, "xroute_env_amd", "csrc", "xr_device.h")).read()
+    assert "XR_LINE_WEIGHTED" in dev[dev.index("enum XrLineKind"):dev.index("struct XrLineLaunch")]
 
 
 # ---- the twin's properties -------------------------------------------------------------------------------------------------------------

@@ -1499,17 +1499,36 @@ int32_t xr_batch_net_planes(xr_batch* b, const int32_t* pair_region_dev, const i
     return XR_OK;
 }
 
+namespace {
+// bytes of a packed state row: the 16-byte head, the legal words, one bit per node of the largest region in 64-bit words
+int64_t state_row_need(const xr_batch* b) { return 16 + 8 * ((int64_t)b->legal_words + ((b->n_max + 63) >> 6)); }
+
+// The checks of the packed rows a caller hands to xr_batch_peek / xr_batch_tree_leaves.  They sit at two places of the check order, so
+// there are two parts: ROWS_ALIGNED looks at no batch and comes before "load regions first", ROWS_LONG comes after the group check
+enum RowPart { ROWS_ALIGNED, ROWS_LONG };
+int32_t state_row_check(const xr_batch* b, const char* fn, const uint8_t* rows_out, int64_t row_bytes, RowPart part) {
+    if (part == ROWS_ALIGNED) {
+        if ((reinterpret_cast<uintptr_t>(rows_out) & 7) || row_bytes % 8 != 0)
+            return fail(XR_ERR_INVALID, "%s: rows_out_dev %p / row_bytes %lld are not 8-byte aligned", fn, (const void*)rows_out, (long long)row_bytes);
+        return XR_OK;
+    }
+    const int64_t need = state_row_need(b);
+    if (row_bytes < need) return fail(XR_ERR_RANGE, "%s: row_bytes %lld < %lld (xr_batch_state_row_bytes)", fn, (long long)row_bytes, (long long)need);
+    return XR_OK;
+}
+}  // namespace
+
 int32_t xr_batch_state_row_bytes(const xr_batch* b, int64_t* row_bytes) {
     if (!b || !row_bytes) return fail(XR_ERR_INVALID, "xr_batch_state_row_bytes: null argument");
     if (!b->loaded) return fail(XR_ERR_STATE, "xr_batch_state_row_bytes: load regions first");
-    *row_bytes = 16 + 8 * ((int64_t)b->legal_words + ((b->n_max + 63) >> 6));
+    *row_bytes = state_row_need(b);
     return XR_OK;
 }
 
 int32_t xr_batch_pack_state(xr_batch* b, uint8_t* rows_dev, int64_t row_bytes, int32_t region_base, void* stream) {
     if (!b || !rows_dev) return fail(XR_ERR_INVALID, "xr_batch_pack_state: null argument");
     if (!b->loaded) return fail(XR_ERR_STATE, "xr_batch_pack_state: load regions first");
-    const int64_t need = 16 + 8 * ((int64_t)b->legal_words + ((b->n_max + 63) >> 6));
+    const int64_t need = state_row_need(b);
     if (row_bytes < need || row_bytes % 8 != 0 || (reinterpret_cast<uintptr_t>(rows_dev) & 7) != 0 || region_base < 0)
         return fail(XR_ERR_RANGE, "xr_batch_pack_state: row_bytes %lld (need >= %lld, a multiple of 8, 8-byte aligned rows), region_base %d",
                     (long long)row_bytes, (long long)need, region_base);
@@ -1932,6 +1951,43 @@ int32_t shadow_pool(xr_batch* b, xr_batch::LookPool& lp, const XrRouteVariant& v
     }
     return XR_OK;
 }
+
+// What every call that plays in shadow slots starts from once its checks have passed: the caller's slots [lo, lo + rows), the stream, the
+// router variant, the caller's pool and the shadow view of it
+struct ShadowCall {
+    int lo = 0, rows = 0;
+    hipStream_t st = nullptr;
+    XrRouteVariant v{};
+    xr_batch::LookPool* lp = nullptr;
+    XrBatchDev sh{};
+};
+
+// The one prologue: device, stream, variant, the pool of the caller (brought up on its first call; roll_ctr: with the claim counters of
+// the line kernels), the view.  Allocates, so it comes after every check
+int32_t shadow_call(xr_batch* b, int32_t group, int lo, int rows, void* stream, const char* fn, bool roll_ctr, ShadowCall& c) {
+    XR_HIP(hipSetDevice(b->cfg.device));
+    c.lo = lo; c.rows = rows;
+    c.st = static_cast<hipStream_t>(stream);
+    c.v = route_variant(b);
+    c.lp = &b->look[group + 1];
+    if (const int32_t rc = shadow_pool(b, *c.lp, c.v, c.st, fn, roll_ctr)) return rc;
+    c.sh = shadow_view(b, *c.lp);
+    return XR_OK;
+}
+
+// One line launch on the call's pool.  The caller has set l.kind, l.per_row and what is its own; everything the launches share is
+// filled here: the views, the tasks (per_row lines for each of the caller's rows), this launch's claim counter (the banks flip), one
+// workgroup per task up to the grid, and the two "absent means 0" rules — no prefix: stride 0, no order rows: k_cap 0
+hipError_t launch_line(const xr_batch* b, const ShadowCall& c, XrLineLaunch l) {
+    const int64_t tasks = (int64_t)c.rows * l.per_row;
+    const Banks ctr = flip_banks(c.lp->roll_ctr.p, c.lp->roll_bank, 1);
+    l.src = &b->dev; l.shadow = &c.sh; l.env_lo = c.lo; l.n_tasks = (int)tasks;
+    l.ctr = ctr.cur; l.next_ctr = ctr.next;
+    if (!l.prefix) l.prefix_stride = 0;
+    if (!l.order_out) l.k_cap = 0;
+    l.v = c.v; l.blocks = (int)std::min<int64_t>(b->look_grid, tasks);
+    return xr_launch_line(&l, c.st);
+}
 }  // namespace
 
 int32_t xr_batch_lookahead(xr_batch* b, int32_t group, const uint64_t* cand_mask_dev, int32_t* out_dev, int32_t k_cap, double* reward_out_dev,
@@ -1946,17 +2002,13 @@ int32_t xr_batch_lookahead(xr_batch* b, int32_t group, const uint64_t* cand_mask
         return fail(XR_ERR_RANGE, "xr_batch_lookahead: n_envs x k_max (or rows x k_cap) does not fit 31 bits");
     if (!xr_lookahead_occupancy || !xr_launch_lookahead_plan || !xr_launch_lookahead)
         return fail(XR_ERR_STATE, "xr_batch_lookahead: lookahead kernels not linked");
-    XR_HIP(hipSetDevice(b->cfg.device));
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    const XrRouteVariant v = route_variant(b);
-    xr_batch::LookPool& lp = b->look[group + 1];
-    if (const int32_t rc = shadow_pool(b, lp, v, st, "xr_batch_lookahead", false)) return rc;
-    const XrBatchDev sh = shadow_view(b, lp);
-    const Banks ctr = flip_banks(lp.ctr.p, lp.bank, 2);
-    XR_HIP(xr_launch_lookahead_plan(&b->dev, lo, rows, cand_mask_dev, out_dev, reward_out_dev, k_cap, b->k_max, lp.tasks.p, ctr.cur, ctr.next, st));
+    ShadowCall c;
+    if (const int32_t rc = shadow_call(b, group, lo, rows, stream, "xr_batch_lookahead", false, c)) return rc;
+    const Banks ctr = flip_banks(c.lp->ctr.p, c.lp->bank, 2);          // its own banks, two counters wide: {tasks listed, next task}
+    XR_HIP(xr_launch_lookahead_plan(&b->dev, lo, rows, cand_mask_dev, out_dev, reward_out_dev, k_cap, b->k_max, c.lp->tasks.p, ctr.cur, ctr.next, c.st));
     if (b->k_max < 1) return XR_OK;          // (no region has a net: the fill is the whole answer)
     const int blocks = (int)std::min<int64_t>(b->look_grid, (int64_t)rows * b->k_max);
-    XR_HIP(xr_launch_lookahead(&b->dev, &sh, lo, lp.tasks.p, ctr.cur, out_dev, reward_out_dev, k_cap, b->k_max, v, blocks, st));
+    XR_HIP(xr_launch_lookahead(&b->dev, &c.sh, lo, c.lp->tasks.p, ctr.cur, out_dev, reward_out_dev, k_cap, b->k_max, c.v, blocks, c.st));
     return XR_OK;
 }
 
@@ -1983,22 +2035,16 @@ int32_t rollout_impl(const char* fn, bool weighted, xr_batch* b, int32_t group, 
     if (const int32_t rc = lds_field_check(b, fn)) return rc;
     const int64_t tasks = (int64_t)rows * n_rollouts;
     if (tasks >= ((int64_t)1 << 31)) return fail(XR_ERR_RANGE, "%s: rows x n_rollouts does not fit 31 bits", fn);
-    if (!xr_lookahead_occupancy || !xr_launch_rollout || (by_weights && !xr_launch_rollout_weighted)) return fail(XR_ERR_STATE, "%s: rollout kernels not linked", fn);
-    XR_HIP(hipSetDevice(b->cfg.device));
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    const XrRouteVariant v = route_variant(b);
-    xr_batch::LookPool& lp = b->look[group + 1];
-    if (const int32_t rc = shadow_pool(b, lp, v, st, fn, true)) return rc;
-    const XrBatchDev sh = shadow_view(b, lp);
-    const Banks ctr = flip_banks(lp.roll_ctr.p, lp.roll_bank, 1);
-    const int blocks = (int)std::min<int64_t>(b->look_grid, tasks);
-    if (by_weights) {
-        XR_HIP(xr_launch_rollout_weighted(&b->dev, &sh, lo, (int)tasks, n_rollouts, seed, prefix_dev, prefix_dev ? prefix_stride : 0, max_plies, ctr.cur, ctr.next,
-                                          out_dev, return_out_dev, hash_out_dev, order_out_dev, order_out_dev ? k_cap : 0, weights_dev, weights_k_cap, v, blocks, st));
-        return XR_OK;
-    }
-    XR_HIP(xr_launch_rollout(&b->dev, &sh, lo, (int)tasks, n_rollouts, policy, seed, prefix_dev, prefix_dev ? prefix_stride : 0, max_plies, ctr.cur, ctr.next,
-                             out_dev, return_out_dev, hash_out_dev, order_out_dev, order_out_dev ? k_cap : 0, v, blocks, st));
+    if (!xr_lookahead_occupancy || !xr_launch_line) return fail(XR_ERR_STATE, "%s: rollout kernels not linked", fn);
+    ShadowCall c;
+    if (const int32_t rc = shadow_call(b, group, lo, rows, stream, fn, true, c)) return rc;
+    XrLineLaunch l{};
+    l.kind = by_weights ? XR_LINE_WEIGHTED : XR_LINE_POLICY; l.per_row = n_rollouts;
+    l.policy = policy; l.seed = seed;
+    l.prefix = prefix_dev; l.prefix_stride = prefix_stride; l.max_plies = max_plies;
+    l.out = out_dev; l.return_out = return_out_dev; l.hash_out = hash_out_dev; l.order_out = order_out_dev; l.k_cap = k_cap;
+    l.weights = weights_dev; l.weights_k_cap = weights_k_cap;
+    XR_HIP(launch_line(b, c, l));
     return XR_OK;
 }
 }  // namespace
@@ -2025,31 +2071,26 @@ int32_t xr_batch_peek(xr_batch* b, int32_t group, int32_t n_lines, const int32_t
                       int32_t* order_out_dev, int32_t k_cap, void* stream) {
     const char* fn = "xr_batch_peek";
     if (!b || !rows_out_dev || !out_dev) return fail(XR_ERR_INVALID, "%s: null argument", fn);
-    if ((reinterpret_cast<uintptr_t>(rows_out_dev) & 7) || row_bytes % 8 != 0)
-        return fail(XR_ERR_INVALID, "%s: rows_out_dev %p / row_bytes %lld are not 8-byte aligned", fn, (void*)rows_out_dev, (long long)row_bytes);
+    if (const int32_t rc = state_row_check(b, fn, rows_out_dev, row_bytes, ROWS_ALIGNED)) return rc;
     if (!b->loaded) return fail(XR_ERR_STATE, "%s: load regions first", fn);
     int lo, rows;
     if (const int32_t rc = group_rows(b, group, fn, lo, rows)) return rc;
     if (prefix_dev && prefix_stride < 1) return fail(XR_ERR_INVALID, "%s: prefix_stride %d < 1 with a prefix", fn, prefix_stride);
     if (max_plies < 0) return fail(XR_ERR_INVALID, "%s: max_plies %d is negative", fn, max_plies);
     if (n_lines < 1 || n_lines > XR_PEEK_MAX) return fail(XR_ERR_RANGE, "%s: n_lines %d outside 1..%d", fn, n_lines, XR_PEEK_MAX);
-    const int64_t need = 16 + 8 * ((int64_t)b->legal_words + ((b->n_max + 63) >> 6));
-    if (row_bytes < need) return fail(XR_ERR_RANGE, "%s: row_bytes %lld < %lld (xr_batch_state_row_bytes)", fn, (long long)row_bytes, (long long)need);
+    if (const int32_t rc = state_row_check(b, fn, rows_out_dev, row_bytes, ROWS_LONG)) return rc;
     if (order_out_dev && k_cap < b->k_max) return fail(XR_ERR_RANGE, "%s: k_cap %d < k_max %d", fn, k_cap, b->k_max);
     if (const int32_t rc = lds_field_check(b, fn)) return rc;
-    const int64_t tasks = (int64_t)rows * n_lines;
-    if (tasks >= ((int64_t)1 << 31)) return fail(XR_ERR_RANGE, "%s: rows x n_lines does not fit 31 bits", fn);
-    if (!xr_lookahead_occupancy || !xr_launch_peek) return fail(XR_ERR_STATE, "%s: peek kernels not linked", fn);
-    XR_HIP(hipSetDevice(b->cfg.device));
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    const XrRouteVariant v = route_variant(b);
-    xr_batch::LookPool& lp = b->look[group + 1];
-    if (const int32_t rc = shadow_pool(b, lp, v, st, fn, true)) return rc;
-    const XrBatchDev sh = shadow_view(b, lp);
-    const Banks ctr = flip_banks(lp.roll_ctr.p, lp.roll_bank, 1);
-    const int blocks = (int)std::min<int64_t>(b->look_grid, tasks);
-    XR_HIP(xr_launch_peek(&b->dev, &sh, lo, (int)tasks, n_lines, prefix_dev, prefix_dev ? prefix_stride : 0, max_plies, ctr.cur, ctr.next, rows_out_dev,
-                          row_bytes, region_base, out_dev, return_out_dev, hash_out_dev, order_out_dev, order_out_dev ? k_cap : 0, v, blocks, st));
+    if ((int64_t)rows * n_lines >= ((int64_t)1 << 31)) return fail(XR_ERR_RANGE, "%s: rows x n_lines does not fit 31 bits", fn);
+    if (!xr_lookahead_occupancy || !xr_launch_line) return fail(XR_ERR_STATE, "%s: peek kernels not linked", fn);
+    ShadowCall c;
+    if (const int32_t rc = shadow_call(b, group, lo, rows, stream, fn, true, c)) return rc;
+    XrLineLaunch l{};
+    l.kind = XR_LINE_PEEK; l.per_row = n_lines;
+    l.prefix = prefix_dev; l.prefix_stride = prefix_stride; l.max_plies = max_plies;
+    l.rows = rows_out_dev; l.row_bytes = row_bytes; l.region_base = region_base;
+    l.out = out_dev; l.return_out = return_out_dev; l.hash_out = hash_out_dev; l.order_out = order_out_dev; l.k_cap = k_cap;
+    XR_HIP(launch_line(b, c, l));
     return XR_OK;
 }
 
@@ -2074,152 +2115,240 @@ int32_t xr_tree_exploration_table(double c_init, double c_base, int32_t n, doubl
 }
 
 namespace {
-// xr_batch_tree_search (sim_weights_dev null) and xr_batch_tree_search_weighted: Evaluate runs XR_ROLLOUT_RANDOM, or XR_ROLLOUT_WEIGHTED
-// with the row's sim weights ([rows][k_cap]); every refusal names the entry point (fn).  keep: xr_batch_tree_search_keep — the same
-// checks and the same waves, on the caller's kept-tree pool, after xr_tree_keep_begin_kernel in place of the reset
-int32_t tree_search_impl(const char* fn, bool keep, const int32_t* played_dev, int32_t* kept_out_dev, xr_batch* b, int32_t group, int32_t n_waves, int32_t n_par, uint64_t seed, const float* prior_dev, int32_t node_cap,
-                         double c_init, double c_base, int32_t* visits_out_dev, double* value_out_dev, int32_t k_cap, int32_t* info_out_dev,
-                         int32_t* best_order_out_dev, double* best_return_out_dev, int32_t* paths_out_dev, double* returns_out_dev,
-                         const int32_t* sim_weights_dev, void* stream) {
-    if (!b || !visits_out_dev || !value_out_dev || !info_out_dev) return fail(XR_ERR_INVALID, "%s: null argument", fn);
-    if (!b->loaded) return fail(XR_ERR_STATE, "%s: load regions first", fn);
-    int lo, rows;
-    if (const int32_t rc = group_rows(b, group, fn, lo, rows)) return rc;
-    if (n_waves < 1) return fail(XR_ERR_INVALID, "%s: n_waves %d < 1", fn, n_waves);
-    if (n_par < 1) return fail(XR_ERR_INVALID, "%s: n_par %d < 1", fn, n_par);
-    if (!std::isfinite(c_init)) return fail(XR_ERR_INVALID, "%s: c_init is not finite", fn);
-    if (!tree_knobs_ok(c_init, c_base)) return fail(XR_ERR_INVALID, "%s: c_base must be finite and > 0", fn);
-    if (n_par > XR_ROLLOUT_MAX) return fail(XR_ERR_RANGE, "%s: n_par %d above %d", fn, n_par, XR_ROLLOUT_MAX);
-    if ((int64_t)n_waves * n_par > XR_TREE_MAX_SIMS)
-        return fail(XR_ERR_RANGE, "%s: n_waves x n_par = %lld simulations above %d", fn, (long long)n_waves * n_par, XR_TREE_MAX_SIMS);
-    if (node_cap < 1) return fail(XR_ERR_RANGE, "%s: node_cap %d < 1", fn, node_cap);
-    if (k_cap < b->k_max) return fail(XR_ERR_RANGE, "%s: k_cap %d < k_max %d", fn, k_cap, b->k_max);
-    if (const int32_t rc = lds_field_check(b, fn)) return rc;
-    const int64_t tasks = (int64_t)rows * n_par;
-    if (tasks >= ((int64_t)1 << 31)) return fail(XR_ERR_RANGE, "%s: rows x n_par does not fit 31 bits", fn);
-    if (!xr_lookahead_occupancy || !xr_launch_rollout || !xr_launch_tree_reset || !xr_launch_tree_select || !xr_launch_tree_backup ||
-        (sim_weights_dev && !xr_launch_rollout_weighted) || (keep && !xr_launch_tree_keep_begin))
-        return fail(XR_ERR_STATE, "%s: tree search kernels not linked", fn);
-    if (k_cap < 1) k_cap = 1;
-    const int n_sims = n_waves * n_par;
-    // the private memory: six arrays in one allocation, each starting on a 16-byte boundary
-    if ((double)rows * ((keep ? 2.0 : 1.0) * (double)node_cap * sizeof(XrTreeNode) + (keep ? 8.0 * b->legal_words + 24.0 : 0.0) + (double)n_par * (8.0 * k_cap + 40.0) + 64.0) > 1e15)
-        return fail(XR_ERR_NOMEM, "%s: %d rows x %d nodes do not fit any device", fn, rows, node_cap);
-    Carver c;
-    const size_t R = (size_t)rows, P = (size_t)n_par, K = (size_t)k_cap;
-    // (a kept call: the nodes, the row states and the keys live in the pool's other allocation, carved below)
-    const size_t o_nodes = keep ? 0 : c.take(R * (size_t)node_cap * sizeof(XrTreeNode)), o_rs = keep ? 0 : c.take(R * sizeof(XrTreeRow));
-    const size_t o_prefix = c.take(R * P * K * sizeof(int32_t)), o_order = c.take(R * P * K * sizeof(int32_t));
-    const size_t o_rec = c.take(R * P * 8 * sizeof(int32_t)), o_ret = c.take(R * P * sizeof(double));
-    XR_HIP(hipSetDevice(b->cfg.device));
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    const XrRouteVariant v = route_variant(b);
-    xr_batch::LookPool& lp = b->look[group + 1];
-    if (const int32_t rc = shadow_pool(b, lp, v, st, fn, true)) return rc;
-    const XrBatchDev sh = shadow_view(b, lp);
-    xr_batch::TreePool& tp = b->tree[group + 1];
-    xr_batch::KeepPool& kp = b->keep[group + 1];
-    DevBuf<uint8_t>& wave_mem = keep ? kp.scratch : tp.mem;
-    if (wave_mem.n < c.off && wave_mem.alloc(c.off) != hipSuccess) {
-        wave_mem.release();
-        return fail(XR_ERR_NOMEM, "%s: hipMalloc of %zu bytes of trees failed", fn, c.off);
-    }
-    Carver ck;          // the kept trees: two halves of nodes, the row states, the keys, their legal words
-    const size_t half_bytes = R * (size_t)node_cap * sizeof(XrTreeNode);
-    const size_t k_half0 = ck.take(half_bytes), k_half1 = ck.take(half_bytes), k_rs = ck.take(R * sizeof(XrTreeRow));
-    const size_t k_key = ck.take(R * sizeof(XrTreeKey)), k_legal = ck.take(R * (size_t)b->legal_words * sizeof(uint64_t));
-    bool rebuild_all = !played_dev;
-    if (keep) {
-        if (kp.rows != rows || kp.lo != lo || kp.node_cap != node_cap || kp.k_cap != k_cap || kp.legal_words != b->legal_words || kp.trees.n < ck.off) {
-            rebuild_all = true;          // another shape (or the first call): no row of the pool is a tree of this call's rows
-            if (kp.trees.n < ck.off && kp.trees.alloc(ck.off) != hipSuccess) {
-                kp.release();
-                return fail(XR_ERR_NOMEM, "%s: hipMalloc of %zu bytes of kept trees failed", fn, ck.off);
-            }
-        }
-        kp.rows = 0;          // (the pool holds this call's trees once its first kernel is enqueued, not before)
-    }
-    auto& tables = keep ? kp.tables : tp.tables;
-    const int e_max = keep ? XR_TREE_MAX_SIMS : n_sims;          // a kept root meets visit counts above this call's simulations
+using TreeTables = std::vector<std::unique_ptr<xr_batch::TreeTable>>;
+
+// Which uploaded table serves a call that wants E[0 .. e_max].  The searches take any table of their knobs that is long enough
+// (TABLE_AT_LEAST: a later, longer call adds a table and the shorter one stays, since a launch in flight may read it); a session takes
+// one of exactly its length (TABLE_EXACTLY: EvalPool keeps one per (c_init, c_base, max_sims)).  Both kernels clamp their index at the
+// e_max they are handed, not at the table's length, so a longer table would serve a session as well; the rules stay as they were
+enum TableMatch { TABLE_AT_LEAST, TABLE_EXACTLY };
+
+// The exploration table of (c_init, c_base) among `tables`, found or built and uploaded: the single copy.  E: its device address
+int32_t exploration_table(TreeTables& tables, double c_init, double c_base, int e_max, TableMatch match, hipStream_t st, const char* fn, const double*& E) {
+    const size_t len = (size_t)e_max + 1;
     xr_batch::TreeTable* tab = nullptr;
     for (auto& t : tables)
-        if (t->c_init == c_init && t->c_base == c_base && t->host.size() >= (size_t)e_max + 1) tab = t.get();
+        if (t->c_init == c_init && t->c_base == c_base && (match == TABLE_EXACTLY ? t->host.size() == len : t->host.size() >= len)) tab = t.get();
     if (!tab) {
         std::unique_ptr<xr_batch::TreeTable> t(new (std::nothrow) xr_batch::TreeTable);
         if (!t) return fail(XR_ERR_NOMEM, "%s: no host memory for the exploration table", fn);
         t->c_init = c_init; t->c_base = c_base;
-        t->host.resize((size_t)e_max + 1);
+        t->host.resize(len);
         tree_table_fill(c_init, c_base, 0, e_max, t->host.data());
         if (t->dev.alloc(t->host.size()) != hipSuccess) return fail(XR_ERR_NOMEM, "%s: hipMalloc of the exploration table failed", fn);
         XR_HIP(hipMemcpyAsync(t->dev.p, t->host.data(), t->host.size() * sizeof(double), hipMemcpyHostToDevice, st));
-        tab = t.get();          // (a shorter table of the same knobs stays: a launch in flight may read it)
+        tab = t.get();          // (the host copy stays: the asynchronous upload reads it)
         tables.push_back(std::move(t));
     }
-    uint8_t* const m = wave_mem.p;
-    XrTreeDev t{};
-    XrTreeKeepDev kd{};
-    if (keep) {          // the half flip: this call searches in the other half, and reads the last call's
-        uint8_t* const km = kp.trees.p;
-        kd.old_nodes = reinterpret_cast<const XrTreeNode*>(km + (kp.half ? k_half1 : k_half0));
-        kp.half ^= 1;
-        t.nodes = reinterpret_cast<XrTreeNode*>(km + (kp.half ? k_half1 : k_half0)); t.rs = reinterpret_cast<XrTreeRow*>(km + k_rs);
-        kd.key = reinterpret_cast<XrTreeKey*>(km + k_key); kd.key_legal = reinterpret_cast<uint64_t*>(km + k_legal);
-        kd.played = rebuild_all ? nullptr : played_dev; kd.kept_out = kept_out_dev; kd.n_add = n_sims;
-    } else {
-        t.nodes = reinterpret_cast<XrTreeNode*>(m + o_nodes); t.rs = reinterpret_cast<XrTreeRow*>(m + o_rs);
+    E = tab->dev.p;
+    return XR_OK;
+}
+
+// What the three tree searches take: xr_batch_tree_search (sim_weights null, keep false), xr_batch_tree_search_weighted (Evaluate runs
+// XR_ROLLOUT_WEIGHTED with the row's sim weights, [rows][k_cap], instead of XR_ROLLOUT_RANDOM) and xr_batch_tree_search_keep (keep: the
+// same checks and the same waves on the caller's kept-tree pool, after xr_tree_keep_begin_kernel in place of the reset)
+struct TreeSearchArgs {
+    const char* fn = nullptr;          // the entry point: every refusal names it
+    int32_t group = -1, n_waves = 0, n_par = 0, node_cap = 0, k_cap = 0;
+    uint64_t seed = 0;
+    double c_init = 0, c_base = 0;
+    const float* prior = nullptr;
+    const int32_t* sim_weights = nullptr;
+    int32_t* visits_out = nullptr;
+    double* value_out = nullptr;
+    int32_t* info_out = nullptr;
+    int32_t* best_order_out = nullptr;
+    double* best_return_out = nullptr;
+    int32_t* paths_out = nullptr;
+    double* returns_out = nullptr;
+    void* stream = nullptr;
+    bool keep = false;
+    const int32_t* played = nullptr;   // keep alone: null (every row is rebuilt), or [rows]
+    int32_t* kept_out = nullptr;       // keep alone: null, or [rows][2]
+};
+
+// Step 1: every refusal, in the documented order, up to "do not fit any device".  Allocates nothing; k_cap leaves it at 1 or more
+int32_t tree_check(const xr_batch* b, TreeSearchArgs& a, int& lo, int& rows) {
+    const char* fn = a.fn;
+    if (!b || !a.visits_out || !a.value_out || !a.info_out) return fail(XR_ERR_INVALID, "%s: null argument", fn);
+    if (!b->loaded) return fail(XR_ERR_STATE, "%s: load regions first", fn);
+    if (const int32_t rc = group_rows(b, a.group, fn, lo, rows)) return rc;
+    if (a.n_waves < 1) return fail(XR_ERR_INVALID, "%s: n_waves %d < 1", fn, a.n_waves);
+    if (a.n_par < 1) return fail(XR_ERR_INVALID, "%s: n_par %d < 1", fn, a.n_par);
+    if (!std::isfinite(a.c_init)) return fail(XR_ERR_INVALID, "%s: c_init is not finite", fn);
+    if (!tree_knobs_ok(a.c_init, a.c_base)) return fail(XR_ERR_INVALID, "%s: c_base must be finite and > 0", fn);
+    if (a.n_par > XR_ROLLOUT_MAX) return fail(XR_ERR_RANGE, "%s: n_par %d above %d", fn, a.n_par, XR_ROLLOUT_MAX);
+    if ((int64_t)a.n_waves * a.n_par > XR_TREE_MAX_SIMS)
+        return fail(XR_ERR_RANGE, "%s: n_waves x n_par = %lld simulations above %d", fn, (long long)a.n_waves * a.n_par, XR_TREE_MAX_SIMS);
+    if (a.node_cap < 1) return fail(XR_ERR_RANGE, "%s: node_cap %d < 1", fn, a.node_cap);
+    if (a.k_cap < b->k_max) return fail(XR_ERR_RANGE, "%s: k_cap %d < k_max %d", fn, a.k_cap, b->k_max);
+    if (const int32_t rc = lds_field_check(b, fn)) return rc;
+    if ((int64_t)rows * a.n_par >= ((int64_t)1 << 31)) return fail(XR_ERR_RANGE, "%s: rows x n_par does not fit 31 bits", fn);
+    if (!xr_lookahead_occupancy || !xr_launch_line || !xr_launch_tree_reset || !xr_launch_tree_select || !xr_launch_tree_backup ||
+        (a.keep && !xr_launch_tree_keep_begin))
+        return fail(XR_ERR_STATE, "%s: tree search kernels not linked", fn);
+    if (a.k_cap < 1) a.k_cap = 1;
+    if ((double)rows * ((a.keep ? 2.0 : 1.0) * (double)a.node_cap * sizeof(XrTreeNode) + (a.keep ? 8.0 * b->legal_words + 24.0 : 0.0) +
+                        (double)a.n_par * (8.0 * a.k_cap + 40.0) + 64.0) > 1e15)
+        return fail(XR_ERR_NOMEM, "%s: %d rows x %d nodes do not fit any device", fn, rows, a.node_cap);
+    return XR_OK;
+}
+
+// Step 2: the private memory of the waves, grown to this call's shape — six arrays in one allocation, each starting on a 16-byte
+// boundary (a kept call: four; its nodes and row states live in the kept pool).  rec: the rollout launch's records, read by no one
+int32_t wave_memory(xr_batch* b, const TreeSearchArgs& a, int rows, XrTreeDev& t, int32_t*& rec) {
+    Carver c;
+    const size_t R = (size_t)rows, P = (size_t)a.n_par, K = (size_t)a.k_cap;
+    const size_t o_nodes = a.keep ? 0 : c.take(R * (size_t)a.node_cap * sizeof(XrTreeNode)), o_rs = a.keep ? 0 : c.take(R * sizeof(XrTreeRow));
+    const size_t o_prefix = c.take(R * P * K * sizeof(int32_t)), o_order = c.take(R * P * K * sizeof(int32_t));
+    const size_t o_rec = c.take(R * P * 8 * sizeof(int32_t)), o_ret = c.take(R * P * sizeof(double));
+    DevBuf<uint8_t>& mem = a.keep ? b->keep[a.group + 1].scratch : b->tree[a.group + 1].mem;
+    if (mem.n < c.off && mem.alloc(c.off) != hipSuccess) {
+        mem.release();
+        return fail(XR_ERR_NOMEM, "%s: hipMalloc of %zu bytes of trees failed", a.fn, c.off);
     }
+    uint8_t* const m = mem.p;
+    if (!a.keep) { t.nodes = reinterpret_cast<XrTreeNode*>(m + o_nodes); t.rs = reinterpret_cast<XrTreeRow*>(m + o_rs); }
     t.prefix = reinterpret_cast<int32_t*>(m + o_prefix); t.order = reinterpret_cast<int32_t*>(m + o_order);
     t.ret = reinterpret_cast<double*>(m + o_ret);
-    int32_t* const rec = reinterpret_cast<int32_t*>(m + o_rec);
-    t.E = tab->dev.p; t.prior = prior_dev;
-    t.node_cap = node_cap; t.n_par = n_par; t.k_cap = k_cap; t.n_sims = n_sims; t.env_lo = lo; t.e_max = e_max;
-    t.visits_out = visits_out_dev; t.value_out = value_out_dev; t.info_out = info_out_dev; t.best_order_out = best_order_out_dev;
-    t.best_return_out = best_return_out_dev; t.paths_out = paths_out_dev; t.returns_out = returns_out_dev;
-    const int blocks = (int)std::min<int64_t>(b->look_grid, tasks);
-    if (keep) {
-        XR_HIP(xr_launch_tree_keep_begin(&b->dev, &t, &kd, rows, st));
-        kp.rows = rows; kp.lo = lo; kp.node_cap = node_cap; kp.k_cap = k_cap; kp.legal_words = b->legal_words;
-    } else {
-        XR_HIP(xr_launch_tree_reset(&b->dev, &t, rows, st));
+    rec = reinterpret_cast<int32_t*>(m + o_rec);
+    return XR_OK;
+}
+
+// the kept trees of a pool: two halves of nodes, the row states, the keys, their legal words
+struct KeptCarve { size_t half[2], rs, key, legal, bytes; };
+KeptCarve kept_carve(const xr_batch* b, int rows, int node_cap) {
+    Carver c;
+    const size_t R = (size_t)rows, half_bytes = R * (size_t)node_cap * sizeof(XrTreeNode);
+    KeptCarve k{};
+    k.half[0] = c.take(half_bytes); k.half[1] = c.take(half_bytes); k.rs = c.take(R * sizeof(XrTreeRow));
+    k.key = c.take(R * sizeof(XrTreeKey)); k.legal = c.take(R * (size_t)b->legal_words * sizeof(uint64_t));
+    k.bytes = c.off;
+    return k;
+}
+
+// Step 3 (a kept call): the pool against this call's shape.  Another shape, or the first call: no row of the pool is a tree of this
+// call's rows, every row is rebuilt and `played` is dropped; the pool grows if it has to.  From here until the first kernel is enqueued
+// (kept_begin) the pool holds no trees
+int32_t kept_pool(xr_batch* b, const TreeSearchArgs& a, int lo, int rows, bool& rebuild_all) {
+    xr_batch::KeepPool& kp = b->keep[a.group + 1];
+    const size_t bytes = kept_carve(b, rows, a.node_cap).bytes;
+    rebuild_all = !a.played;
+    if (kp.rows != rows || kp.lo != lo || kp.node_cap != a.node_cap || kp.k_cap != a.k_cap || kp.legal_words != b->legal_words || kp.trees.n < bytes) {
+        rebuild_all = true;
+        if (kp.trees.n < bytes && kp.trees.alloc(bytes) != hipSuccess) {
+            kp.release();
+            return fail(XR_ERR_NOMEM, "%s: hipMalloc of %zu bytes of kept trees failed", a.fn, bytes);
+        }
     }
-    for (int w = 0; w < n_waves; w++) {
-        XR_HIP(xr_launch_tree_select(&b->dev, &t, rows, w, st));
-        const Banks ctr = flip_banks(lp.roll_ctr.p, lp.roll_bank, 1);
-        const uint64_t seed_w = seed + (uint64_t)w * 0xD1B54A32D192ED03ULL;
-        if (sim_weights_dev)
-            XR_HIP(xr_launch_rollout_weighted(&b->dev, &sh, lo, (int)tasks, n_par, seed_w, t.prefix, k_cap, 0, ctr.cur, ctr.next, rec, t.ret, nullptr, t.order,
-                                              k_cap, sim_weights_dev, k_cap, v, blocks, st));
-        else
-            XR_HIP(xr_launch_rollout(&b->dev, &sh, lo, (int)tasks, n_par, XR_ROLLOUT_RANDOM, seed_w, t.prefix, k_cap, 0, ctr.cur, ctr.next, rec, t.ret, nullptr,
-                                     t.order, k_cap, v, blocks, st));
-        XR_HIP(xr_launch_tree_backup(&b->dev, &t, rows, w, w == n_waves - 1 ? 1 : 0, st));
+    kp.rows = 0;
+    return XR_OK;
+}
+
+// Step 5 (a kept call), after the last step that can refuse, so that a refused call leaves the halves where they were: the half flip —
+// this call searches in the other half and reads the last call's — and the first kernel, which re-roots or rebuilds every row
+int32_t kept_begin(xr_batch* b, const TreeSearchArgs& a, int lo, int rows, bool rebuild_all, XrTreeDev& t, hipStream_t st) {
+    xr_batch::KeepPool& kp = b->keep[a.group + 1];
+    const KeptCarve k = kept_carve(b, rows, a.node_cap);
+    uint8_t* const km = kp.trees.p;
+    XrTreeKeepDev kd{};
+    kd.old_nodes = reinterpret_cast<const XrTreeNode*>(km + k.half[kp.half]);
+    kp.half ^= 1;
+    t.nodes = reinterpret_cast<XrTreeNode*>(km + k.half[kp.half]); t.rs = reinterpret_cast<XrTreeRow*>(km + k.rs);
+    kd.key = reinterpret_cast<XrTreeKey*>(km + k.key); kd.key_legal = reinterpret_cast<uint64_t*>(km + k.legal);
+    kd.played = rebuild_all ? nullptr : a.played; kd.kept_out = a.kept_out; kd.n_add = t.n_sims;
+    XR_HIP(xr_launch_tree_keep_begin(&b->dev, &t, &kd, rows, st));
+    kp.rows = rows; kp.lo = lo; kp.node_cap = a.node_cap; kp.k_cap = a.k_cap; kp.legal_words = b->legal_words;
+    return XR_OK;
+}
+
+// The last step: per wave select, the rollout launch of the wave's paths (its records go to rec, its returns and orders to the tree's
+// rows), backup
+int32_t run_waves(const xr_batch* b, const TreeSearchArgs& a, const ShadowCall& c, const XrTreeDev& t, int32_t* rec) {
+    XrLineLaunch l{};
+    l.kind = a.sim_weights ? XR_LINE_WEIGHTED : XR_LINE_POLICY; l.per_row = a.n_par;
+    l.policy = XR_ROLLOUT_RANDOM;
+    l.prefix = t.prefix; l.prefix_stride = a.k_cap;
+    l.out = rec; l.return_out = t.ret; l.order_out = t.order; l.k_cap = a.k_cap;
+    l.weights = a.sim_weights; l.weights_k_cap = a.k_cap;
+    for (int w = 0; w < a.n_waves; w++) {
+        XR_HIP(xr_launch_tree_select(&b->dev, &t, c.rows, w, c.st));
+        l.seed = a.seed + (uint64_t)w * 0xD1B54A32D192ED03ULL;
+        XR_HIP(launch_line(b, c, l));
+        XR_HIP(xr_launch_tree_backup(&b->dev, &t, c.rows, w, w == a.n_waves - 1 ? 1 : 0, c.st));
     }
     return XR_OK;
+}
+
+int32_t tree_search_impl(xr_batch* b, TreeSearchArgs a) {
+    int lo, rows;
+    if (const int32_t rc = tree_check(b, a, lo, rows)) return rc;
+    ShadowCall c;
+    if (const int32_t rc = shadow_call(b, a.group, lo, rows, a.stream, a.fn, true, c)) return rc;
+    XrTreeDev t{};
+    int32_t* rec = nullptr;
+    bool rebuild_all = false;
+    if (const int32_t rc = wave_memory(b, a, rows, t, rec)) return rc;
+    if (a.keep)
+        if (const int32_t rc = kept_pool(b, a, lo, rows, rebuild_all)) return rc;
+    t.n_sims = a.n_waves * a.n_par;
+    t.e_max = a.keep ? XR_TREE_MAX_SIMS : t.n_sims;          // a kept root meets visit counts above this call's simulations
+    if (const int32_t rc = exploration_table(a.keep ? b->keep[a.group + 1].tables : b->tree[a.group + 1].tables, a.c_init, a.c_base, t.e_max, TABLE_AT_LEAST, c.st,
+                                             a.fn, t.E))
+        return rc;
+    t.prior = a.prior;
+    t.node_cap = a.node_cap; t.n_par = a.n_par; t.k_cap = a.k_cap; t.env_lo = lo;
+    t.visits_out = a.visits_out; t.value_out = a.value_out; t.info_out = a.info_out; t.best_order_out = a.best_order_out;
+    t.best_return_out = a.best_return_out; t.paths_out = a.paths_out; t.returns_out = a.returns_out;
+    if (a.keep) {
+        if (const int32_t rc = kept_begin(b, a, lo, rows, rebuild_all, t, c.st)) return rc;
+    } else {
+        XR_HIP(xr_launch_tree_reset(&b->dev, &t, rows, c.st));
+    }
+    return run_waves(b, a, c, t, rec);
+}
+
+// what the three exports have in common, into `a` (by reference: this namespace lies inside extern "C")
+void tree_args(TreeSearchArgs& a, const char* fn, int32_t group, int32_t n_waves, int32_t n_par, uint64_t seed, const float* prior_dev, int32_t node_cap, double c_init,
+               double c_base, int32_t* visits_out_dev, double* value_out_dev, int32_t k_cap, int32_t* info_out_dev, int32_t* best_order_out_dev,
+               double* best_return_out_dev, int32_t* paths_out_dev, double* returns_out_dev, void* stream) {
+    a.fn = fn; a.group = group; a.n_waves = n_waves; a.n_par = n_par; a.seed = seed; a.prior = prior_dev; a.node_cap = node_cap;
+    a.c_init = c_init; a.c_base = c_base; a.visits_out = visits_out_dev; a.value_out = value_out_dev; a.k_cap = k_cap; a.info_out = info_out_dev;
+    a.best_order_out = best_order_out_dev; a.best_return_out = best_return_out_dev; a.paths_out = paths_out_dev; a.returns_out = returns_out_dev;
+    a.stream = stream;
 }
 }  // namespace
 
 int32_t xr_batch_tree_search(xr_batch* b, int32_t group, int32_t n_waves, int32_t n_par, uint64_t seed, const float* prior_dev, int32_t node_cap,
                              double c_init, double c_base, int32_t* visits_out_dev, double* value_out_dev, int32_t k_cap, int32_t* info_out_dev,
                              int32_t* best_order_out_dev, double* best_return_out_dev, int32_t* paths_out_dev, double* returns_out_dev, void* stream) {
-    return tree_search_impl("xr_batch_tree_search", false, nullptr, nullptr, b, group, n_waves, n_par, seed, prior_dev, node_cap, c_init, c_base, visits_out_dev, value_out_dev, k_cap,
-                            info_out_dev, best_order_out_dev, best_return_out_dev, paths_out_dev, returns_out_dev, nullptr, stream);
+    TreeSearchArgs a;
+    tree_args(a, "xr_batch_tree_search", group, n_waves, n_par, seed, prior_dev, node_cap, c_init, c_base, visits_out_dev, value_out_dev, k_cap, info_out_dev,
+              best_order_out_dev, best_return_out_dev, paths_out_dev, returns_out_dev, stream);
+    return tree_search_impl(b, a);
 }
 
 int32_t xr_batch_tree_search_weighted(xr_batch* b, int32_t group, int32_t n_waves, int32_t n_par, uint64_t seed, const float* prior_dev, int32_t node_cap,
                                       double c_init, double c_base, int32_t* visits_out_dev, double* value_out_dev, int32_t k_cap, int32_t* info_out_dev,
                                       int32_t* best_order_out_dev, double* best_return_out_dev, int32_t* paths_out_dev, double* returns_out_dev,
                                       const int32_t* sim_weights_dev, void* stream) {
-    return tree_search_impl("xr_batch_tree_search_weighted", false, nullptr, nullptr, b, group, n_waves, n_par, seed, prior_dev, node_cap, c_init, c_base, visits_out_dev, value_out_dev,
-                            k_cap, info_out_dev, best_order_out_dev, best_return_out_dev, paths_out_dev, returns_out_dev, sim_weights_dev, stream);
+    TreeSearchArgs a;
+    tree_args(a, "xr_batch_tree_search_weighted", group, n_waves, n_par, seed, prior_dev, node_cap, c_init, c_base, visits_out_dev, value_out_dev, k_cap, info_out_dev,
+              best_order_out_dev, best_return_out_dev, paths_out_dev, returns_out_dev, stream);
+    a.sim_weights = sim_weights_dev;
+    return tree_search_impl(b, a);
 }
 
 int32_t xr_batch_tree_search_keep(xr_batch* b, int32_t group, const int32_t* played_dev, int32_t n_waves, int32_t n_par, uint64_t seed, const float* prior_dev,
                                   int32_t node_cap, double c_init, double c_base, int32_t* visits_out_dev, double* value_out_dev, int32_t k_cap,
                                   int32_t* info_out_dev, int32_t* best_order_out_dev, double* best_return_out_dev, int32_t* paths_out_dev,
                                   double* returns_out_dev, const int32_t* sim_weights_dev, int32_t* kept_out_dev, void* stream) {
-    return tree_search_impl("xr_batch_tree_search_keep", true, played_dev, kept_out_dev, b, group, n_waves, n_par, seed, prior_dev, node_cap, c_init, c_base,
-                            visits_out_dev, value_out_dev, k_cap, info_out_dev, best_order_out_dev, best_return_out_dev, paths_out_dev, returns_out_dev,
-                            sim_weights_dev, stream);
+    TreeSearchArgs a;
+    tree_args(a, "xr_batch_tree_search_keep", group, n_waves, n_par, seed, prior_dev, node_cap, c_init, c_base, visits_out_dev, value_out_dev, k_cap, info_out_dev,
+              best_order_out_dev, best_return_out_dev, paths_out_dev, returns_out_dev, stream);
+    a.sim_weights = sim_weights_dev;
+    a.keep = true; a.played = played_dev; a.kept_out = kept_out_dev;
+    return tree_search_impl(b, a);
 }
 
 // ---- evaluated tree search ---------------------------------------------------------------------------------------------------------
@@ -2242,7 +2371,7 @@ int32_t xr_batch_tree_open(xr_batch* b, int32_t group, int32_t n_par, int32_t no
     if (const int32_t rc = lds_field_check(b, fn)) return rc;
     const int64_t tasks = (int64_t)rows * n_par;
     if (tasks >= ((int64_t)1 << 31)) return fail(XR_ERR_RANGE, "%s: rows x n_par does not fit 31 bits", fn);
-    if (!xr_lookahead_occupancy || !xr_launch_peek || !xr_launch_tree_eval_open || !xr_launch_tree_eval_select || !xr_launch_tree_eval_backup)
+    if (!xr_lookahead_occupancy || !xr_launch_line || !xr_launch_tree_eval_open || !xr_launch_tree_eval_select || !xr_launch_tree_eval_backup)
         return fail(XR_ERR_STATE, "%s: evaluated tree search kernels not linked", fn);
     if (k_cap < 1) k_cap = 1;
     if ((double)rows * ((double)node_cap * sizeof(XrTreeNode) + (double)n_par * (4.0 * k_cap + 16.0) + 8.0 * k_cap + 8.0 * b->legal_words + 44.0 + 160.0) > 1e15)
@@ -2253,31 +2382,17 @@ int32_t xr_batch_tree_open(xr_batch* b, int32_t group, int32_t n_par, int32_t no
     const size_t o_prefix = c.take(R * P * K * sizeof(int32_t)), o_ret = c.take(R * P * sizeof(double)), o_leaf = c.take(R * P * 2 * sizeof(int32_t));
     const size_t o_best = c.take(R * K * sizeof(int32_t)), o_legal = c.take(R * (size_t)b->legal_words * sizeof(uint64_t));
     const size_t o_nlegal = c.take(R * sizeof(int32_t)), o_prior = c.take(R * K * sizeof(float));
-    XR_HIP(hipSetDevice(b->cfg.device));
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    const XrRouteVariant v = route_variant(b);
-    xr_batch::LookPool& lp = b->look[group + 1];
-    if (const int32_t rc = shadow_pool(b, lp, v, st, fn, true)) return rc;          // (the peek launches of the session play there)
+    ShadowCall sc;          // (the peek launches of the session play in the caller's shadow slots)
+    if (const int32_t rc = shadow_call(b, group, lo, rows, stream, fn, true, sc)) return rc;
+    hipStream_t st = sc.st;
     xr_batch::EvalPool& ep = b->eval[group + 1];
     ep.open = false; ep.pending = false;          // the last session ends here, whatever becomes of this call
     if (ep.mem.n < c.off && ep.mem.alloc(c.off) != hipSuccess) {
         ep.mem.release();
         return fail(XR_ERR_NOMEM, "%s: hipMalloc of %zu bytes of trees failed", fn, c.off);
     }
-    xr_batch::TreeTable* tab = nullptr;
-    for (auto& t : ep.tables)
-        if (t->c_init == c_init && t->c_base == c_base && t->host.size() == (size_t)max_sims + 1) tab = t.get();
-    if (!tab) {
-        std::unique_ptr<xr_batch::TreeTable> t(new (std::nothrow) xr_batch::TreeTable);
-        if (!t) return fail(XR_ERR_NOMEM, "%s: no host memory for the exploration table", fn);
-        t->c_init = c_init; t->c_base = c_base;
-        t->host.resize((size_t)max_sims + 1);
-        tree_table_fill(c_init, c_base, 0, max_sims, t->host.data());
-        if (t->dev.alloc(t->host.size()) != hipSuccess) return fail(XR_ERR_NOMEM, "%s: hipMalloc of the exploration table failed", fn);
-        XR_HIP(hipMemcpyAsync(t->dev.p, t->host.data(), t->host.size() * sizeof(double), hipMemcpyHostToDevice, st));
-        tab = t.get();          // (the host copy stays: the asynchronous upload reads it)
-        ep.tables.push_back(std::move(t));
-    }
+    const double* E = nullptr;
+    if (const int32_t rc = exploration_table(ep.tables, c_init, c_base, max_sims, TABLE_EXACTLY, st, fn, E)) return rc;
     uint8_t* const m = ep.mem.p;
     XrTreeEvalDev d{};
     d.nodes = reinterpret_cast<XrTreeNode*>(m + o_nodes); d.rs = reinterpret_cast<XrTreeRow*>(m + o_rs);
@@ -2285,7 +2400,7 @@ int32_t xr_batch_tree_open(xr_batch* b, int32_t group, int32_t n_par, int32_t no
     d.leaf = reinterpret_cast<int32_t*>(m + o_leaf); d.best_order = reinterpret_cast<int32_t*>(m + o_best);
     d.legal = reinterpret_cast<uint64_t*>(m + o_legal); d.nlegal = reinterpret_cast<int32_t*>(m + o_nlegal);
     d.prior = reinterpret_cast<float*>(m + o_prior);
-    d.E = tab->dev.p;
+    d.E = E;
     d.node_cap = node_cap; d.n_par = n_par; d.k_cap = k_cap; d.e_max = max_sims; d.env_lo = lo; d.legal_words = b->legal_words;
     d.has_prior = root_prior_dev ? 1 : 0;
     XR_HIP(xr_launch_tree_eval_open(&b->dev, &d, root_prior_dev, rows, st));
@@ -2297,13 +2412,11 @@ int32_t xr_batch_tree_leaves(xr_batch* b, int32_t group, uint8_t* rows_out_dev, 
                              double* return_out_dev, int32_t* paths_out_dev, int32_t* leaf_out_dev, void* stream) {
     const char* fn = "xr_batch_tree_leaves";
     if (!b || !rows_out_dev || !out_dev) return fail(XR_ERR_INVALID, "%s: null argument", fn);
-    if ((reinterpret_cast<uintptr_t>(rows_out_dev) & 7) || row_bytes % 8 != 0)
-        return fail(XR_ERR_INVALID, "%s: rows_out_dev %p / row_bytes %lld are not 8-byte aligned", fn, (void*)rows_out_dev, (long long)row_bytes);
+    if (const int32_t rc = state_row_check(b, fn, rows_out_dev, row_bytes, ROWS_ALIGNED)) return rc;
     if (!b->loaded) return fail(XR_ERR_STATE, "%s: load regions first", fn);
     int lo, rows;
     if (const int32_t rc = group_rows(b, group, fn, lo, rows)) return rc;
-    const int64_t need = 16 + 8 * ((int64_t)b->legal_words + ((b->n_max + 63) >> 6));
-    if (row_bytes < need) return fail(XR_ERR_RANGE, "%s: row_bytes %lld < %lld (xr_batch_state_row_bytes)", fn, (long long)row_bytes, (long long)need);
+    if (const int32_t rc = state_row_check(b, fn, rows_out_dev, row_bytes, ROWS_LONG)) return rc;
     if (const int32_t rc = lds_field_check(b, fn)) return rc;
     xr_batch::EvalPool& ep = b->eval[group + 1];
     if (!ep.open || ep.rows != rows || ep.lo != lo || ep.d.legal_words != b->legal_words)
@@ -2311,20 +2424,19 @@ int32_t xr_batch_tree_leaves(xr_batch* b, int32_t group, uint8_t* rows_out_dev, 
     if (ep.pending) return fail(XR_ERR_STATE, "%s: the last wave's leaves still wait for xr_batch_tree_backup", fn);
     if (ep.sims + ep.d.n_par > ep.max_sims)
         return fail(XR_ERR_RANGE, "%s: %d simulations so far, a wave of %d would pass max_sims %d", fn, ep.sims, ep.d.n_par, ep.max_sims);
-    if (!xr_lookahead_occupancy || !xr_launch_peek || !xr_launch_tree_eval_select) return fail(XR_ERR_STATE, "%s: evaluated tree search kernels not linked", fn);
-    XR_HIP(hipSetDevice(b->cfg.device));
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    const XrRouteVariant v = route_variant(b);
-    xr_batch::LookPool& lp = b->look[group + 1];
-    if (const int32_t rc = shadow_pool(b, lp, v, st, fn, true)) return rc;
-    const XrBatchDev sh = shadow_view(b, lp);
+    if (!xr_lookahead_occupancy || !xr_launch_line || !xr_launch_tree_eval_select) return fail(XR_ERR_STATE, "%s: evaluated tree search kernels not linked", fn);
+    ShadowCall c;
+    if (const int32_t rc = shadow_call(b, group, lo, rows, stream, fn, true, c)) return rc;
+    hipStream_t st = c.st;
     const int64_t tasks = (int64_t)rows * ep.d.n_par;
     XR_HIP(xr_launch_tree_eval_select(&ep.d, paths_out_dev, leaf_out_dev, rows, st));
     ep.pending = true;          // (the paths carry pending visits from here on: only a backup, or a new open, clears them)
-    const Banks ctr = flip_banks(lp.roll_ctr.p, lp.roll_bank, 1);
-    const int blocks = (int)std::min<int64_t>(b->look_grid, tasks);
-    XR_HIP(xr_launch_peek(&b->dev, &sh, lo, (int)tasks, ep.d.n_par, ep.d.prefix, ep.d.k_cap, 0, ctr.cur, ctr.next, rows_out_dev, row_bytes, region_base, out_dev,
-                          ep.d.ret, nullptr, nullptr, 0, v, blocks, st));
+    XrLineLaunch l{};           // the wave's paths as prefixes, no policy after them: the rows of the leaves, their line returns into the pool
+    l.kind = XR_LINE_PEEK; l.per_row = ep.d.n_par;
+    l.prefix = ep.d.prefix; l.prefix_stride = ep.d.k_cap;
+    l.rows = rows_out_dev; l.row_bytes = row_bytes; l.region_base = region_base;
+    l.out = out_dev; l.return_out = ep.d.ret;
+    XR_HIP(launch_line(b, c, l));
     if (return_out_dev) XR_HIP(hipMemcpyAsync(return_out_dev, ep.d.ret, (size_t)tasks * sizeof(double), hipMemcpyDeviceToDevice, st));
     return XR_OK;
 }

@@ -287,6 +287,33 @@ struct XrRouteVariant {
     int threads;             // workgroup size
 };
 
+// One launch of a kernel that plays lines in the shadow slots (xr_rollout.h, xr_weighted.h, xr_peek.h): task t = (row t / per_row, line
+// t % per_row) of the caller's rows.  What the three kernels share, then each kind's own arguments (xr_launch_line)
+enum XrLineKind { XR_LINE_POLICY, XR_LINE_WEIGHTED, XR_LINE_PEEK };
+struct XrLineLaunch {
+    XrLineKind kind;
+    const XrBatchDev* src;       // the batch
+    const XrBatchDev* shadow;    // the shadow slots of the caller's pool
+    int env_lo, n_tasks, per_row;
+    int policy;                  // XR_LINE_POLICY alone: XR_ROLLOUT_STOP / XR_ROLLOUT_RANDOM (the other kinds have one policy each)
+    uint64_t seed;               // not XR_LINE_PEEK: a line ends with its prefix there
+    const int32_t* prefix;       // null, or [rows][per_row][prefix_stride]
+    int prefix_stride, max_plies;
+    uint32_t *ctr, *next_ctr;    // the claim counter of this launch, and the one it zeroes for the next
+    int32_t* out;
+    double* return_out;
+    uint64_t* hash_out;
+    int32_t* order_out;          // null, or rows of k_cap
+    int k_cap;
+    XrRouteVariant v;
+    int blocks;
+    const int32_t* weights;      // XR_LINE_WEIGHTED: [rows][weights_k_cap]
+    int weights_k_cap;
+    uint8_t* rows;               // XR_LINE_PEEK: packed state rows of row_bytes, region indices from region_base
+    int64_t row_bytes;
+    int region_base;
+};
+
 // The kernel launchers (xr_kernels.hip, xr_agent.hip; stand-ins that do nothing in tests/hostsan/stub_launch.cpp), declared once: every
 // definition and every caller is checked against these.  Seen only after a HIP runtime header (hipError_t, hipStream_t).
 #ifdef HIP_INCLUDE_HIP_HIP_RUNTIME_H
@@ -314,23 +341,12 @@ hipError_t xr_launch_lookahead_plan(const XrBatchDev* b, int env_lo, int rows, c
                                     int k_max, uint32_t* tasks, uint32_t* ctr, uint32_t* next_ctr, hipStream_t st) __attribute__((weak));
 hipError_t xr_launch_lookahead(const XrBatchDev* src, const XrBatchDev* shadow, int env_lo, const uint32_t* tasks, uint32_t* ctr, int32_t* out,
                                double* reward_out, int k_cap, int k_max, XrRouteVariant v, int blocks, hipStream_t st) __attribute__((weak));
-// rollouts (xr_rollout.h).  Weak for the same reason: xr_batch_rollout answers XR_ERR_STATE where it is not linked
-hipError_t xr_launch_rollout(const XrBatchDev* src, const XrBatchDev* shadow, int env_lo, int n_tasks, int n_rollouts, int policy, uint64_t seed,
-                             const int32_t* prefix, int prefix_stride, int max_plies, uint32_t* ctr, uint32_t* next_ctr, int32_t* out, double* return_out,
-                             uint64_t* hash_out, int32_t* order_out, int k_cap, XrRouteVariant v, int blocks, hipStream_t st) __attribute__((weak));
-// peek (xr_peek.h).  Weak for the same reason: xr_batch_peek answers XR_ERR_STATE where it is not linked
-hipError_t xr_launch_peek(const XrBatchDev* src, const XrBatchDev* shadow, int env_lo, int n_tasks, int n_lines, const int32_t* prefix, int prefix_stride,
-                          int max_plies, uint32_t* ctr, uint32_t* next_ctr, uint8_t* rows, int64_t row_bytes, int region_base, int32_t* out,
-                          double* return_out, uint64_t* hash_out, int32_t* order_out, int k_cap, XrRouteVariant v, int blocks, hipStream_t st)
-    __attribute__((weak));
-// weighted net sampling (xr_weighted.h).  Weak for the same reason: xr_batch_weighted_actions, xr_batch_rollout_weighted and
-// xr_batch_tree_search_weighted answer XR_ERR_STATE where they are not linked
+// rollouts, weighted rollouts and peek (xr_rollout.h, xr_weighted.h, xr_peek.h): the persistent launch of the kernel of l->kind.  Weak for
+// the same reason: xr_batch_rollout, xr_batch_rollout_weighted, xr_batch_peek and the tree searches answer XR_ERR_STATE where it is not linked
+hipError_t xr_launch_line(const XrLineLaunch* l, hipStream_t st) __attribute__((weak));
+// weighted net sampling (xr_weighted.h).  Weak for the same reason: xr_batch_weighted_actions answers XR_ERR_STATE where it is not linked
 hipError_t xr_launch_weighted_actions(const XrBatchDev* b, const int32_t* weights, int k_cap, int32_t* actions, uint64_t seed, hipStream_t st)
     __attribute__((weak));
-hipError_t xr_launch_rollout_weighted(const XrBatchDev* src, const XrBatchDev* shadow, int env_lo, int n_tasks, int n_rollouts, uint64_t seed,
-                                      const int32_t* prefix, int prefix_stride, int max_plies, uint32_t* ctr, uint32_t* next_ctr, int32_t* out,
-                                      double* return_out, uint64_t* hash_out, int32_t* order_out, int k_cap, const int32_t* weights, int weights_k_cap,
-                                      XrRouteVariant v, int blocks, hipStream_t st) __attribute__((weak));
 // branch (xr_branch.h): both passes, in stream order.  Weak for the same reason: xr_batch_branch answers XR_ERR_STATE where it is not linked
 hipError_t xr_launch_branch(const XrSlotRows* env, const XrSlotRows* stg, int env_lo, int rows, const int32_t* parent, int n_max, int path_cap,
                             int legal_words, int chunks, hipStream_t st) __attribute__((weak));

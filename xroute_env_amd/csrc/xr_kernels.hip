@@ -2259,13 +2259,17 @@ hipError_t xr_launch_reset(const XrBatchDev* b, const uint8_t* mask, int rotate,
     return hipGetLastError();
 }
 
+// every kernel that routes with the variant's dynamic LDS: a batch above 64 KB of it raises their limits here, once per load, and
+// nowhere else (the three line kernels included: xr_launch_line sets no attribute)
 hipError_t xr_route_set_max_lds(size_t bytes) {
     return xr_each_variant([&](auto L, auto Z) {
-        const void* fns[6] = {reinterpret_cast<const void*>(&xr_route_kernel<L.value, Z.value>), reinterpret_cast<const void*>(&xr_order_kernel<L.value, Z.value>),
+        const void* fns[8] = {reinterpret_cast<const void*>(&xr_route_kernel<L.value, Z.value>), reinterpret_cast<const void*>(&xr_order_kernel<L.value, Z.value>),
                               reinterpret_cast<const void*>(&xr_step_queue_kernel<L.value, Z.value>),
                               reinterpret_cast<const void*>(&xr_step_queue_u8_kernel<L.value, Z.value>),
                               reinterpret_cast<const void*>(&xr_lookahead_kernel<L.value, Z.value>),
-                              reinterpret_cast<const void*>(&xr_rollout_kernel<L.value, Z.value>)};
+                              reinterpret_cast<const void*>(&xr_rollout_kernel<L.value, Z.value>),
+                              reinterpret_cast<const void*>(&xr_rollout_weighted_kernel<L.value, Z.value>),
+                              reinterpret_cast<const void*>(&xr_peek_kernel<L.value, Z.value>)};
         for (const void* fn : fns) {
             const hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
             if (e != hipSuccess) return e;
@@ -2329,34 +2333,36 @@ hipError_t xr_launch_lookahead(const XrBatchDev* src, const XrBatchDev* shadow, 
     return hipGetLastError();
 }
 
-// rollouts (xr_rollout.h): the persistent launch; task t = (row t / n_rollouts, rollout t % n_rollouts)
-hipError_t xr_launch_rollout(const XrBatchDev* src, const XrBatchDev* shadow, int env_lo, int n_tasks, int n_rollouts, int policy, uint64_t seed,
-                             const int32_t* prefix, int prefix_stride, int max_plies, uint32_t* ctr, uint32_t* next_ctr, int32_t* out, double* return_out,
-                             uint64_t* hash_out, int32_t* order_out, int k_cap, XrRouteVariant v, int blocks, hipStream_t st) {
-    const dim3 g(blocks), t(v.threads);
-    xr_with_variant(v.lds_dist, v.zch, [&](auto L, auto Z) {
-        hipLaunchKernelGGL((xr_rollout_kernel<L.value, Z.value>), g, t, v.lds_bytes, st, *src, *shadow, env_lo, n_tasks, n_rollouts, policy, seed, prefix,
-                           prefix_stride, max_plies, ctr, next_ctr, out, return_out, hash_out, order_out, k_cap);
-    });
+// rollouts, weighted rollouts, peek (xr_rollout.h, xr_weighted.h, xr_peek.h): the persistent launch of the kind's kernel; task t =
+// (row t / per_row, line t % per_row).  Dynamic LDS above 64 KB: xr_route_set_max_lds has raised all three kernels' limits at load.
+// The kind is selected OUTSIDE xr_with_variant, one dispatch per kind in this order: the compiler emits kernels in the order their
+// dispatches are written, and one dispatch for all three would interleave the 36 instantiations in the code object
+hipError_t xr_launch_line(const XrLineLaunch* l, hipStream_t st) {
+    const XrRouteVariant& v = l->v;
+    const dim3 g(l->blocks), t(v.threads);
+    switch (l->kind) {
+    case XR_LINE_POLICY:
+        xr_with_variant(v.lds_dist, v.zch, [&](auto L, auto Z) {
+            hipLaunchKernelGGL((xr_rollout_kernel<L.value, Z.value>), g, t, v.lds_bytes, st, *l->src, *l->shadow, l->env_lo, l->n_tasks, l->per_row, l->policy, l->seed,
+                               l->prefix, l->prefix_stride, l->max_plies, l->ctr, l->next_ctr, l->out, l->return_out, l->hash_out, l->order_out, l->k_cap);
+        });
+        break;
+    case XR_LINE_PEEK:
+        xr_with_variant(v.lds_dist, v.zch, [&](auto L, auto Z) {
+            hipLaunchKernelGGL((xr_peek_kernel<L.value, Z.value>), g, t, v.lds_bytes, st, *l->src, *l->shadow, l->env_lo, l->n_tasks, l->per_row, l->prefix,
+                               l->prefix_stride, l->max_plies, l->ctr, l->next_ctr, l->rows, l->row_bytes, l->region_base, l->out, l->return_out, l->hash_out,
+                               l->order_out, l->k_cap);
+        });
+        break;
+    case XR_LINE_WEIGHTED:
+        xr_with_variant(v.lds_dist, v.zch, [&](auto L, auto Z) {
+            hipLaunchKernelGGL((xr_rollout_weighted_kernel<L.value, Z.value>), g, t, v.lds_bytes, st, *l->src, *l->shadow, l->env_lo, l->n_tasks, l->per_row, l->seed,
+                               l->prefix, l->prefix_stride, l->max_plies, l->ctr, l->next_ctr, l->out, l->return_out, l->hash_out, l->order_out, l->k_cap, l->weights,
+                               l->weights_k_cap);
+        });
+        break;
+    }
     return hipGetLastError();
-}
-
-// peek (xr_peek.h): the persistent launch; task t = (row t / n_lines, line t % n_lines).  A launch above 64 KB of dynamic LDS raises the
-// kernel's limit itself, as xr_launch_rollout_weighted does
-hipError_t xr_launch_peek(const XrBatchDev* src, const XrBatchDev* shadow, int env_lo, int n_tasks, int n_lines, const int32_t* prefix, int prefix_stride,
-                          int max_plies, uint32_t* ctr, uint32_t* next_ctr, uint8_t* rows, int64_t row_bytes, int region_base, int32_t* out,
-                          double* return_out, uint64_t* hash_out, int32_t* order_out, int k_cap, XrRouteVariant v, int blocks, hipStream_t st) {
-    const dim3 g(blocks), t(v.threads);
-    return xr_with_variant(v.lds_dist, v.zch, [&](auto L, auto Z) {
-        if (v.lds_bytes > 64 * 1024) {
-            const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&xr_peek_kernel<L.value, Z.value>),
-                                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)v.lds_bytes);
-            if (e != hipSuccess) return e;
-        }
-        hipLaunchKernelGGL((xr_peek_kernel<L.value, Z.value>), g, t, v.lds_bytes, st, *src, *shadow, env_lo, n_tasks, n_lines, prefix, prefix_stride,
-                           max_plies, ctr, next_ctr, rows, row_bytes, region_base, out, return_out, hash_out, order_out, k_cap);
-        return hipGetLastError();
-    });
 }
 
 // weighted net sampling (xr_weighted.h): one wave per env, four per workgroup; rows of `weights` / `actions` start at env_base
@@ -2364,25 +2370,6 @@ hipError_t xr_launch_weighted_actions(const XrBatchDev* b, const int32_t* weight
     const int n = XR_ENV_END(*b) - b->env_base;
     hipLaunchKernelGGL(xr_weighted_action_kernel, dim3((n + 3) / 4), dim3(256), 0, st, *b, weights, k_cap, actions, seed);
     return hipGetLastError();
-}
-
-// the rollout launch with the policy XR_ROLLOUT_WEIGHTED: xr_launch_rollout's shape.  A launch above 64 KB of dynamic LDS raises the
-// kernel's limit itself (xr_route_set_max_lds covers the kernels that were there before it)
-hipError_t xr_launch_rollout_weighted(const XrBatchDev* src, const XrBatchDev* shadow, int env_lo, int n_tasks, int n_rollouts, uint64_t seed,
-                                      const int32_t* prefix, int prefix_stride, int max_plies, uint32_t* ctr, uint32_t* next_ctr, int32_t* out,
-                                      double* return_out, uint64_t* hash_out, int32_t* order_out, int k_cap, const int32_t* weights, int weights_k_cap,
-                                      XrRouteVariant v, int blocks, hipStream_t st) {
-    const dim3 g(blocks), t(v.threads);
-    return xr_with_variant(v.lds_dist, v.zch, [&](auto L, auto Z) {
-        if (v.lds_bytes > 64 * 1024) {
-            const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&xr_rollout_weighted_kernel<L.value, Z.value>),
-                                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)v.lds_bytes);
-            if (e != hipSuccess) return e;
-        }
-        hipLaunchKernelGGL((xr_rollout_weighted_kernel<L.value, Z.value>), g, t, v.lds_bytes, st, *src, *shadow, env_lo, n_tasks, n_rollouts, seed, prefix,
-                           prefix_stride, max_plies, ctr, next_ctr, out, return_out, hash_out, order_out, k_cap, weights, weights_k_cap);
-        return hipGetLastError();
-    });
 }
 
 // branch (xr_branch.h): workgroup (i, c) = chunk c of row i; the stream orders the staging pass before the writing pass
