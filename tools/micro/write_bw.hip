@@ -1,6 +1,6 @@
 // Device write-bandwidth probe: what a pure-write kernel can sustain on this GPU as a function of footprint and of
 // the store pattern.  Build: hipcc --offload-arch=gfx950 -O3 -o write_bw write_bw.hip ; run: ./write_bw (every row) or ./write_bw slabs
-// (the slab-ticket rows only)
+// (the slab-ticket rows only) or ./write_bw heads (slab tickets from 1 or 8 ticket heads)
 #include <hip/hip_runtime.h>
 #include <cstdio>
 #include <cstdlib>
@@ -104,6 +104,79 @@ __global__ void __launch_bounds__(256) k_slab(float* __restrict__ base, const un
     }
 }
 
+// The same writer with H ticket heads (1 or 8, each in a 128-byte line of its own) and one claim kept ahead.  Head h = blockIdx.x & 7
+// hands out the dynamic tickets h, h + 8, h + 16, ...; a workgroup whose head is exhausted reads the other seven at once and moves on to
+// the next one that has tickets left (xr_claim_head_ticket of the step kernel).  LATE: the claim is issued after the ticket's stores
+// instead of before them.
+template <int T, int H, bool LATE>
+__global__ void __launch_bounds__(256) k_slab_heads(float* __restrict__ base, const unsigned* __restrict__ units, int nunits, size_t stride, int N,
+                                                    unsigned* __restrict__ heads) {
+    constexpr int S = (9 + T - 1) / T;
+    const f4 v = {1.f, 2.f, 3.f, 4.f};
+    __shared__ unsigned s_t;
+    const int tid = threadIdx.x;
+    const unsigned total = (unsigned)nunits * S, first = gridDim.x;
+    const int ngrp = N >> 2;
+    int hd = H == 1 ? 0 : (int)(blockIdx.x & 7);
+    auto claim = [&]() -> unsigned {
+        if (H == 1) return first + atomicAdd(heads, 1u);
+        for (;;) {
+            const unsigned t = first + 8u * atomicAdd(&heads[hd * 32], 1u) + (unsigned)hd;
+            if (t < total) return t;
+            unsigned c[7];
+#pragma unroll
+            for (int k = 1; k < 8; k++) c[k - 1] = __hip_atomic_load(&heads[((hd + k) & 7) * 32], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            int nh = -1;
+#pragma unroll
+            for (int k = 7; k >= 1; k--)
+                if (first + 8u * c[k - 1] + (unsigned)((hd + k) & 7) < total) nh = (hd + k) & 7;
+            if (nh < 0) return total;
+            hd = nh;
+        }
+    };
+    unsigned nx = blockIdx.x;
+    for (;;) {
+        if (tid == 0) s_t = nx;
+        __syncthreads();
+        const unsigned t = __builtin_amdgcn_readfirstlane(s_t);
+        __syncthreads();
+        if (t >= total) break;
+        if (!LATE && tid == 0) nx = claim();
+        const unsigned u = t / S, p = t % S;
+        const unsigned ent = units[u];
+        float* __restrict__ out = base + (size_t)(ent >> 14) * stride + (size_t)(2 + 7 * (ent & 0x3FFFu)) * N;
+#pragma unroll
+        for (int j = 0; j < T; j++) {
+            const int g = ((int)p * T + j) * 256 + tid;
+            if (g < ngrp) {
+                float* __restrict__ pp = out + ((size_t)g << 2);
+#pragma unroll
+                for (int pl = 0; pl < 7; pl++) __builtin_nontemporal_store(v, (f4*)(pp + (size_t)pl * N));
+            }
+        }
+        if (LATE && tid == 0) nx = claim();
+    }
+}
+
+template <int T, int H, bool LATE>
+static void run_slab_heads(float* base, const unsigned* units, int nunits, size_t stride, int N, unsigned* heads, hipEvent_t e0, hipEvent_t e1) {
+    const int grids[] = {512, 1024};
+    for (int G : grids) {
+        float best = 1e30f, worst = 0.f;
+        for (int rep = 0; rep < 4; rep++) {
+            CK(hipMemsetAsync(heads, 0, 8 * 128, 0));
+            CK(hipEventRecord(e0));
+            hipLaunchKernelGGL((k_slab_heads<T, H, LATE>), dim3(G), dim3(256), 0, 0, base, units, nunits, stride, N, heads);
+            CK(hipEventRecord(e1)); CK(hipEventSynchronize(e1));
+            float ms; CK(hipEventElapsedTime(&ms, e0, e1));
+            if (rep > 0) { if (ms < best) best = ms; if (ms > worst) worst = ms; }
+        }
+        const double wr = (double)nunits * 7 * N * 4;
+        printf("%5.1f GB  slab T=%d (%6.1f KB) heads=%d claim %-6s %4dx256  %8.3f ms  %6.2f TB/s  spread %.3f ms (%.1f %%)\n", wr / 1e9, T, T * 28.0, H,
+               LATE ? "after" : "before", G, best, wr / best / 1e9, worst - best, 100.0 * (worst - best) / best);
+    }
+}
+
 template <int T, int D>
 static void run_slab(float* base, const unsigned* units, int nunits, size_t stride, int N, unsigned* ctr, hipEvent_t e0, hipEvent_t e1) {
     const int grids[] = {512, 1024};
@@ -124,7 +197,7 @@ static void run_slab(float* base, const unsigned* units, int nunits, size_t stri
 }
 
 // the step's own span: 4096 rows of (2 + 7 * 36) * 8640 floats (8.78 MB, 36 GB in all), 2..19 units per row (10.4 GB written)
-static void slab_rows(hipEvent_t e0, hipEvent_t e1) {
+static void slab_rows(hipEvent_t e0, hipEvent_t e1, bool heads_rows) {
     const int rows = 4096, N = 8640;
     const size_t stride = (size_t)(2 + 7 * 36) * N;
     std::vector<unsigned> h;
@@ -135,10 +208,26 @@ static void slab_rows(hipEvent_t e0, hipEvent_t e1) {
     const int nunits = (int)h.size();
     float* base; unsigned *units, *ctr;
     if (hipMalloc(&base, rows * stride * 4) != hipSuccess) { printf("alloc of the 36 GB span failed\n"); return; }
-    CK(hipMalloc(&units, h.size() * 4)); CK(hipMalloc(&ctr, 4));
+    CK(hipMalloc(&units, h.size() * 4)); CK(hipMalloc(&ctr, 8 * 128));
     CK(hipMemcpy(units, h.data(), h.size() * 4, hipMemcpyHostToDevice));
     printf("# slab tickets: %d units of %d B over %d rows %zu B apart, best of 3 timed launches (spread = worst - best)\n", nunits, 7 * N * 4, rows,
            stride * 4);
+    if (heads_rows) {       // ./write_bw heads: T x heads x claim placement, one claim ahead, and hipMemset of the same byte count
+#define HEADS_ROWS(T) run_slab_heads<T, 1, false>(base, units, nunits, stride, N, ctr, e0, e1); run_slab_heads<T, 1, true>(base, units, nunits, stride, N, ctr, e0, e1); \
+                      run_slab_heads<T, 8, false>(base, units, nunits, stride, N, ctr, e0, e1); run_slab_heads<T, 8, true>(base, units, nunits, stride, N, ctr, e0, e1)
+        HEADS_ROWS(3); HEADS_ROWS(2); HEADS_ROWS(1);
+#undef HEADS_ROWS
+        const size_t wr = (size_t)nunits * 7 * N * 4;
+        float best = 1e30f, worst = 0.f;
+        for (int rep = 0; rep < 4; rep++) {
+            CK(hipEventRecord(e0)); CK(hipMemsetAsync(base, 0, wr, 0)); CK(hipEventRecord(e1)); CK(hipEventSynchronize(e1));
+            float ms; CK(hipEventElapsedTime(&ms, e0, e1));
+            if (rep > 0) { if (ms < best) best = ms; if (ms > worst) worst = ms; }
+        }
+        printf("%5.1f GB  hipMemset (contiguous)  %8.3f ms  %6.2f TB/s  spread %.3f ms\n", wr / 1e9, best, wr / best / 1e9, worst - best);
+        CK(hipFree(base)); CK(hipFree(units)); CK(hipFree(ctr));
+        return;
+    }
     run_slab<9, 1>(base, units, nunits, stride, N, ctr, e0, e1);
     run_slab<9, 2>(base, units, nunits, stride, N, ctr, e0, e1);
     run_slab<9, 4>(base, units, nunits, stride, N, ctr, e0, e1);
@@ -154,7 +243,8 @@ static void slab_rows(hipEvent_t e0, hipEvent_t e1) {
 int main(int argc, char** argv) {
     const double gbs[] = {4.0, 10.9, 36.0};
     hipEvent_t e0, e1; CK(hipEventCreate(&e0)); CK(hipEventCreate(&e1));
-    if (argc > 1 && argv[1][0] == 's') { slab_rows(e0, e1); return 0; }      // ./write_bw slabs: the slab-ticket rows only
+    if (argc > 1 && argv[1][0] == 's') { slab_rows(e0, e1, false); return 0; }      // ./write_bw slabs: the slab-ticket rows only
+    if (argc > 1 && argv[1][0] == 'h') { slab_rows(e0, e1, true); return 0; }       // ./write_bw heads: 1 or 8 ticket heads, claim before / after the stores
     for (double gb : gbs) {
         size_t bytes = (size_t)(gb * 1e9) & ~(size_t)((1 << 22) - 1);
         f4* p; if (hipMalloc(&p, bytes) != hipSuccess) { printf("alloc %.1f GB failed\n", gb); continue; }
@@ -197,6 +287,6 @@ int main(int argc, char** argv) {
         }
         CK(hipFree(p));
     }
-    slab_rows(e0, e1);
+    slab_rows(e0, e1, false);
     return 0;
 }

@@ -1802,6 +1802,9 @@ constexpr int XR_QUEUE_BATCH = 1;      // tickets a workgroup claims per atomic 
 // (profiles/step_ticket_slabs_ab.json).  The pure-write micro (tools/micro/write_bw.hip slabs, profiles/step_ticket_slabs_micro.txt) has 3
 // level with 9 at 1024 writers and +0.8 % at 512; 1 is bound by the claim rate of one counter word (88 M/s: 2.4 TB/s); claims kept 2 or
 // 4 ahead are 1-4 % slower at every ticket size, so the claim stays one ahead.
+// Per-XCD ticket heads (eight counters, interleaved tickets, stealing) lift the claim-rate bound of 1- and 2-tile tickets for pure writers
+// and lose at every ticket size in the step (-4.3 % alone, -2.1 % with the claim after the stores; 2 tiles -3.3 %, 1 tile -13.8 %):
+// one counter word stays (LAB_NOTES.md §21, profiles/step_ticket_heads_micro.txt, tools/archive/xr_ticket_heads.patch).
 constexpr int XR_TICKET_TILES = 3;
 static_assert(XR_TICKET_TILES >= 1 && XR_TICKET_TILES <= XR_NP_J, "a slab is one pass of xr_unit_aligned");
 // Static first tasks of the queue form (see xr_step_queue_kernel): of G workgroups, those with bit `sh` of their index clear start with
@@ -1865,6 +1868,7 @@ __device__ __forceinline__ void xr_step_queue_body(XrBatchDev& b, const int32_t*
         if ((int64_t)units * S > 0x7FF00000LL) S = 1;
     }
     const int total = units * S;                        // tickets of this launch
+    const bool claim_late = S > 1;                      // slab tickets: the next claim is issued AFTER the current ticket's stores (below)
     // (after a route: 0.75 x the average BYTES per env, whatever the ticket size)
     const int quota = S * max(1, (int)(((int64_t)units * b.queue_quota_pm) / (1000 * (int64_t)B)));
     bool routes_left = true, units_left = total > 0;
@@ -1913,14 +1917,19 @@ __device__ __forceinline__ void xr_step_queue_body(XrBatchDev& b, const int32_t*
         }
         skip_route = false;
         if (units_left) {
-            // the next claim is issued before the current ticket is written (an atomic round trip costs ~4 us, a whole unit ~20 us, a
-            // 3-tile slab ~5 us); claiming several at once measured slower (XR_QUEUE_BATCH), and so did whole units as tickets
-            // (XR_TICKET_TILES)
+            // One claim is kept ahead: thread 0 asks for the next ticket while the current one is written (an atomic round trip costs
+            // 1-4 us, a whole unit ~20 us, a 3-tile slab ~5 us).  Where in the ticket it asks matters: the compiler follows the returning
+            // atomic at once with s_waitcnt vmcnt(0) (its result goes through v_readfirstlane), so a claim issued BEFORE the ticket's stores
+            // has wave 0 wait out the round trip with none of them issued while the other waves stream (the S = 1 launches keep that
+            // order: only slab tickets were measured the other way), and a claim issued AFTER them (slab tickets) waits with the wave's
+            // stores in flight, in a wait that the next ticket's descriptor loads would impose anyway: +3.3 % and +4.5 % env-steps/s at 4096
+            // envs on two machines (LAB_NOTES.md §21).  Claiming several at once measured slower (XR_QUEUE_BATCH), and so did whole units as tickets
+            // (XR_TICKET_TILES).
             const int nb = routes_left ? max(1, quota / XR_QUEUE_BATCH) : (1 << 30);
             unsigned nx = 0;
             const unsigned ubase = (unsigned)first_u * (unsigned)XR_QUEUE_BATCH;
-            if (tid == 0) nx = (my_first >= 0 && unit_first) ? (unsigned)my_first * (unsigned)XR_QUEUE_BATCH
-                                                             : ubase + atomicAdd(&b.queue[1], (unsigned)XR_QUEUE_BATCH);
+            auto claim = [&]() -> unsigned { return ubase + atomicAdd(&b.queue[1], (unsigned)XR_QUEUE_BATCH); };
+            if (tid == 0) nx = (my_first >= 0 && unit_first) ? (unsigned)my_first * (unsigned)XR_QUEUE_BATCH : claim();
             if (unit_first) my_first = -1;
             for (int i = 0; i < nb; i++) {
                 if (tid == 0) s_task = (int)nx;
@@ -1928,7 +1937,7 @@ __device__ __forceinline__ void xr_step_queue_body(XrBatchDev& b, const int32_t*
                 const int u0 = s_task;
                 xr_lds_barrier();
                 if (u0 >= total) { units_left = false; break; }
-                if (tid == 0 && i + 1 < nb) nx = ubase + atomicAdd(&b.queue[1], (unsigned)XR_QUEUE_BATCH);     // used after this batch
+                if (!claim_late && tid == 0 && i + 1 < nb) nx = claim();     // used after this batch
 #ifdef XR_TIMELINE
                 const long long t0 = XR_TL_NOW();
 #endif
@@ -1949,6 +1958,7 @@ __device__ __forceinline__ void xr_step_queue_body(XrBatchDev& b, const int32_t*
 #ifdef XR_TIMELINE
                 tl_unit += XR_TL_NOW() - t0; tl_nu += u1 - u0;
 #endif
+                if (claim_late && tid == 0 && i + 1 < nb) nx = claim();       // (after the timeline's stamp: a claim counts as `other`)
             }
             xr_lds_barrier();
         }
