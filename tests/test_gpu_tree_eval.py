@@ -193,6 +193,43 @@ def test_values_from_rollouts_reproduce_tree_search_bit_for_bit(n_par):
     assert (want["info"][:, 2] >= 2).any()
 
 
+def test_wide_blocks_entered_within_their_wave_as_the_pool_runs_out_match_across_forms():
+    """Blocks wider than a wavefront, made by one lane of a wave and entered by a later lane of the same wave, in a pool that runs out
+    part-way: the rollout search and the evaluated session fed with rollout returns, bit for bit.  All the prior's weight is on two nets,
+    so in wave 0 lane 0 takes the lowest net (E[0] == 0: a tie), lane 1 the heavier net, and lane 2 follows lane 1 into the block lane 1
+    has just made; the pool holds the root, its block and those two blocks, so lane 2's own block is the one that does not fit.
+    best_return is compared with what each form's spec says of it, not across the forms: with more than 128 legal nets and 6 simulations
+    no line of the session ends the episode, so the session's best terminal line is -inf, while the rollout search's is its highest G."""
+    from tests.helpers import OBS_MANY_NETS
+    b = RegionBatch([generate_region(9300, **OBS_MANY_NETS)], n_envs=1, device=DEV)
+    assert b.legal_words >= 4
+    b.reset()
+    nets = _legal_rows(b)[0]
+    nlegal, K = len(nets), b.k_max
+    assert nlegal > 128
+    prior = torch.zeros((1, K), dtype=torch.float32, device=DEV)          # test_a_region_with_several_legal_words' prior
+    prior[0, nets[-1] - 1] = 5.0
+    prior[0, nets[70] - 1] = 1.0
+    n_par, W = 3, 2
+    cap = 1 + nlegal + 2 * (nlegal - 1)                                    # the root, its block, exactly two second-level blocks
+    want = _np(b.tree_search(W, n_par, SEED, prior=prior, node_cap=cap, trace=True))
+    b.tree_open(n_par, W * n_par, prior, cap)
+    paths, returns = [], []
+    for w in range(W):
+        lv = b.tree_leaves()
+        ro = b.rollout(n_par, _lib.tree_seed(SEED, w), prefix=lv["paths"])
+        assert bool(((ro["ret"] * 2.0) == torch.round(ro["ret"] * 2.0)).all())
+        res = b.tree_backup((ro["ret"] - lv["ret"]).contiguous(), None)
+        paths.append(lv["paths"]); returns.append(res["returns"])
+    got = _np(dict(res, paths=torch.cat(paths, dim=1), returns=torch.cat(returns, dim=1)))
+    for k in ("visits", "value", "info", "paths", "returns"):
+        _same(got[k], want[k], k)
+    _same(want["best_return"], want["returns"].max(axis=1), "best_return, rollout search")
+    assert (got["best_return"] == -np.inf).all()
+    assert (want["info"][:, 3] == FULL).all() and (want["info"][:, 2] >= 2).all() and (want["info"][:, 1] == cap).all()
+    assert ((want["paths"][0, 1:n_par] > 0).sum(axis=1) == 2).any()       # a later lane of wave 0 went through a block made in wave 0
+
+
 # ---- 4. edges -----------------------------------------------------------------------------------------------------------------------
 def test_a_region_with_more_than_64_nets():
     wide = generate_region(9400, dims=(23, 15, 5), k_range=(66, 70), net_span=6, pins=(2, 2), aps=(1, 1))

@@ -18,6 +18,7 @@
 //   xr_tree_keep_begin_kernel      (xr_tree_keep.h) the first kernel of a search that continues from the played net's subtree
 //   xr_tree_eval_open / select / backup_kernel   (xr_tree_eval.h) the search whose leaves the caller's evaluator values
 //   xr_tree_reset / select / backup_kernel   (xr_tree.h) pUCT over net orderings with the tree in device memory, one wavefront per row
+//                                (xr_tree_core.h) the tree's rules, once, for the three forms above
 //   xr_random_action_kernel
 //   xr_weighted_action_kernel    (xr_weighted.h) XR-Pick v1: a legal net drawn in proportion to caller-supplied integer weights, one wave per env
 //   xr_rollout_weighted_kernel   (xr_weighted.h) the rollout whose policy is that pick
@@ -2214,6 +2215,7 @@ __global__ void __launch_bounds__(256) xr_expand_state_kernel(XrBatchDev b, cons
 #include "xr_rollout.h"
 #include "xr_peek.h"
 #include "xr_weighted.h"
+#include "xr_tree_core.h"
 #include "xr_tree.h"
 #include "xr_tree_keep.h"
 #include "xr_tree_eval.h"

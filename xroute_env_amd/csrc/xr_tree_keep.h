@@ -1,6 +1,7 @@
 // xr_tree_keep.h — kept trees (xr_batch_tree_search_keep, "XR-Tree v1, kept" of include/xroute_hip.h): the first kernel of a search that
 // continues from the tree its caller's last kept call left.  Included by xr_kernels.hip after xr_tree.h; select, the rollout launch and
-// backup of the call are xr_tree.h's, run on the half this kernel fills.
+// backup of the call are xr_tree.h's, run on the half this kernel fills.  Clearing the outputs, the rebuilt root, the lookup of the
+// played net's child and the expansion are xr_tree_core.h's; the key and the compaction are this file's own.
 //
 //   xr_tree_keep_begin_kernel   clears the row's outputs, checks the row's key against the env, then either copies the subtree below the
 //                               played net from the old half into the new one (breadth first, returns shifted by the step's reward),
@@ -40,18 +41,10 @@ __global__ void __launch_bounds__(64) xr_tree_keep_begin_kernel(XrBatchDev src, 
     const int words = src.legal_words;
     const double ninf = -__builtin_inf();
     // 1. the row's outputs
-    for (int k = lane; k < t.k_cap; k += 64) {
-        t.visits_out[(int64_t)row * t.k_cap + k] = 0;
-        t.value_out[(int64_t)row * t.k_cap + k] = ninf;
-        if (t.best_order_out) t.best_order_out[(int64_t)row * t.k_cap + k] = 0;
-    }
-    if (lane == 0) {
-        int32_t* info = t.info_out + (int64_t)row * 4;
-        info[0] = 0; info[1] = 0; info[2] = 0; info[3] = 0;
-        if (t.best_return_out) t.best_return_out[row] = ninf;
-    }
+    xr_tree_clear_outputs(t.visits_out, t.value_out, t.best_order_out, t.info_out, t.best_return_out, row, t.k_cap, lane);
     XrTreeRow* const rs = t.rs + row;
     XrTreeNode* const nodes = t.nodes + (int64_t)row * t.node_cap;
+    const XrTreeView v = {nodes, rs, t.node_cap, t.k_cap, words, lane};
     const XrTreeNode* const old = kp.old_nodes + (int64_t)row * t.node_cap;
     XrTreeKey* const key = kp.key + row;
     uint64_t* const klegal = kp.key_legal + (int64_t)row * words;
@@ -86,14 +79,7 @@ __global__ void __launch_bounds__(64) xr_tree_keep_begin_kernel(XrBatchDev src, 
                 const int first = __builtin_amdgcn_readfirstlane(old[0].first);
                 const int cnt = __builtin_amdgcn_readfirstlane(old[0].count);
                 if (first >= 1 && cnt >= 1 && (int64_t)first + cnt <= used_old) {
-                    int found = 0x7FFFFFFF;
-                    for (int c = lane; c < cnt; c += 64)
-                        if (old[first + c].net == a && c < found) found = c;
-                    for (int off = 32; off > 0; off >>= 1) {
-                        const int o = __shfl_xor(found, off, 64);
-                        found = o < found ? o : found;
-                    }
-                    found = __builtin_amdgcn_readfirstlane(found);
+                    const int found = xr_tree_child_by_net(old, first, cnt, a, lane);
                     if (found < cnt) {
                         child = first + found;
                         if ((int64_t)old[child].N + kp.n_add <= XR_TREE_MAX_SIMS) mode = 2;
@@ -107,16 +93,7 @@ __global__ void __launch_bounds__(64) xr_tree_keep_begin_kernel(XrBatchDev src, 
     // 3. the tree
     int kept_n = 0, kept_nodes = 0;
     if (mode == 0) {
-        if (lane == 0) {
-            rs->mn = __builtin_inf(); rs->mx = ninf; rs->best = ninf;
-            rs->used = 0; rs->max_depth = 0; rs->flags = 0; rs->pad = 0;
-            if (nl0 > 0) {
-                XrTreeNode root;
-                root.W = 0.0; root.P = 1.0; root.N = 0; root.V = 0; root.first = -1; root.count = 0; root.net = 0; root.pad = 0;
-                nodes[0] = root;
-                rs->used = 1;
-            }
-        }
+        if (lane == 0) xr_tree_init_row(v, nl0);
     } else if (mode == 1) {
         for (int i = lane; i < used_old; i += 64) nodes[i] = old[i];
         kept_n = old[0].N;
@@ -167,8 +144,9 @@ __global__ void __launch_bounds__(64) xr_tree_keep_begin_kernel(XrBatchDev src, 
     }
     __syncthreads();
     // 4. an unexpanded root (a rebuilt row's, or a kept child no simulation has left yet) gets its children under this call's prior
-    if (lane == 0 && nl0 > 0 && nodes[0].first < 0)
-        xr_tree_expand(t, nodes, rs, 0, legal, nullptr, words, nl0, t.prior ? t.prior + (int64_t)row * t.k_cap : nullptr);
+    // (every lane; the block's next reader is the next kernel)
+    if (nl0 > 0 && __builtin_amdgcn_readfirstlane(nodes[0].first) < 0)
+        xr_tree_expand_block(v, 0, legal, nullptr, nl0, t.prior ? t.prior + (int64_t)row * t.k_cap : nullptr);
     // 5. the key of the state this tree belongs to
     for (int wd = lane; wd < words; wd += 64) klegal[wd] = legal[wd];
     if (lane == 0) {
