@@ -12,7 +12,12 @@ THE NETWORK IS UNTRAINED: a seeded, randomly initialised ActorCritic.  Its value
 so the evaluated-tree row says nothing about what a trained network would do — this example shows the plumbing (per wave: select, peek,
 expand, tower + critic + actor head, backup, all enqueue-only), not a result.
 
-    python examples/network_tree.py [regions=64] [waves=4] [lanes=4]
+With --reuse the evaluated tree is also played with tree reuse ("XR-Tree v2, kept": `envs.tree_eval.evaluated_episodes(reuse=True)`,
+RegionBatch.tree_open(keep=True, played=...)): the session of a ply continues from the subtree below the net just stepped.  Beside the
+fresh episodes it prints the visits and nodes the kept trees carried per ply and the nets the simulations routed.  The network is the
+same UNTRAINED one: these numbers, too, show plumbing, not quality.
+
+    python examples/network_tree.py [regions=64] [waves=4] [lanes=4] [--reuse]
 """
 import argparse
 import os, sys
@@ -22,7 +27,7 @@ import torch
 
 from xroute_env_amd.agents import ActorCritic, GroupedFusedPolicy
 from xroute_env_amd.envs import peek as pk
-from xroute_env_amd.envs.tree_eval import actor_critic_evaluator, evaluated_search
+from xroute_env_amd.envs.tree_eval import actor_critic_evaluator, evaluated_episodes, evaluated_search
 from xroute_env_amd.envs.vector_env import XRouteVectorEnv
 from xroute_env_amd.lefdef import load_region_pack
 
@@ -30,6 +35,7 @@ ap = argparse.ArgumentParser()
 ap.add_argument("regions", nargs="?", type=int, default=64)
 ap.add_argument("waves", nargs="?", type=int, default=4)
 ap.add_argument("lanes", nargs="?", type=int, default=4)
+ap.add_argument("--reuse", action="store_true", help="also play the evaluated tree with tree reuse (XR-Tree v2, kept)")
 a = ap.parse_args()
 pack = load_region_pack(os.path.join(ROOT, "tests", "golden", "ispd18_test1_regions.npz"))[:a.regions]
 R = len(pack)
@@ -76,3 +82,14 @@ for policy, name in (("random", "random"), ("greedy", "greedy"), ("tree", "tree 
     cost, routed = play(policy)
     extra = f", {routed} nets routed by its simulations" if routed else ""
     print(f"{name:40s} ordering: mean episode cost {cost:.1f} over {R} regions{extra}")
+
+if a.reuse:
+    print("tree reuse (UNTRAINED network: plumbing, not quality) — episodes of evaluated_episodes, fresh sessions beside reopened ones:")
+    for reuse in (False, True):
+        stats = {}
+        out = evaluated_episodes(pack, actor_critic_evaluator(model), a.waves, a.lanes, device=DEV, stats=stats, reuse=reuse)
+        cost = -sum(o["ret"] for o in out) / len(out)
+        line = f"{'reopened' if reuse else 'fresh':10s} sessions: mean episode cost {cost:.1f}, {stats['routed_nets']} nets routed by the simulations of {stats['plies']} plies"
+        if reuse:
+            line += f", carried per ply {stats['carried_visits'] / stats['plies']:.2f} visits and {stats['carried_nodes'] / stats['plies']:.2f} nodes"
+        print(line)

@@ -827,7 +827,9 @@ int32_t xr_batch_tree_search_keep(xr_batch* b, int32_t group, const int32_t* pla
  * in-place observation buffers is kept.  Sessions of DIFFERENT groups may be in flight at once on different streams; within one group
  * (or for the whole batch) the calls of a session, other searches, peeks, rollouts, lookaheads, branches and steps are ordered by the
  * caller, and so is the evaluator: it runs on `stream`, or is ordered against it by the caller.
- * Cuts: no Dirichlet noise, no discounting, no kept tree for this form (a session starts from an empty tree), no HBM-scratch forms. */
+ * A session started by xr_batch_tree_open is not keyed (see xr_batch_tree_reopen below): the next reopen rebuilds every row.
+ * Cuts: no Dirichlet noise, no discounting, no HBM-scratch forms; no kept tree for this form in a session started by
+ * xr_batch_tree_open (it starts from an empty tree): the kept tree is xr_batch_tree_reopen's ("XR-Tree v2, kept", below). */
 #define XR_TREE_LEAF_TERMINAL 1
 #define XR_TREE_LEAF_FRESH 2
 #define XR_TREE_LEAF_NONE 4
@@ -838,6 +840,60 @@ int32_t xr_batch_tree_leaves(xr_batch* b, int32_t group, uint8_t* rows_out_dev, 
 int32_t xr_batch_tree_backup(xr_batch* b, int32_t group, const double* value_dev, const float* leaf_prior_dev,
                              int32_t* visits_out_dev, double* value_out_dev, int32_t* info_out_dev,
                              int32_t* best_order_out_dev, double* best_return_out_dev, double* returns_out_dev, void* stream);
+
+/* ---- kept evaluated trees: a session that continues after a real step ---- */
+/* xr_batch_tree_reopen is xr_batch_tree_open in every argument the two share: the same checks in the same order and the same error
+ * codes (every message names xr_batch_tree_reopen), the same refusal of the HBM-scratch forms and of stream_per_region, the
+ * enqueue-only contract and the no-trace contract, the same caller's evaluated-tree pool.  It ends the pool's last session and starts
+ * a new one; xr_batch_tree_leaves and xr_batch_tree_backup then run on that session unchanged.  What differs is where the new session's
+ * trees come from: the subtree below the net the env has really played since the last session.  "XR-Tree v2, kept" — "XR-Tree v1, kept"
+ * (the kept trees section above) carried over to this pool:
+ *   Key.     A session started by reopen is KEYED: its first kernel ends by writing, per row, the env's env_steps, region, replay and a
+ *            valid bit.  The session's snapshot of the legal words is the key's legal words: there is no second copy.  A session started
+ *            by xr_batch_tree_open is not keyed.
+ *   Host-side rebuild of every row.  The kernel receives played == NULL when played_dev is NULL (a fresh session that leaves a keyed
+ *            tree behind); when the pool's last session was not keyed; when that session still has leaves waiting for a backup (pending
+ *            visits V are in its nodes); when rows, the group's first slot, node_cap, k_cap, legal_words or n_par differ from that
+ *            session's; and when the pool had to be allocated again.  max_sims, c_init, c_base and the prior may differ.  After
+ *            xr_batch_set_groups or xr_batch_load_regions every row is rebuilt.
+ *   played_dev.  Otherwise int32 [rows], a = played[row]:
+ *            a == 0: the row is kept whole if the key is valid, equals the env's current env_steps, region, replay and legal words
+ *            exactly, and the kept root's N + max_sims <= XR_TREE_MAX_SIMS.
+ *            a > 0: the row is re-rooted if all of these hold: the key is valid; region and replay are equal; env_steps ==
+ *            key.env_steps + 1; bit a is set in the key's legal words; the env's legal words equal the key's with bit a cleared; the kept
+ *            root is expanded and has a child of net a; that child's N + max_sims <= XR_TREE_MAX_SIMS.
+ *            Otherwise, and for any negative entry, the row is rebuilt exactly as xr_batch_tree_open builds it.  A rebuild is never an
+ *            error.
+ *   Re-rooting (normative, node numbering included).  New node 0 is the old child of a, with net = 0 and P = 1.0.  The new nodes are
+ *            then taken in index order, and the children block of every expanded one is appended in its old (ascending net) order: a
+ *            breadth-first compaction.  Let r be the slot's reward row (the reward of the step that played a).  Every copied node gets
+ *            W' = W - (double)N * r: one multiplication, then one subtraction, each rounded on its own, contraction off; N, P, net and
+ *            count are kept, V is 0.  The row state gets min' = min - r and max' = max - r (infinities stay).  With a == 0 nothing is
+ *            shifted or renumbered.  In both cases best restarts at -inf and the pool's best order at all 0, max_depth restarts at 0, the
+ *            flags become XR_TREE_KEPT alone, the snapshot (nlegal, legal words) becomes the env's current one, and the pool's row prior
+ *            becomes this call's root_prior_dev (uniform when NULL): it serves the new expansions of this session.  Kept nodes keep the
+ *            P they have, a P an evaluator's leaf prior gave them included.  A new root that is unexpanded is expanded at once under this
+ *            call's prior.  A carried node is never FRESH again, so a leaf prior never overwrites its block.  A row whose env has no
+ *            legal net is a done row: v1's empty result, kept {0, 0}.
+ *   Table and counting.  A reopen session indexes E[0 .. XR_TREE_MAX_SIMS], the kept search's formula, uploaded once per (c_init,
+ *            c_base): Select never clamps at a carried root.  The session's simulation counter starts at 0: max_sims bounds THIS
+ *            session's simulations, xr_batch_tree_leaves refuses the wave that would pass it, and info[0] is this session's
+ *            simulations.  visits_out / value_out show the root's children with the carried visits included, in the current frame.
+ *   kept_out_dev.  NULL, or int32 [rows][2] = {N of the new root before this session's simulations, nodes carried}; {0, 0} for a
+ *            rebuilt row.
+ *   Memory.  The pool of a keyed session holds two halves of rows x node_cap nodes (a reopen re-roots from the half the last session
+ *            searched in into the other one) and a key per row beside what a plain session holds:
+ *            rows x (80 node_cap + 40 + n_par x (4 k_cap + 16) + 8 k_cap + 8 legal_words + 4 + 24) bytes, each of its eleven arrays (the
+ *            two halves, row states, paths, line returns, leaf records, best order, legal words, nlegal, prior, keys) rounded up to 16,
+ *            allocated again when a call needs more than any before it, plus 8 x (XR_TREE_MAX_SIMS + 1) bytes per distinct (c_init,
+ *            c_base) for the table.  xr_batch_tree_open keeps its own formula and carve of the same allocation.  A reopen that has to
+ *            allocate has nothing to keep and rebuilds every row.
+ * Cuts: the best line does not carry (best_order and best_return are this session's terminal simulations' alone); at most one real
+ * route between two sessions (a row whose env made two is rebuilt); a tree does not follow xr_batch_branch to another slot; an abandoned
+ * wave (leaves without backup) forfeits the tree. */
+int32_t xr_batch_tree_reopen(xr_batch* b, int32_t group, const int32_t* played_dev,
+                             int32_t n_par, int32_t node_cap, double c_init, double c_base, int32_t max_sims,
+                             const float* root_prior_dev, int32_t k_cap, int32_t* kept_out_dev, void* stream);
 
 /* ---- XR-Maze v2: global-route guides (optional) ---------------------------------------------- */
 /* The reference's simulator runs with `-follow_guide 1` (ispd/ispd18_test1/run-net-ordering-training.tcl:3) on the guide file

@@ -39,7 +39,7 @@ SYMBOLS = [
     "xr_tree_exploration_table", "xr_batch_tree_search",
     "xr_batch_weighted_actions", "xr_batch_rollout_weighted", "xr_batch_tree_search_weighted",
     "xr_batch_tree_search_keep",
-    "xr_batch_tree_open", "xr_batch_tree_leaves", "xr_batch_tree_backup",
+    "xr_batch_tree_open", "xr_batch_tree_leaves", "xr_batch_tree_backup", "xr_batch_tree_reopen",
     "xr_observation_from_records", "xr_proto_decode", "xr_proto_encode_response", "xr_proto_encode_request",
 ]
 
@@ -167,7 +167,8 @@ def lib():
     L.xr_batch_tree_search_keep.argtypes = [vp, C.c_int32, vp, C.c_int32, C.c_int32, C.c_uint64, vp, C.c_int32, C.c_double, C.c_double,
                                             vp, vp, C.c_int32, vp, vp, vp, vp, vp, vp, vp, vp]
     L.xr_batch_tree_open.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32, C.c_double, C.c_double, C.c_int32, vp, C.c_int32, vp]
-    L.xr_batch_tree_leaves.argtypes = [vp, C.c_int32, vp, C.c_int64, C.c_int32, vp, vp, vp, vp, vp]
+    L.xr_batch_tree_reopen.argtypes = [vp, C.c_int32, vp, C.c_int32, C.c_int32, C.c_double, C.c_double, C.c_int32, vp, C.c_int32, vp, vp]
+    L.xr_batch_tree_leaves.argtypes =[vp, C.c_int32, vp, C.c_int64, C.c_int32, vp, vp, vp, vp, vp]
     L.xr_batch_tree_backup.argtypes = [vp, C.c_int32, vp, vp, vp, vp, vp, vp, vp, vp, vp]
     L.xr_batch_random_actions_group.argtypes = [vp, C.c_int32, vp, C.c_uint64, vp]
     L.xr_batch_fetch_group.argtypes = [vp, C.c_int32, C.c_int32, vp, C.c_size_t, vp]

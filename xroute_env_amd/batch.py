@@ -588,14 +588,24 @@ class RegionBatch:
         return C.c_void_p(t.data_ptr())
 
     def tree_open(self, n_par: int, max_sims: int, root_prior: Optional[torch.Tensor] = None, node_cap: Optional[int] = None,
-                  c_init: float = 1.25, c_base: float = 19652.0, group: Optional[int] = None, stream=None) -> None:
+                  c_init: float = 1.25, c_base: float = 19652.0, group: Optional[int] = None, stream=None, keep: bool = False,
+                  played: Optional[torch.Tensor] = None) -> Optional[torch.Tensor]:
         """Start a session of "XR-Tree v2, evaluated" (include/xroute_hip.h) from the state every env is in now: a tree per row whose
         simulations stop at the selected leaf; tree_leaves() hands out a wave's leaves as packed state rows, the caller's evaluator values
         them, tree_backup() takes the values.  n_par: lanes per wave (1..XR_PEEK_MAX); max_sims: the simulations the session may run
         (n_par..XR_TREE_MAX_SIMS); root_prior: None (uniform) or float32 [rows, k_max] weights per net, the prior of every block the
         search expands until an evaluator's leaf prior replaces it; node_cap: nodes per row, default 1 + (max_sims + 1) * k_max (always
         enough).  The env's legal set is copied: a caller who steps the env before the last tree_backup must open again.  Enqueue-only;
-        the batch is left exactly as it was.  group: an env group (rows = its slots, enqueued on `stream`); None: the whole batch."""
+        the batch is left exactly as it was.  group: an env group (rows = its slots, enqueued on `stream`); None: the whole batch.
+        keep=True: the session of "XR-Tree v2, kept" (xr_batch_tree_reopen): it is keyed to the state it starts from, and continues from
+        the tree the caller's last keyed session left where `played` says how the env has moved since — None: every row starts over;
+        int32 [rows]: 0 the env has not moved, a > 0 the env has made exactly one step, of net a; a row whose key does not agree (and any
+        negative entry) starts over.  max_sims then bounds this session's simulations.  Returns `kept` int32 [rows, 2] = {visits of the
+        new root carried in, nodes carried} (None without keep); info's flags carry XR_TREE_KEPT.  node_cap is part of the pool's shape
+        (a reopen with another one starts every row over); its default with keep is 1 + 4 * (max_sims + 1) * k_max, room for what a
+        tree carries along."""
+        if played is not None and not keep:
+            raise ValueError("played needs keep=True")
         g, rows = self._tree_rows(group)
         P, M = int(n_par), int(max_sims)
         if not 1 <= P <= _lib.XR_PEEK_MAX:
@@ -610,15 +620,24 @@ class RegionBatch:
         if not (math.isfinite(cb) and cb > 0):
             raise ValueError(f"c_base must be finite and > 0, got {c_base}")
         k = max(int(self.k_max), 1)
-        cap = 1 + (M + 1) * k if node_cap is None else int(node_cap)
+        cap = 1 + (4 if keep else 1) * (M + 1) * k if node_cap is None else int(node_cap)
         if not 1 <= cap < 2 ** 31:
             raise ValueError(f"node_cap must be in 1..2^31 - 1, got {node_cap}")
         pp = self._tree_tensor(root_prior, "root_prior", torch.float32, (rows, k)) if root_prior is not None else None
+        pl = self._tree_tensor(played, "played", torch.int32, (rows,)) if played is not None else None
+        kept = None
+        if keep:
+            with torch.cuda.stream(stream if stream is not None else torch.cuda.current_stream(self.device)):
+                kept = torch.empty((rows, 2), dtype=torch.int32, device=self.device)
         with torch.cuda.device(self.device):
-            _lib.check(self.L.xr_batch_tree_open(self._h, g, P, cap, ci, cb, M, pp, k, self._stream_arg(stream)))
+            if keep:
+                _lib.check(self.L.xr_batch_tree_reopen(self._h, g, pl, P, cap, ci, cb, M, pp, k, C.c_void_p(kept.data_ptr()), self._stream_arg(stream)))
+            else:
+                _lib.check(self.L.xr_batch_tree_open(self._h, g, P, cap, ci, cb, M, pp, k, self._stream_arg(stream)))
         if not hasattr(self, "_tree_sessions"):
             self._tree_sessions = {}
         self._tree_sessions[g] = P
+        return kept
 
     def _tree_session(self, group, fn: str):
         g, rows = self._tree_rows(group)

@@ -203,14 +203,22 @@ struct xr_batch {
     } keep[1 + XR_MAX_GROUPS];
     // evaluated tree search (xr_batch_tree_open / _leaves / _backup): a pool of its own per caller, indexed like tree[].  One session lives
     // here from its open call on: the trees, the snapshot of the legal words, one wave's paths, line returns and leaf records (`d` is the
-    // view the kernels get), and on the host the session's shape, its simulations so far and whether a wave waits for its backup
+    // view the kernels get), and on the host the session's shape, its simulations so far and whether a wave waits for its backup.  A
+    // session started by xr_batch_tree_reopen is `keyed`: its carve of `mem` holds two halves of nodes (d.nodes is halves[half], the one
+    // the session searches in; the next reopen re-roots from it into the other one) and a key per row, and its shape (rows, lo and d's
+    // n_par, node_cap, k_cap, legal_words) is what the next reopen compares before it lets `played` reach the kernel
     struct EvalPool {
         DevBuf<uint8_t> mem;
         std::vector<std::unique_ptr<TreeTable>> tables;          // E[0 .. max_sims] per (c_init, c_base, max_sims)
         XrTreeEvalDev d{};
-        int rows = 0, lo = -1, max_sims = 0, sims = 0;
-        bool open = false, pending = false;
-        void release() { mem.release(); tables.clear(); d = XrTreeEvalDev{}; rows = 0; lo = -1; max_sims = 0; sims = 0; open = false; pending = false; }
+        XrTreeNode* halves[2] = {nullptr, nullptr};
+        XrTreeKey* key = nullptr;
+        int rows = 0, lo = -1, max_sims = 0, sims = 0, half = 0;
+        bool open = false, pending = false, keyed = false;
+        void release() {
+            mem.release(); tables.clear(); d = XrTreeEvalDev{}; halves[0] = halves[1] = nullptr; key = nullptr;
+            rows = 0; lo = -1; max_sims = 0; sims = 0; half = 0; open = false; pending = false; keyed = false;
+        }
     } eval[1 + XR_MAX_GROUPS];
     int look_grid = 0;                         // workgroups of the persistent lookahead launch the chip holds at once (0: not asked yet)
     XrBatchDev dev{};
@@ -1786,6 +1794,7 @@ int32_t xr_batch_set_groups(xr_batch* b, const int32_t* bounds_host, int32_t n_g
     b->n_groups = n_groups;
     for (int g = 0; g <= n_groups; g++) b->group_bounds[g] = bounds_host[g];
     for (int g = 0; g < XR_MAX_GROUPS; g++) { b->group_bank[g] = 0; b->group_valid[g].clear(); }
+    for (xr_batch::EvalPool& ep : b->eval) ep.keyed = false;          // a keyed tree belongs to the rows of the groups it was searched under
     return XR_OK;
 }
 
@@ -2353,10 +2362,29 @@ int32_t xr_batch_tree_search_keep(xr_batch* b, int32_t group, const int32_t* pla
 
 // ---- evaluated tree search ---------------------------------------------------------------------------------------------------------
 // "XR-Tree v2, evaluated": open starts a session on the caller's pool, leaves runs one wave's select and its peek launch, backup takes
-// the evaluator's values.  The host keeps the session's shape and its place in the call order; every refusal names its entry point
-int32_t xr_batch_tree_open(xr_batch* b, int32_t group, int32_t n_par, int32_t node_cap, double c_init, double c_base, int32_t max_sims,
-                           const float* root_prior_dev, int32_t k_cap, void* stream) {
-    const char* fn = "xr_batch_tree_open";
+// the evaluator's values.  The host keeps the session's shape and its place in the call order; every refusal names its entry point.
+// "XR-Tree v2, kept": reopen starts a keyed session that may continue from the trees the pool's last keyed session left
+namespace {
+// The pool of a session in one allocation, each array starting on a 16-byte boundary: xr_batch_tree_open's nine arrays, in its order; a
+// keyed session's (xr_batch_tree_reopen) eleven — the second half of nodes after the first, the keys at the end
+struct EvalCarve { size_t half[2], rs, prefix, ret, leaf, best, legal, nlegal, prior, key, bytes; };
+EvalCarve eval_carve(const xr_batch* b, int rows, int n_par, int node_cap, int k_cap, bool keyed) {
+    Carver c;
+    const size_t R = (size_t)rows, P = (size_t)n_par, K = (size_t)k_cap, half_bytes = R * (size_t)node_cap * sizeof(XrTreeNode);
+    EvalCarve v{};
+    v.half[0] = c.take(half_bytes); v.half[1] = keyed ? c.take(half_bytes) : v.half[0]; v.rs = c.take(R * sizeof(XrTreeRow));
+    v.prefix = c.take(R * P * K * sizeof(int32_t)); v.ret = c.take(R * P * sizeof(double)); v.leaf = c.take(R * P * 2 * sizeof(int32_t));
+    v.best = c.take(R * K * sizeof(int32_t)); v.legal = c.take(R * (size_t)b->legal_words * sizeof(uint64_t));
+    v.nlegal = c.take(R * sizeof(int32_t)); v.prior = c.take(R * K * sizeof(float));
+    v.key = keyed ? c.take(R * sizeof(XrTreeKey)) : 0;
+    v.bytes = c.off;
+    return v;
+}
+
+// xr_batch_tree_open (keep false) and xr_batch_tree_reopen (keep: the session is keyed and may continue from the pool's last one; played,
+// kept_out: its two own arguments): one prologue, one carve, one table cache; fn: the entry point, named by every refusal
+int32_t eval_open_impl(xr_batch* b, const char* fn, bool keep, int32_t group, const int32_t* played_dev, int32_t n_par, int32_t node_cap, double c_init,
+                       double c_base, int32_t max_sims, const float* root_prior_dev, int32_t k_cap, int32_t* kept_out_dev, void* stream) {
     if (!b) return fail(XR_ERR_INVALID, "%s: null argument", fn);
     if (!b->loaded) return fail(XR_ERR_STATE, "%s: load regions first", fn);
     int lo, rows;
@@ -2371,41 +2399,70 @@ int32_t xr_batch_tree_open(xr_batch* b, int32_t group, int32_t n_par, int32_t no
     if (const int32_t rc = lds_field_check(b, fn)) return rc;
     const int64_t tasks = (int64_t)rows * n_par;
     if (tasks >= ((int64_t)1 << 31)) return fail(XR_ERR_RANGE, "%s: rows x n_par does not fit 31 bits", fn);
-    if (!xr_lookahead_occupancy || !xr_launch_line || !xr_launch_tree_eval_open || !xr_launch_tree_eval_select || !xr_launch_tree_eval_backup)
+    if (!xr_lookahead_occupancy || !xr_launch_line || !xr_launch_tree_eval_open || !xr_launch_tree_eval_select || !xr_launch_tree_eval_backup ||
+        (keep && !xr_launch_tree_eval_reopen))
         return fail(XR_ERR_STATE, "%s: evaluated tree search kernels not linked", fn);
     if (k_cap < 1) k_cap = 1;
-    if ((double)rows * ((double)node_cap * sizeof(XrTreeNode) + (double)n_par * (4.0 * k_cap + 16.0) + 8.0 * k_cap + 8.0 * b->legal_words + 44.0 + 160.0) > 1e15)
+    if ((double)rows * ((keep ? 2.0 : 1.0) * (double)node_cap * sizeof(XrTreeNode) + (double)n_par * (4.0 * k_cap + 16.0) + 8.0 * k_cap + 8.0 * b->legal_words +
+                        44.0 + (keep ? 24.0 : 0.0) + 160.0) > 1e15)
         return fail(XR_ERR_NOMEM, "%s: %d rows x %d nodes do not fit any device", fn, rows, node_cap);
-    Carver c;          // nine arrays in one allocation, each starting on a 16-byte boundary
-    const size_t R = (size_t)rows, P = (size_t)n_par, K = (size_t)k_cap;
-    const size_t o_nodes = c.take(R * (size_t)node_cap * sizeof(XrTreeNode)), o_rs = c.take(R * sizeof(XrTreeRow));
-    const size_t o_prefix = c.take(R * P * K * sizeof(int32_t)), o_ret = c.take(R * P * sizeof(double)), o_leaf = c.take(R * P * 2 * sizeof(int32_t));
-    const size_t o_best = c.take(R * K * sizeof(int32_t)), o_legal = c.take(R * (size_t)b->legal_words * sizeof(uint64_t));
-    const size_t o_nlegal = c.take(R * sizeof(int32_t)), o_prior = c.take(R * K * sizeof(float));
+    const EvalCarve cv = eval_carve(b, rows, n_par, node_cap, k_cap, keep);
     ShadowCall sc;          // (the peek launches of the session play in the caller's shadow slots)
     if (const int32_t rc = shadow_call(b, group, lo, rows, stream, fn, true, sc)) return rc;
     hipStream_t st = sc.st;
     xr_batch::EvalPool& ep = b->eval[group + 1];
-    ep.open = false; ep.pending = false;          // the last session ends here, whatever becomes of this call
-    if (ep.mem.n < c.off && ep.mem.alloc(c.off) != hipSuccess) {
-        ep.mem.release();
-        return fail(XR_ERR_NOMEM, "%s: hipMalloc of %zu bytes of trees failed", fn, c.off);
+    // what a reopen may keep: the trees of a keyed session of this very shape with no wave waiting for its backup (pending visits would
+    // be in its nodes); anything else, and a call without `played`, rebuilds every row: the kernel gets played == NULL
+    bool rebuild_all = !keep || !played_dev || !ep.keyed || ep.pending || ep.rows != rows || ep.lo != lo || ep.d.n_par != n_par || ep.d.node_cap != node_cap ||
+                       ep.d.k_cap != k_cap || ep.d.legal_words != b->legal_words;
+    ep.open = false; ep.pending = false; ep.keyed = false;          // the last session ends here, whatever becomes of this call
+    if (ep.mem.n < cv.bytes) {
+        rebuild_all = true;          // (a new allocation holds no tree)
+        if (ep.mem.alloc(cv.bytes) != hipSuccess) {
+            ep.mem.release();
+            return fail(XR_ERR_NOMEM, "%s: hipMalloc of %zu bytes of trees failed", fn, cv.bytes);
+        }
     }
+    // a keyed session's table runs to XR_TREE_MAX_SIMS, as the kept search's does: a carried root meets visit counts above max_sims
+    const int e_max = keep ? XR_TREE_MAX_SIMS : max_sims;
     const double* E = nullptr;
-    if (const int32_t rc = exploration_table(ep.tables, c_init, c_base, max_sims, TABLE_EXACTLY, st, fn, E)) return rc;
+    if (const int32_t rc = exploration_table(ep.tables, c_init, c_base, e_max, TABLE_EXACTLY, st, fn, E)) return rc;
     uint8_t* const m = ep.mem.p;
+    const int old_half = rebuild_all ? 1 : ep.half, new_half = keep ? old_half ^ 1 : 0;          // (nothing refuses from here on)
     XrTreeEvalDev d{};
-    d.nodes = reinterpret_cast<XrTreeNode*>(m + o_nodes); d.rs = reinterpret_cast<XrTreeRow*>(m + o_rs);
-    d.prefix = reinterpret_cast<int32_t*>(m + o_prefix); d.ret = reinterpret_cast<double*>(m + o_ret);
-    d.leaf = reinterpret_cast<int32_t*>(m + o_leaf); d.best_order = reinterpret_cast<int32_t*>(m + o_best);
-    d.legal = reinterpret_cast<uint64_t*>(m + o_legal); d.nlegal = reinterpret_cast<int32_t*>(m + o_nlegal);
-    d.prior = reinterpret_cast<float*>(m + o_prior);
+    d.nodes = reinterpret_cast<XrTreeNode*>(m + cv.half[new_half]); d.rs = reinterpret_cast<XrTreeRow*>(m + cv.rs);
+    d.prefix = reinterpret_cast<int32_t*>(m + cv.prefix); d.ret = reinterpret_cast<double*>(m + cv.ret);
+    d.leaf = reinterpret_cast<int32_t*>(m + cv.leaf); d.best_order = reinterpret_cast<int32_t*>(m + cv.best);
+    d.legal = reinterpret_cast<uint64_t*>(m + cv.legal); d.nlegal = reinterpret_cast<int32_t*>(m + cv.nlegal);
+    d.prior = reinterpret_cast<float*>(m + cv.prior);
     d.E = E;
-    d.node_cap = node_cap; d.n_par = n_par; d.k_cap = k_cap; d.e_max = max_sims; d.env_lo = lo; d.legal_words = b->legal_words;
+    d.node_cap = node_cap; d.n_par = n_par; d.k_cap = k_cap; d.e_max = e_max; d.env_lo = lo; d.legal_words = b->legal_words;
     d.has_prior = root_prior_dev ? 1 : 0;
-    XR_HIP(xr_launch_tree_eval_open(&b->dev, &d, root_prior_dev, rows, st));
+    if (keep) {
+        XrTreeKeepDev kd{};
+        kd.old_nodes = reinterpret_cast<const XrTreeNode*>(m + cv.half[old_half]);
+        kd.key = reinterpret_cast<XrTreeKey*>(m + cv.key); kd.key_legal = d.legal;          // the snapshot is the key's legal words
+        kd.played = rebuild_all ? nullptr : played_dev; kd.kept_out = kept_out_dev; kd.n_add = max_sims;
+        XR_HIP(xr_launch_tree_eval_reopen(&b->dev, &d, &kd, root_prior_dev, rows, st));
+        ep.halves[0] = reinterpret_cast<XrTreeNode*>(m + cv.half[0]); ep.halves[1] = reinterpret_cast<XrTreeNode*>(m + cv.half[1]);
+        ep.key = kd.key; ep.half = new_half;
+    } else {
+        XR_HIP(xr_launch_tree_eval_open(&b->dev, &d, root_prior_dev, rows, st));
+    }
+    ep.keyed = keep;          // (a session started by xr_batch_tree_open is not keyed: the next reopen rebuilds every row)
     ep.d = d; ep.rows = rows; ep.lo = lo; ep.max_sims = max_sims; ep.sims = 0; ep.open = true;
     return XR_OK;
+}
+}  // namespace
+
+int32_t xr_batch_tree_open(xr_batch* b, int32_t group, int32_t n_par, int32_t node_cap, double c_init, double c_base, int32_t max_sims,
+                           const float* root_prior_dev, int32_t k_cap, void* stream) {
+    return eval_open_impl(b, "xr_batch_tree_open", false, group, nullptr, n_par, node_cap, c_init, c_base, max_sims, root_prior_dev, k_cap, nullptr, stream);
+}
+
+int32_t xr_batch_tree_reopen(xr_batch* b, int32_t group, const int32_t* played_dev, int32_t n_par, int32_t node_cap, double c_init, double c_base,
+                             int32_t max_sims, const float* root_prior_dev, int32_t k_cap, int32_t* kept_out_dev, void* stream) {
+    return eval_open_impl(b, "xr_batch_tree_reopen", true, group, played_dev, n_par, node_cap, c_init, c_base, max_sims, root_prior_dev, k_cap, kept_out_dev, stream);
 }
 
 int32_t xr_batch_tree_leaves(xr_batch* b, int32_t group, uint8_t* rows_out_dev, int64_t row_bytes, int32_t region_base, int32_t* out_dev,

@@ -358,6 +358,9 @@ hipError_t xr_launch_tree_backup(const XrBatchDev* src, const XrTreeDev* t, int 
 hipError_t xr_launch_tree_keep_begin(const XrBatchDev* src, const XrTreeDev* t, const XrTreeKeepDev* k, int rows, hipStream_t st) __attribute__((weak));
 // evaluated tree search (xr_tree_eval.h).  Weak for the same reason: xr_batch_tree_open answers XR_ERR_STATE where they are not linked
 hipError_t xr_launch_tree_eval_open(const XrBatchDev* src, const XrTreeEvalDev* t, const float* root_prior, int rows, hipStream_t st) __attribute__((weak));
+// (reopen: xr_batch_tree_reopen's first kernel; k->key_legal is the pool's snapshot, t->legal)
+hipError_t xr_launch_tree_eval_reopen(const XrBatchDev* src, const XrTreeEvalDev* t, const XrTreeKeepDev* k, const float* root_prior, int rows, hipStream_t st)
+    __attribute__((weak));
 hipError_t xr_launch_tree_eval_select(const XrTreeEvalDev* t, int32_t* paths_out, int32_t* leaf_out, int rows, hipStream_t st) __attribute__((weak));
 hipError_t xr_launch_tree_eval_backup(const XrTreeEvalDev* t, const double* value, const float* leaf_prior, int sims, int32_t* visits_out, double* value_out,
                                       int32_t* info_out, int32_t* best_order_out, double* best_return_out, double* returns_out, int rows, hipStream_t st)

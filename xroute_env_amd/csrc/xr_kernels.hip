@@ -16,7 +16,7 @@
 //   xr_peek_kernel               (xr_peek.h) the state after a line of play as a packed state row: the rollout's loops, then xr_pack_state_kernel's packing
 //   xr_branch_kernel<0 / 1>      (xr_branch.h) env slots take other slots' state: parents of overwritten parents to staging, then every moved slot
 //   xr_tree_keep_begin_kernel      (xr_tree_keep.h) the first kernel of a search that continues from the played net's subtree
-//   xr_tree_eval_open / select / backup_kernel   (xr_tree_eval.h) the search whose leaves the caller's evaluator values
+//   xr_tree_eval_open / reopen / select / backup_kernel   (xr_tree_eval.h) the search whose leaves the caller's evaluator values
 //   xr_tree_reset / select / backup_kernel   (xr_tree.h) pUCT over net orderings with the tree in device memory, one wavefront per row
 //                                (xr_tree_core.h) the tree's rules, once, for the three forms above
 //   xr_random_action_kernel
@@ -2419,6 +2419,12 @@ hipError_t xr_launch_tree_keep_begin(const XrBatchDev* src, const XrTreeDev* t, 
 // evaluated tree search (xr_tree_eval.h): one wavefront per row.  select's dynamic LDS is the plain search's
 hipError_t xr_launch_tree_eval_open(const XrBatchDev* src, const XrTreeEvalDev* t, const float* root_prior, int rows, hipStream_t st) {
     hipLaunchKernelGGL(xr_tree_eval_open_kernel, dim3(rows), dim3(64), 0, st, *src, *t, root_prior);
+    return hipGetLastError();
+}
+
+hipError_t xr_launch_tree_eval_reopen(const XrBatchDev* src, const XrTreeEvalDev* t, const XrTreeKeepDev* k, const float* root_prior, int rows,
+                                      hipStream_t st) {
+    hipLaunchKernelGGL(xr_tree_eval_reopen_kernel, dim3(rows), dim3(64), 0, st, *src, *t, *k, root_prior);
     return hipGetLastError();
 }
 

@@ -7,6 +7,9 @@
 //
 //   xr_tree_eval_open_kernel     copies the env's nlegal and legal words (and the row's prior) into the pool — every later kernel of the
 //                                session reads the copy, never the env — resets the row state, makes the root and expands it
+//   xr_tree_eval_reopen_kernel   the same for a session that continues ("XR-Tree v2, kept"): checks the row's key, re-roots the last
+//                                session's tree below the played net into the pool's other half (xr_tree_keep.h's functions), keeps it
+//                                whole, or rebuilds the row as the open kernel does; then the snapshot, the row prior and the new key
 //   xr_tree_eval_select_kernel   the descent for the n_par lanes of a wave, one after the other; a fresh leaf is expanded here under the
 //                                open call's row prior; writes the paths (the prefix of the peek launch) and the leaf records
 //   xr_tree_eval_backup_kernel   simulations in lane order: G = the line's return (+ the evaluator's value unless the leaf is terminal),
@@ -38,6 +41,55 @@ __global__ void __launch_bounds__(64) xr_tree_eval_open_kernel(XrBatchDev src, X
     __syncthreads();          // the copies and the root, before every lane reads them
     if (nl0 <= 0) return;          // a done env: no tree, no simulation
     xr_tree_expand_block(v, 0, legal, nullptr, nl0, t.has_prior ? t.prior + (int64_t)row * k_cap : nullptr);
+}
+
+// The first kernel of a session that continues ("XR-Tree v2, kept"): xr_tree_keep_begin_kernel's work on this pool.  t.nodes is the half
+// the new session searches in, kp.old_nodes the half the last one searched in; the key's legal words are the last session's snapshot
+// (kp.key_legal == t.legal), read before this kernel overwrites them with the env's current words.  A rebuilt row ends exactly as
+// xr_tree_eval_open_kernel leaves it.
+__global__ void __launch_bounds__(64) xr_tree_eval_reopen_kernel(XrBatchDev src, XrTreeEvalDev t, XrTreeKeepDev kp, const float* __restrict__ root_prior) {
+#pragma clang fp contract(off)
+    const int row = blockIdx.x, lane = threadIdx.x;
+    const int e = t.env_lo + row;
+    const int words = t.legal_words, k_cap = t.k_cap;
+    XrTreeRow* const rs = t.rs + row;
+    XrTreeNode* const nodes = t.nodes + (int64_t)row * t.node_cap;
+    const XrTreeView v = {nodes, rs, t.node_cap, k_cap, words, lane};
+    const XrTreeNode* const old = kp.old_nodes + (int64_t)row * t.node_cap;
+    XrTreeKey* const key = kp.key + row;
+    uint64_t* const snap = kp.key_legal + (int64_t)row * words;
+    const uint64_t* const legal = src.legal + (int64_t)e * words;
+    int nl0 = __builtin_amdgcn_readfirstlane(src.nlegal[e]);
+    if (nl0 > k_cap) nl0 = k_cap;          // (never: nlegal <= k_max <= k_cap)
+    const int64_t steps = src.env_steps[e];
+    const int region = src.env_region[e], replay = src.env_replay[e];
+    // 1. the key against the env, 2. the tree: the kept search's rules
+    int child, used_old;
+    const int a = kp.played ? __builtin_amdgcn_readfirstlane(kp.played[row]) : -1;
+    const int mode = xr_tree_keep_mode(old, rs, key, snap, legal, words, a, nl0, steps, region, replay, t.node_cap, kp.n_add, lane, child, used_old);
+    int kept_n, kept_nodes;
+    xr_tree_keep_build(v, old, mode, child, used_old, nl0, src.reward + e, kept_n, kept_nodes);
+    // 3. the session's snapshot (the next key's legal words), its row prior, an empty best line
+    for (int wd = lane; wd < words; wd += 64) snap[wd] = legal[wd];
+    for (int k = lane; k < k_cap; k += 64) {
+        t.best_order[(int64_t)row * k_cap + k] = 0;
+        t.prior[(int64_t)row * k_cap + k] = root_prior ? root_prior[(int64_t)row * k_cap + k] : 0.0f;
+    }
+    if (lane == 0) t.nlegal[row] = nl0;
+    __syncthreads();          // the copies, before every lane reads them
+    // 4. an unexpanded root (a rebuilt row's, or a kept child no simulation has left yet) gets its children under this call's prior
+    if (nl0 > 0 && __builtin_amdgcn_readfirstlane(nodes[0].first) < 0)
+        xr_tree_expand_block(v, 0, snap, nullptr, nl0, t.has_prior ? t.prior + (int64_t)row * k_cap : nullptr);
+    // 5. the key of the state this tree belongs to
+    if (lane == 0) {
+        XrTreeKey k;
+        k.env_steps = steps; k.region = region; k.replay = replay; k.valid = 1; k.pad = 0;
+        *key = k;
+        if (kp.kept_out) {
+            kp.kept_out[(int64_t)row * 2] = kept_n;
+            kp.kept_out[(int64_t)row * 2 + 1] = kept_nodes;
+        }
+    }
 }
 
 // dynamic LDS: XrTreePath

@@ -7,7 +7,9 @@ synchronisation.  An evaluator is a callable `evaluate(batch, leaves, group=None
 leaf_prior float32 [rows, n_par, k_max] or None)`; `leaves` is tree_leaves()'s dict (the packed state row of every leaf, the line
 returns, the paths, the leaf records).  `critic_evaluator` values a leaf by an ActorCritic's critic over the obstacle tower of the
 leaf's state; `actor_critic_evaluator` adds the softmax of the actor's logits over the leaf's legal nets as the prior of its children.
-`evaluated_episodes` plays whole episodes with it, as envs.tree.tree_episodes does with the rollout search.
+`evaluated_episodes` plays whole episodes with it, as envs.tree.tree_episodes does with the rollout search.  With keep / reuse the
+sessions are "XR-Tree v2, kept" (RegionBatch.tree_open(keep=True, played=...)): a ply's session continues from the subtree below the net
+just stepped.
 """
 from __future__ import annotations
 
@@ -22,8 +24,11 @@ from .vector_env import XRouteVectorEnv
 
 def evaluated_search(batch: RegionBatch, evaluate: Callable, n_waves: int, n_par: int, root_prior: Optional[torch.Tensor] = None,
                      node_cap: Optional[int] = None, c_init: float = 1.25, c_base: float = 19652.0, group: Optional[int] = None, stream=None,
-                     trace: bool = False):
+                     trace: bool = False, keep: bool = False, played: Optional[torch.Tensor] = None):
     """n_waves waves of n_par evaluated simulations per row from the state every env is in now; the batch is left exactly as it was.
+    keep=True: the kept session (RegionBatch.tree_open(keep=True, played=...), "XR-Tree v2, kept"): it continues from the tree the
+    caller's last kept session left where `played` says how the envs have moved since, and the dict gains `kept` int32 [rows, 2] =
+    {visits of the new root carried in, nodes carried}.
     Returns tree_backup()'s dict after the last wave {visits, value, info, best_order, best_return, returns}; with trace=True `paths`
     int32 [rows, n_waves * n_par, k_max], `returns` float64 [rows, n_waves * n_par] and `leaf` int32 [rows, n_waves * n_par, 2] hold
     every simulation in (wave, lane) order.  Nothing here reads a device value on the host: whether the loop synchronises is up to
@@ -33,7 +38,12 @@ def evaluated_search(batch: RegionBatch, evaluate: Callable, n_waves: int, n_par
         raise ValueError(f"n_waves must be >= 1, got {n_waves}")
     if not callable(evaluate):
         raise ValueError("evaluate must be a callable (batch, leaves, group=, stream=) -> (value, leaf_prior or None)")
-    batch.tree_open(P, W * P, root_prior, node_cap, c_init, c_base, group=group, stream=stream)
+    if played is not None and not keep:
+        raise ValueError("played needs keep=True")
+    if keep:
+        carried = batch.tree_open(P, W * P, root_prior, node_cap, c_init, c_base, group=group, stream=stream, keep=True, played=played)
+    else:
+        batch.tree_open(P, W * P, root_prior, node_cap, c_init, c_base, group=group, stream=stream)
     res, kept = None, {"paths": [], "returns": [], "leaf": []}
     with torch.cuda.stream(stream if stream is not None else torch.cuda.current_stream(batch.device)):
         for _ in range(W):
@@ -44,6 +54,8 @@ def evaluated_search(batch: RegionBatch, evaluate: Callable, n_waves: int, n_par
                 kept["paths"].append(leaves["paths"]); kept["returns"].append(res["returns"]); kept["leaf"].append(leaves["leaf"])
         if trace:
             res = dict(res, **{k: torch.cat(v, dim=1) for k, v in kept.items()})
+    if keep:
+        res = dict(res, kept=carried)
     return res
 
 
@@ -122,14 +134,17 @@ def actor_critic_evaluator(model, policy=None, groups=None) -> Callable:
 
 def evaluated_episodes(regions: Sequence, evaluate, n_waves: int, n_par: int, device="cuda:0", root_prior: Optional[Callable] = None,
                        node_cap: Optional[int] = None, c_init: float = 1.25, c_base: float = 19652.0, stats: Optional[dict] = None,
-                       **batch_kw) -> List[dict]:
+                       reuse: bool = False, waves_after: Optional[int] = None, **batch_kw) -> List[dict]:
     """Play every region's episode by evaluated tree search, all regions at once (one slot per region): at every ply one session of
     n_waves x n_par simulations per env, then the most visited child of the root is stepped (ties to the higher value, then to the lower
     net).  evaluate: an evaluator (critic_evaluator, actor_critic_evaluator, or any callable of their form).  Returns per region {"order": the nets played, "ret": the episode's return (the step rewards
     summed in step order in double), "best_order": the best complete ordering a terminal simulation of any ply saw (the order played
     where none did), "best_ret": its return, "simulations": the simulations run}.  root_prior: None, or a callable (batch) -> float32
     [n_envs, k_max] asked before every search.  stats: an optional dict that receives "routed_nets", the nets the simulations routed
-    (the sum of their path lengths), and "plies"."""
+    (the sum of their path lengths), and "plies".  reuse: search, step, reopen with the actions just stepped ("XR-Tree v2, kept"): the
+    session of a ply continues from the subtree below the net the env has played; one node_cap serves every ply (default 1 + 4 *
+    (n_waves * n_par + 1) * k_max), and stats also receives "carried_visits" and "carried_nodes", the sums over plies and regions of
+    what the kept trees brought along.  waves_after: the waves of every ply but the first (default n_waves)."""
     R = len(regions)
     if R < 1:
         raise ValueError("evaluated_episodes needs at least one region")
@@ -147,6 +162,10 @@ def evaluated_episodes(regions: Sequence, evaluate, n_waves: int, n_par: int, de
         sims = torch.zeros(R, dtype=torch.int64, device=dev)
         routed = torch.zeros((), dtype=torch.int64, device=dev)
         live_plies = 0
+        carried = torch.zeros(2, dtype=torch.int64, device=dev)
+        played = None
+        if reuse and node_cap is None:          # one pool shape for every ply, with room for what the trees carry along
+            node_cap = 1 + 4 * (int(n_waves) * int(n_par) + 1) * K
         from ..dist import unpack_records
         for ply in range(K + 1):
             nl = b.fetch("nlegal")
@@ -154,7 +173,11 @@ def evaluated_episodes(regions: Sequence, evaluate, n_waves: int, n_par: int, de
                 break
             if ply >= K:
                 raise RuntimeError("evaluated_episodes: nets left after k_max plies")
-            res = evaluated_search(b, ev, n_waves, n_par, root_prior(b) if root_prior is not None else None, node_cap, c_init, c_base, trace=True)
+            waves = int(n_waves) if ply == 0 or waves_after is None else int(waves_after)
+            res = evaluated_search(b, ev, waves, n_par, root_prior(b) if root_prior is not None else None, node_cap, c_init, c_base, trace=True,
+                                   keep=reuse, played=played)
+            if reuse:
+                carried += res["kept"].to(torch.int64).sum(dim=0)
             live_plies += int((nl > 0).sum())
             act = XRouteVectorEnv._most_visited(res)
             line = res["best_return"] + ret
@@ -170,12 +193,15 @@ def evaluated_episodes(regions: Sequence, evaluate, n_waves: int, n_par: int, de
             live = act > 0
             ret = torch.where(live, ret + rec["reward"], ret)
             order[:, ply] = act
+            played = act if reuse else None
         played_better = ret > best_ret                       # (no terminal simulation, or none as good as the line played)
         best_order = torch.where(played_better.unsqueeze(1), order, best_order)
         best_ret = torch.where(played_better, ret, best_ret)
         if stats is not None:
             stats["routed_nets"] = int(routed)
             stats["plies"] = live_plies
+            if reuse:
+                stats["carried_visits"], stats["carried_nodes"] = (int(v) for v in carried.cpu().tolist())
         ret_h, order_h, bret_h, border_h, sims_h = ret.cpu(), order.cpu(), best_ret.cpu(), best_order.cpu(), sims.cpu()
         return [{"order": [int(v) for v in order_h[r].tolist() if v > 0], "ret": float(ret_h[r]),
                  "best_order": [int(v) for v in border_h[r].tolist() if v > 0], "best_ret": float(bret_h[r]), "simulations": int(sims_h[r])}

@@ -316,9 +316,11 @@ class XRouteVectorEnv:
         return res
 
     def tree_open(self, n_par: int, max_sims: int, root_prior: Optional[torch.Tensor] = None, node_cap: Optional[int] = None,
-                  c_init: float = 1.25, c_base: float = 19652.0, group: Optional[int] = None) -> None:
-        """RegionBatch.tree_open: start an evaluated-tree session from the state the envs (of the group) are in now."""
-        return self._tree_eval_call("tree_open", group, n_par, max_sims, root_prior, node_cap, c_init, c_base)
+                  c_init: float = 1.25, c_base: float = 19652.0, group: Optional[int] = None, keep: bool = False,
+                  played: Optional[torch.Tensor] = None) -> Optional[torch.Tensor]:
+        """RegionBatch.tree_open: start an evaluated-tree session from the state the envs (of the group) are in now.  keep, played: the
+        kept session (xr_batch_tree_reopen): it continues where `played` says how its envs have moved, and returns `kept`."""
+        return self._tree_eval_call("tree_open", group, n_par, max_sims, root_prior, node_cap, c_init, c_base, keep=keep, played=played)
 
     def tree_leaves(self, region_base: int = 0, row_bytes: Optional[int] = None, group: Optional[int] = None):
         """RegionBatch.tree_leaves's dict {rows, out, ret, paths, leaf}: one wave's leaves as packed state rows."""
